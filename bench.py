@@ -19,9 +19,17 @@ call; rank 0 prints the JSON line.  The workload is config 4 (10k queries) unles
                  collective on the data path: "scaling": "weak".
 
 Prints one JSON line on rank 0 (schema in the task contract) with a "roofline" object for the
-search kernel (algorithmic bytes from the kernel's own counters / HIP-event kernel time) and a
-"cpu_baseline" object (the CPU restatement of the reference's coroutine batch_search, oracle/,
-timed on this host at the same ef -- test infrastructure, never the product path).
+search kernel (algorithmic bytes from the kernel's own counters / HIP-event kernel time).
+
+A plain run does what `value` needs and no more: data, graph, ground truth and the ef sweep, the
+warm-up, the --steps timed steps, the result line.  --full adds every other leg, each reported
+beside `value` and never part of it: the "cpu_baseline" object (the CPU restatement of the
+reference's coroutine batch_search, oracle/, timed on this host at the same ef -- test
+infrastructure, never the product path), "pcie_inclusive", "batch_tail", the measured streaming-read
+peak of the roofline, the float64 spot checks of the ground truth and of the flat workload and,
+for N > 1, the layouts leg.
+--dump-outputs DIR writes what the last timed step returned (DIR/ids.npy, DIR/dists.npy; flat:
+also DIR/flags.npy) on rank 0; the inputs are seeded, so two builds can be compared array by array.
 """
 
 from __future__ import annotations
@@ -120,6 +128,11 @@ def parse():
     p.add_argument("--workload", choices=tuple(WORKLOADS) + ("flat",), default="gist-hnsw",
                    help="gist-hnsw: the BASELINE metric (default); sift-hnsw: config 3; sq8-ip: config 5 "
                         "shape (768-d IP, SQ8 search + rerank); flat: config 2, 1M x 128 exact k-NN")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs reported beside value: CPU baseline, PCIe-inclusive rate, batch tail, "
+                        "measured HBM peak, float64 spot checks (ground truth, flat), N>1 layouts leg")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write the last step's results as DIR/<name>.npy (float32 / float64)")
     p.add_argument("--sweep-qps", action="store_true",
                    help="also time every ef of the sweep (config 3 reports the whole QPS/recall curve)")
     a = p.parse_args()
@@ -187,6 +200,29 @@ def host_info():
     q = _cgroup_cpus()
     return {"nproc": os.cpu_count(), "affinity": _affinity(), "cgroup_cpus": None if q is None else round(q, 2),
             "threads_used": host_threads(), "cpu_model": model}
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays):
+    """Write the timed path's last results as dirpath/<name>.npy: integers as float64 (ids and the
+    0xffffffff empty slot are exact), floats as float32.  Every array has one row per query; past
+    64 MB in all, a fixed seeded sample of the rows is kept (its row numbers in rows.npy)."""
+    os.makedirs(dirpath, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        out[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    n_rows = next(iter(out.values())).shape[0]
+    per_row = sum(a.nbytes // max(1, n_rows) for a in out.values()) + 8
+    if per_row * n_rows > DUMP_CAP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, DUMP_CAP_BYTES // per_row, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    log("outputs", {name: list(a.shape) for name, a in out.items()}, "->", dirpath)
 
 
 def spawn_ranks(n):
@@ -290,14 +326,18 @@ def f64_topk(base, ys, k=K, chunk=32768):
     return [np.lexsort((np.arange(d.shape[1]), d[i]))[:k] for i in range(d.shape[0])]
 
 
-def exact_gt_flat(native, base, queries, device, k=K):
+def exact_gt_flat(native, base, queries, device, k=K, check=True):
     """Exact top-k for L2 from the engine's own flat path (find_exact_gt's f32 metric, evaluate.hpp:29-62,
     ties by id; queries whose shortlist bound fails are recomputed exhaustively), cross-checked in
-    float64 on 1% of the queries, at most 16.  Returns (ids, f64 sample agreement)."""
+    float64 on 1% of the queries, at most 16, unless check is False (a plain bench run).
+    Returns (ids, f64 sample agreement or None)."""
     fi = native.DeviceIndex(device)
     fi.set_base(base, 0)
     ids, _, redo = fi.flat_search(queries, k)
     del fi
+    if not check:
+        log(f"ground truth: flat path, {redo} queries recomputed")
+        return ids.astype(np.int64), None
     rng = np.random.default_rng(0)
     sample = rng.choice(queries.shape[0], min(16, max(1, queries.shape[0] // 100)), replace=False)
     ref = f64_topk(base, queries[sample], k)
@@ -418,12 +458,17 @@ def run_flat(args):
     elapsed = time.perf_counter() - t0
     ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     n_flag = int(flags.sum().item())
-    # exactness spot check against float64 on a sample (ties aside)
-    sample = np.random.default_rng(0).choice(nq, 16, replace=False)
     got = ids.cpu().numpy()
-    ok = 0
-    for r, qi in zip(f64_topk(base, queries[sample], K), sample):
-        ok += int(set(r.tolist()) == set(got[qi].tolist()))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ids": got, "dists": dists.cpu().numpy(), "flags": flags.cpu().numpy()})
+    # exactness spot check against float64 on a sample (ties aside)
+    spot = None
+    if args.full:
+        sample = np.random.default_rng(0).choice(nq, 16, replace=False)
+        ok = 0
+        for r, qi in zip(f64_topk(base, queries[sample], K), sample):
+            ok += int(set(r.tolist()) == set(got[qi].tolist()))
+        spot = f"{ok}/{len(sample)}"
     flops = 2.0 * n * nq * dim
     tf = flops / (ms * 1e-3) / 1e12
     # the roofline is the issued contraction's own MFMA peak (alaya_index_flat_last_contraction):
@@ -446,7 +491,7 @@ def run_flat(args):
             traffic, tsrc = t, os.path.relpath(tpath, ROOT)
             break
     cpu = None
-    if not args.no_cpu_baseline:  # find_exact_gt restated (oracle/), a bounded sample of the queries
+    if args.full and not args.no_cpu_baseline:  # find_exact_gt restated (oracle/), a bounded sample of the queries
         import oracle
 
         oracle.build()
@@ -467,7 +512,7 @@ def run_flat(args):
         "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": data,
         "config": {"workload": f"flat-{n // 1000}k-{dim}-l2-{nq}q", "n_base": n, "n_queries": nq, "dim": dim, "k": K,
-                   "flagged_queries": n_flag, "exact_vs_f64_sample": f"{ok}/{len(sample)}"},
+                   "flagged_queries": n_flag, "exact_vs_f64_sample": spot},
         "roofline": {"bound": "mfma", "achieved": round(tf, 2), "peak": mfma_peak, "unit": "TFLOP/s",
                      "frac": round(tf / mfma_peak, 4),
                      "traffic": round(traffic["traffic_bytes_per_launch"] / (ms * 1e-3) / 1e9, 1) if traffic else None,
@@ -612,7 +657,7 @@ def main():
                     "top-10 merged by (float64 distance, id) on rank 0")
     elif rank == 0:
         if metric == 0:
-            gt, gt_check = exact_gt_flat(native, base, queries, local)
+            gt, gt_check = exact_gt_flat(native, base, queries, local, check=args.full)
         else:  # IP (config 5): fp32 GEMM shortlist + float64 re-rank
             base_dev = torch.from_numpy(base).to(dev)
             gt = exact_gt(torch, base_dev, q_all, base, queries, metric=metric)
@@ -644,6 +689,8 @@ def main():
     else:
         ef = choose_ef(probe)
 
+    last = [ids_dev, dists_dev]  # what the latest timed step returned to its caller
+
     def timed(ef_t, steps, warmup):
         for _ in range(warmup):
             step(ef_t)
@@ -658,7 +705,7 @@ def main():
             ev[i][1].record(stream)
             if shard_mode:
                 # exchange + merge of the same step (the search above is the per-shard kernel)
-                exchange_and_merge(ids_dev, dists_dev, lo, K, group)
+                last[:] = exchange_and_merge(ids_dev, dists_dev, lo, K, group)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -689,8 +736,8 @@ def main():
         sync_elapsed = elapsed
         reserve = args.exchange_cus if args.exchange_cus >= 0 else (
             8 if (world > 1 and dist.get_backend() == "nccl") else 0)
-        elapsed, pipe_search_ms = timed_pipeline(torch, dist, dev, ef, args.steps, args.warmup, index, lo, use_sq8,
-                                                 q_dev, nq, group, reserve)
+        elapsed, pipe_search_ms, last[:] = timed_pipeline(torch, dist, dev, ef, args.steps, args.warmup, index, lo,
+                                                          use_sq8, q_dev, nq, group, reserve)
         exch_ms = timed_exchange(torch, dist, ids_dev, dists_dev, lo, args.steps, group)
         overlap = {"ms_per_step": round(elapsed / args.steps * 1e3, 4),
                    "sync_ms_per_step": round(sync_elapsed / args.steps * 1e3, 4),
@@ -699,11 +746,18 @@ def main():
                    "bound_ms": round(max(pipe_search_ms, exch_ms), 4), "reserved_cus": reserve,
                    "note": "value = the overlapped steps; sync = search then exchange in one stream per step"}
         log("overlap", overlap)
+    if args.dump_outputs:
+        out_i, out_d = last
+        if shard_mode and lay.groups > 1:  # every query group's merged rows, in query order
+            out_i, out_d = gather_layout_results(out_i, out_d, lay, nq_total, dist)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"ids": out_i.cpu().numpy(), "dists": out_d.cpu().numpy()})
 
     # ---- PCIe-inclusive rate (reported beside value, never value): the host-buffer API's work --
     # queries H2D from pinned host memory, the search, ids + distances D2H, each step synchronised
     pcie = None
-    if world == 1:
+    if world == 1 and args.full:
         q_host = torch.from_numpy(queries).pin_memory()
         ids_host = torch.empty((nq, K), dtype=torch.int32).pin_memory()
         d_host = torch.empty((nq, K), dtype=torch.float32).pin_memory()
@@ -730,7 +784,7 @@ def main():
     # launch, so the tail -- the last queries' searches running on an emptying GPU -- is amortised
     # over four batches' work ("the tail").  Kernel sustained rate vs batch rate.
     tail = None
-    if world == 1 and not args.no_tail_probe:
+    if world == 1 and args.full and not args.no_tail_probe:
         q4 = q_dev.repeat(4, 1).contiguous()
         i4 = torch.empty((4 * nq, K), dtype=torch.int32, device=dev)
         d4 = torch.empty((4 * nq, K), dtype=torch.float32, device=dev)
@@ -782,14 +836,14 @@ def main():
     if args.dump_counters and rank == 0:
         np.save(args.dump_counters, cnt)
     # measured streaming-read ceiling of this GPU (reported beside the 8 TB/s vendor figure)
-    measured_peak = native.hbm_stream_read(local, 4 << 30, 5) if rank == 0 else 0.0
+    measured_peak = native.hbm_stream_read(local, 4 << 30, 5) if (rank == 0 and args.full) else None
 
     units_per_step = nq_total * (world if (world > 1 and args.mode == "replica") else 1)
     value = units_per_step * args.steps / elapsed
 
     # ---- layouts leg (N>1 shard mode): the other S-shard x N/S-query-group layouts -------------
     layouts = None
-    if shard_mode and args.layouts != "none" and not args.no_replica_leg:
+    if shard_mode and args.full and args.layouts != "none" and not args.no_replica_leg:
         others = ([s_ for s_ in range(1, world + 1) if world % s_ == 0 and s_ != lay.shards]
                   if args.layouts == "auto" else [int(x) for x in args.layouts.split(",")])
         layouts = []
@@ -801,7 +855,7 @@ def main():
 
     # ---- CPU baseline: the reference's coroutine batch_search restated (oracle/) --------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, graph, base, queries, ef, metric, sq8, ids_dev.cpu().numpy().astype(np.uint32))
         log("cpu baseline", cpu)
 
@@ -845,11 +899,12 @@ def main():
                        "ground_truth": (gt_check if base is None else
                                         ("engine flat path (f32 metric of find_exact_gt), float64 top-10 sets "
                                          f"equal on {gt_check} sampled queries") if gt_check else
+                                        "engine flat path (f32 metric of find_exact_gt)" if metric == 0 else
                                         "fp32 GEMM shortlist of 64, float64 re-rank")},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "measured_peak": round(measured_peak, 1),
-                         "frac_measured": round(achieved / measured_peak, 4),
+                         "measured_peak": round(measured_peak, 1) if measured_peak else None,
+                         "frac_measured": round(achieved / measured_peak, 4) if measured_peak else None,
                          "measured_peak_source": "alaya_hbm_stream_read: best streaming read of 4 GiB (3 load "
                                                  "shapes x 2 occupancies x 5 runs), this GPU, this run",
                          "traffic": traffic["gbs"] if traffic else None,
@@ -894,7 +949,7 @@ def timed_pipeline(torch, dist, dev, ef, steps, warmup, index, lo, use_sq8, q_de
     """K shard steps through ShardPipeline (double-buffered: the search of step i+1 overlaps the
     exchange of step i; `reserve` CUs left to the exchange stream); barrier + synchronize on both
     sides, max over ranks.  Returns (seconds, mean search ms inside the pipeline, from a second
-    untimed pass with events)."""
+    untimed pass with events, the last timed step's merged ids and distances)."""
     from alayalite_amd.sharded import ShardPipeline, shard_search
 
     fn = lambda q, i, d, c, s: shard_search(index, lo, use_sq8, q, K, ef, i, d, c, s)  # noqa: E731
@@ -904,7 +959,7 @@ def timed_pipeline(torch, dist, dev, ef, steps, warmup, index, lo, use_sq8, q_de
     dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    pipe.run([q_dev] * steps)
+    merged = pipe.run([q_dev] * steps)[-1]
     torch.cuda.synchronize()
     dist.barrier()
     el = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
@@ -917,7 +972,7 @@ def timed_pipeline(torch, dist, dev, ef, steps, warmup, index, lo, use_sq8, q_de
     tp.close()
     sm = torch.tensor([tp.search_ms()], device=dev, dtype=torch.float64)
     dist.all_reduce(sm, op=dist.ReduceOp.MAX)
-    return el.item(), sm.item()
+    return el.item(), sm.item(), list(merged)
 
 
 def timed_exchange(torch, dist, ids_dev, dists_dev, lo, steps, group=None):

@@ -47,6 +47,38 @@ def test_exact_gt_chunked_equals_brute_force(metric, chunk):
     assert np.array_equal(got, np.array(ref))
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_dtypes_and_cap(tmp_path, monkeypatch):
+    ids = np.array([[3, -1], [7, 2 ** 31 - 1], [0, 5]], np.int32)
+    dists = np.array([[0.5, np.finfo(np.float32).max], [1.5, 2.5], [0.0, 1.0]], np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"ids": ids, "dists": dists})
+    got_i, got_d = np.load(tmp_path / "a" / "ids.npy"), np.load(tmp_path / "a" / "dists.npy")
+    assert got_i.dtype == np.float64 and np.array_equal(got_i, ids)
+    assert got_d.dtype == np.float32 and np.array_equal(got_d.view(np.uint32), dists.view(np.uint32))
+    assert sorted(os.listdir(tmp_path / "a")) == ["dists.npy", "ids.npy"]
+    # past the cap: the same seeded rows of every array, twice the same, within the cap
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 2 * (16 + 8 + 8))
+    for name in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / name), {"ids": ids, "dists": dists})
+    rows = np.load(tmp_path / "b" / "rows.npy").astype(np.int64)
+    assert len(rows) == 2 and np.array_equal(np.load(tmp_path / "b" / "ids.npy"), ids[rows])
+    assert np.array_equal(np.load(tmp_path / "b" / "dists.npy"), dists[rows])
+    total = 0
+    for f in os.listdir(tmp_path / "b"):
+        a, b = np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)
+        assert np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= bench.DUMP_CAP_BYTES
+
+
 def test_pmc_traffic_picks_nearest_ef(tmp_path, monkeypatch):
     for r, ef in (("r01", 400), ("r02", 380)):
         d = tmp_path / "profiles" / r
