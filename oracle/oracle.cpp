@@ -613,7 +613,11 @@ double orc_exact_gt(const float *base, uint64_t n, uint32_t dim, const float *qu
         const float *row = base + j * dim;
         dists.emplace_back(static_cast<uint32_t>(j), avx2 ? orc_l2_f32_avx2(q, row, dim) : orc_l2_f32(q, row, dim));
       }
-      std::sort(dists.begin(), dists.end(), [](const auto &a, const auto &b) { return a.second < b.second; });
+      // find_exact_gt sorts by distance alone with an unstable std::sort, so its order among equal
+      // distances is unpinned; (distance, id) is one of its possible outputs and is the device's order
+      std::sort(dists.begin(), dists.end(), [](const auto &a, const auto &b) {
+        return a.second < b.second || (a.second == b.second && a.first < b.first);
+      });
       for (uint32_t j = 0; j < k && j < dists.size(); ++j) ids[i * k + j] = dists[j].first;
     }
   };

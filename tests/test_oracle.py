@@ -144,3 +144,21 @@ def test_exact_gt_restatement(orc):
     for i in range(q.shape[0]):
         d = np.array([orc.l2(q[i], base[j]) for j in range(base.shape[0])], np.float32)
         assert set(ids[i].tolist()) == set(np.argsort(d, kind="stable")[:10].tolist())
+
+
+def test_exact_gt_orders_ties_by_id(orc):
+    """Equal distances come out by ascending id: find_exact_gt's unstable std::sort leaves their
+    order open, and (distance, id) is the flat search's contract.  Integer rows in 0..3 make every
+    distance an exact small integer, so each query has long runs of ties across the k-th place."""
+    rng = np.random.default_rng(12)
+    base = rng.integers(0, 4, (3000, 24)).astype(np.float32)
+    q = rng.integers(0, 4, (16, 24)).astype(np.float32)
+    k = 40
+    ids, _ = orc.exact_gt(base, q, k, 4)
+    n_tied = 0
+    for i in range(q.shape[0]):
+        d = np.array([orc.l2(q[i], base[j]) for j in range(base.shape[0])], np.float32)
+        order = np.lexsort((np.arange(base.shape[0]), d))
+        assert np.array_equal(ids[i], order[:k].astype(np.uint32)), i
+        n_tied += int(d[order[k - 1]] == d[order[k]])
+    assert n_tied >= 8  # the k-th place itself is tied on most queries: the id order decides the set
