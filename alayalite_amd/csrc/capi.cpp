@@ -20,6 +20,7 @@
 #include "hnsw_build.h"
 #include "flat_kernels.h"
 #include <cstdlib>
+#include "screen_bound.h"
 #include "search_kernels.h"
 
 using alaya_amd::HostGraph;
@@ -132,6 +133,14 @@ struct alaya_index {
   int helpers_mode = -1;          // distance helpers: -1 automatic, 0 off, 1 on (alaya_index_set_helpers)
   DevBuf help_stats;              // per searcher of the last helper launch: (memo distances, memo expansions)
   uint64_t help_stats_slots = 0;
+  // candidate screen of the wide-row f32 L2 graph search: the rows as f16 and, per row, an upper
+  // bound on ||x - f16(x)|| (alaya_amd::launch_screen_rows).  Built at the first search that uses it,
+  // kept current by row writes, freed with the base it describes.
+  DevBuf screen_rows, screen_err, screen_stats;
+  uint64_t screen_cap = 0;        // rows the two buffers hold
+  bool screen_ready = false;      // rows [0, n) are current
+  bool screen_failed = false;     // the buffers could not be allocated for this base: plain kernel
+  uint64_t screen_stats_slots = 0;  // searchers of the last launch, 0 = it did not screen
   uint32_t last_grid = 0, last_waves = 0;  // the last search launch's workgroups and waves per workgroup
   int visited_mode_override = 0;  // 0 auto, 1 compact 16-bit slots, 2 wide 32-bit slots,
                                   // 3 compact with probes capped at 2 (exercises the probe spill)
@@ -429,6 +438,8 @@ int stream_cus(const alaya_index *ix, hipStream_t s) {
   return c > 0 && c <= ix->num_cus ? c : ix->num_cus;
 }
 
+bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStream_t stream);
+
 void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef,
                uint32_t *d_ids, float *d_dists, uint32_t *d_cnt, hipStream_t stream,
                uint64_t *d_stamps = nullptr, bool sq8 = false, uint32_t fill_id = 0) {
@@ -495,6 +506,13 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
       p.two_waves = (nq > resident1 && 2 * nq <= 3 * resident1) ? 1u : 0u;
     }
   }
+  // candidate screen on an f16 row copy (wide f32 L2 rows); it selects the kernel, so it is decided
+  // before the launch shape
+  p.screen = ensure_screen(ix, p, !sq8 && !p.help && d_stamps == nullptr, stream) ? 1u : 0u;
+  if (p.screen) {
+    p.screen_rows = ix->screen_rows.as<uint16_t>();
+    p.screen_err = ix->screen_err.as<float>();
+  }
   // waves per workgroup: never more than the batch needs (helpers: always 4).  A plan with helpers
   // that does not fit (the memo, or four waves' LDS with a forced large visited table) falls back
   // to the search without them.
@@ -549,11 +567,68 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
     ix->help_stats.reserve(ix->help_stats_slots * 12);
     p.help_stats = ix->help_stats.as<uint32_t>();
   }
+  ix->screen_stats_slots = 0;
+  if (p.screen) {
+    ix->screen_stats_slots = static_cast<uint64_t>(grid) * W;
+    ix->screen_stats.reserve(ix->screen_stats_slots * 8);
+    p.screen_stats = ix->screen_stats.as<uint32_t>();
+  }
   ix->work.reserve(4);
   p.work_counter = ix->work.as<uint32_t>();
   hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
   hip_check(alaya_amd::launch_search(p, grid, W, lds, stream), "search launch");
   scratch_release(ix, stream);
+}
+
+// Default of ALAYA_SEARCH_SCREEN per kernel width: on where the screened search measured faster on
+// MI355X against the plain kernel (GIST-shaped 1k queries, d = 512 +7 %,
+// 768 +12 %, 960 +29 %, 1024 +27 %; the two-waves-per-SIMD batches +18 % / +41 %) -- every width
+// that has a screening kernel.
+bool screen_default(uint32_t dim) { return dim == 512 || dim == 768 || dim == 960 || dim == 1024; }
+
+// Whether this launch screens: the shape has a screening kernel, ALAYA_SEARCH_SCREEN (0 / 1, read per
+// launch; unset = screen_default) allows it, and the f16 copy exists or can be built now, on the
+// search's stream.  An allocation failure is not an error: the search runs the plain kernel.
+bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStream_t stream) {
+  if (!eligible || !alaya_amd::search_has_screen(ix->dim, p.sq8_order, ix->generic, p.ip)) return false;
+  const char *e = std::getenv("ALAYA_SEARCH_SCREEN");
+  if (!(e && e[0] ? std::atoi(e) != 0 : screen_default(ix->dim))) return false;
+  if (ix->screen_ready) return true;
+  if (ix->screen_failed) return false;
+  const uint64_t rows = std::max<uint64_t>(std::max(ix->capacity, ix->n), 1);
+  try {
+    if (rows > ix->screen_cap) {
+      ix->screen_rows.release();
+      ix->screen_err.release();
+      ix->screen_cap = 0;
+      ix->screen_rows.reserve(rows * ix->stride * 2);
+      ix->screen_err.reserve(rows * 4);
+      ix->screen_cap = rows;
+    }
+  } catch (const DeviceError &) {
+    (void)hipGetLastError();
+    ix->screen_rows.release();
+    ix->screen_err.release();
+    ix->screen_cap = 0;
+    ix->screen_failed = true;
+    return false;
+  }
+  scratch_acquire(ix, stream);  // after every earlier launch that may still read the buffers
+  hip_check(alaya_amd::launch_screen_rows(ix->base.as<float>(), 0, ix->n, ix->stride, ix->screen_rows.as<uint16_t>(),
+                                          ix->screen_err.as<float>(), stream),
+            "screening copy");
+  ix->screen_ready = true;
+  return true;
+}
+
+// The base is gone or replaced: nothing keeps its screening copy alive.
+void screen_drop(alaya_index *ix) {
+  ix->screen_rows.release();
+  ix->screen_err.release();
+  ix->screen_cap = 0;
+  ix->screen_ready = false;
+  ix->screen_failed = false;
+  ix->screen_stats_slots = 0;
 }
 
 void ensure_norms(alaya_index *ix, hipStream_t stream) {
@@ -976,6 +1051,7 @@ int alaya_index_set_base(alaya_index *ix, const float *rows, uint64_t n, uint32_
       ix->sq_max.release();
     }
     ix->base.release();
+    screen_drop(ix);
     ix->base.reserve(std::max<uint64_t>(n, 1) * stride * 4);
     if (n) {
       hip_check(hipMemset2DAsync(ix->base.ptr, static_cast<size_t>(stride) * 4, 0,
@@ -1114,6 +1190,17 @@ void write_rows_locked(alaya_index *ix, uint64_t first, const float *rows, uint6
   ix->n = std::max(ix->n, first + count);
   ix->norms_ready = false;
   ix->tiles_ready = false;
+  // the screening copy follows the written rows; rows past what it holds mark it for a rebuild
+  if (ix->screen_ready) {
+    if (first + count <= ix->screen_cap) {
+      hip_check(alaya_amd::launch_screen_rows(ix->base.as<float>(), first, count, ix->stride,
+                                              ix->screen_rows.as<uint16_t>(), ix->screen_err.as<float>(), ix->stream),
+                "screening copy");
+      hip_check(hipStreamSynchronize(ix->stream), "sync");
+    } else {
+      ix->screen_ready = false;
+    }
+  }
 }
 
 void write_edges_locked(alaya_index *ix, const uint32_t *ids, const uint32_t *edges, uint64_t count) {
@@ -2036,6 +2123,32 @@ int alaya_index_help_stats(alaya_index *ix, uint64_t *memo_dists, uint64_t *memo
     if (memo_dists) *memo_dists = m;
     if (memo_expansions) *memo_expansions = x;
     if (helper_rows) *helper_rows = r;
+  });
+}
+
+int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t n, uint32_t dim, float *out) {
+  return guarded([&] {
+    if (n && (!d_tilde || !e_row || !out)) throw ArgError("invalid arguments");
+    for (uint64_t i = 0; i < n; ++i) out[i] = alaya_amd::screen_lower_bound(d_tilde[i], e_row[i], dim);
+  });
+}
+
+int alaya_index_screen_stats(alaya_index *ix, uint64_t *screened, uint64_t *screened_out) {
+  return guarded_scratch(ix, [&] {
+    if (!ix) throw ArgError("null index");
+    uint64_t a = 0, b = 0;
+    if (ix->screen_stats_slots) {
+      set_device(ix);
+      scratch_drain(ix);
+      std::vector<uint32_t> h(2 * ix->screen_stats_slots);
+      hip_check(hipMemcpy(h.data(), ix->screen_stats.ptr, h.size() * 4, hipMemcpyDeviceToHost), "D2H");
+      for (uint64_t i = 0; i < ix->screen_stats_slots; ++i) {
+        a += h[2 * i];
+        b += h[2 * i + 1];
+      }
+    }
+    if (screened) *screened = a;
+    if (screened_out) *screened_out = b;
   });
 }
 

@@ -292,6 +292,11 @@ class PyIndexInterface {
     check(alaya_index_help_stats(ix_, &m, &x, &r));
     return py::make_tuple(m, x, r);
   }
+  py::tuple screen_stats() {
+    uint64_t a = 0, b = 0;
+    check(alaya_index_screen_stats(ix_, &a, &b));
+    return py::make_tuple(a, b);
+  }
   // SQ8 batch_search rerank: 1 = the reference's PyIndex::rerank (default), 2 = corrected (whole ef pool)
   void set_rerank_mode(int m) {
     if (m != 1 && m != 2) throw std::invalid_argument("rerank mode must be 1 (reference) or 2 (corrected)");
@@ -875,6 +880,11 @@ class DeviceIndex {
     check(alaya_index_help_stats(ix_, &m, &x, &r));
     return py::make_tuple(m, x, r);
   }
+  py::tuple screen_stats() {
+    uint64_t a = 0, b = 0;
+    check(alaya_index_screen_stats(ix_, &a, &b));
+    return py::make_tuple(a, b);
+  }
   py::tuple profile_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k,
                            uint32_t ef, int space) {
     const uint64_t nq = q.shape(0);
@@ -968,6 +978,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("set_helpers", &PyIndexInterface::set_helpers)
       .def("last_launch", &PyIndexInterface::last_launch)
       .def("help_stats", &PyIndexInterface::help_stats)
+      .def("screen_stats", &PyIndexInterface::screen_stats)
       .def("set_rerank_mode", &PyIndexInterface::set_rerank_mode)
       .def("rerank_mode", &PyIndexInterface::rerank_mode)
       .def("device_distances", &PyIndexInterface::device_distances)
@@ -997,6 +1008,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("set_helpers", &DeviceIndex::set_helpers)
       .def("last_launch", &DeviceIndex::last_launch)
       .def("help_stats", &DeviceIndex::help_stats)
+      .def("screen_stats", &DeviceIndex::screen_stats)
       .def("flat_search", &DeviceIndex::flat_search, py::arg("queries"), py::arg("k"))
       .def("flat_search_device", &DeviceIndex::flat_search_device)
       .def("flat_diag", &DeviceIndex::flat_diag)
@@ -1025,6 +1037,14 @@ PYBIND11_MODULE(_alayalitepy, m) {
   }, py::arg("data"), py::arg("min"), py::arg("max"), py::arg("num_threads") = 1u);
   m.def("host_sq8_order", &host_sq8_order);
   m.def("build_info", [] { return std::string(alaya_build_info()); });
+  m.def("screen_lower_bound", [](py::array_t<float, py::array::c_style | py::array::forcecast> d_tilde,
+                                 py::array_t<float, py::array::c_style | py::array::forcecast> e_row, uint32_t dim) {
+    if (d_tilde.size() != e_row.size()) throw std::invalid_argument("d_tilde and e_row differ in size");
+    py::array_t<float> out(d_tilde.size());
+    check(alaya_screen_lower_bound(d_tilde.data(), e_row.data(), static_cast<uint64_t>(d_tilde.size()), dim,
+                                   out.mutable_data()));
+    return out;
+  });
   m.def("device_count", [] {
     int c = 0;
     check(alaya_device_count(&c));

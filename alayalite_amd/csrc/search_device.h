@@ -321,6 +321,88 @@ __device__ __forceinline__ void row_distances(const SearchParams &p, const float
 }
 
 // --------------------------------------------------------------------------------------------
+// Screen pass (search kernel kMode 16): approximate L2 distances d~ = sum (q_j - y_j)^2 of the query
+// to the f16 copies y of `n` rows (SearchParams::screen_rows) -> out[0..n).  Same shape as the exact
+// pass -- 8 lanes per row, every 128 B chunk of the pass issued before the first FMA -- but a
+// chunk holds 64 elements, so a row is kChunks / 2 loads of 16 B per lane: lane m takes elements
+// 64 t + 8 m .. + 7.  f32 arithmetic on the widened values; the summation order is free (the bound,
+// screen_bound.h, holds for any order): two partial sums per lane, then the 8-lane tree.
+// --------------------------------------------------------------------------------------------
+template <int kChunks, int kRows>
+struct ScreenPass {
+  static_assert(kChunks % 2 == 0, "f16 rows are read in 128 B chunks of 64 elements");
+  static constexpr int kT = kChunks / 2;
+  uint4 y[kRows][kT];
+};
+
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void screen_accumulate(float4 qa, float4 qb, uint4 w, float &a0, float &a1) {
+  const half2_t h0 = __builtin_bit_cast(half2_t, w.x), h1 = __builtin_bit_cast(half2_t, w.y);
+  const half2_t h2 = __builtin_bit_cast(half2_t, w.z), h3 = __builtin_bit_cast(half2_t, w.w);
+  const float d0 = qa.x - static_cast<float>(h0.x), d1 = qa.y - static_cast<float>(h0.y);
+  const float d2 = qa.z - static_cast<float>(h1.x), d3 = qa.w - static_cast<float>(h1.y);
+  const float d4 = qb.x - static_cast<float>(h2.x), d5 = qb.y - static_cast<float>(h2.y);
+  const float d6 = qb.z - static_cast<float>(h3.x), d7 = qb.w - static_cast<float>(h3.y);
+  a0 = fmaf(d0, d0, a0); a1 = fmaf(d1, d1, a1);
+  a0 = fmaf(d2, d2, a0); a1 = fmaf(d3, d3, a1);
+  a0 = fmaf(d4, d4, a0); a1 = fmaf(d5, d5, a1);
+  a0 = fmaf(d6, d6, a0); a1 = fmaf(d7, d7, a1);
+}
+
+// after_issue() runs once, right after the first pass's loads are issued (see sq8_distances)
+template <int kChunks, int kRows, typename Hook>
+__device__ __forceinline__ void screen_distances(const SearchParams &p, const float *q, const uint32_t *ids,
+                                                 int n, float *out, Hook after_issue) {
+  using SP = ScreenPass<kChunks, kRows>;
+  const int lane = lane_id();
+  const int g = lane >> 3, m = lane & 7;
+  for (int base = 0; base < n; base += 8 * kRows) {
+    SP P;
+    const uint32_t id0 = ids[base];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      const int idx = base + g + 8 * r;
+      const uint32_t id = idx < n ? ids[idx] : id0;  // a group past n reloads the pass's first row
+      const uint4 *rp = reinterpret_cast<const uint4 *>(p.screen_rows + static_cast<uint64_t>(id) * p.stride) + m;
+      if (base + 8 * r < n) {  // wave-uniform
+#pragma unroll
+        for (int t = 0; t < SP::kT; ++t) P.y[r][t] = rp[8 * t];
+      }
+    }
+    if (base == 0) after_issue();
+    int live = 0;  // wave-uniform number of row slots in use
+    float a[kRows][2];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      a[r][0] = a[r][1] = 0.f;
+      live += base + 8 * r < n ? 1 : 0;
+    }
+    const float4 *qp = reinterpret_cast<const float4 *>(q) + 2 * m;
+#pragma unroll
+    for (int t = 0; t < SP::kT; ++t) {
+      const float4 qa = qp[16 * t], qb = qp[16 * t + 1];
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) {
+        if (r >= live) break;
+        screen_accumulate(qa, qb, P.y[r][t], a[r][0], a[r][1]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      if (r >= live) break;
+      float s = a[r][0] + a[r][1];
+      s += lane_xor<1>(s);
+      s += lane_xor<2>(s);
+      s += lane_xor<4>(s);
+      const int idx = base + g + 8 * r;
+      if (idx < n && m == 0) out[idx] = s;
+    }
+  }
+  wave_sync();
+}
+
+// --------------------------------------------------------------------------------------------
 // SQ8 distances (SQ8Space::QueryComputer over l2_sqr_sq8 / ip_sqr_sq8).  The reference picks the
 // AVX-512 kernel when the host has AVX-512F, else AVX2 (distance_l2.ipp:694-708,
 // distance_ip.ipp:703-716).  Both are "P partial sums, element P*t+j -> acc[j]":

@@ -82,6 +82,13 @@ struct SearchParams {
                           // twice the resident searchers, each with half the rows in flight
   uint32_t *help_stats;   // nullable: per searcher, (fresh distances it took from a memo, expansions
                           // with every fresh distance from the memo, rows it computed as a helper)
+  // Candidate screen (search_has_screen; kMode 16): once the pool is full, an expansion's fresh
+  // candidates are first measured on an f16 copy of their rows, and only those whose proven lower
+  // bound (screen_bound.h) is below the pool's worst distance read their f32 row.
+  uint32_t screen;             // 1 = the screening kernel
+  const uint16_t *screen_rows; // n rows of `stride` f16 values (stride * 2 bytes, a multiple of 64)
+  const float *screen_err;     // per row, >= ||x - f16(x)||_2; +inf = never screened out
+  uint32_t *screen_stats;      // per searcher: (candidates screened, candidates screened out)
 };
 
 // PyIndex::rerank inputs (python/include/index.hpp:450-488).  Per query the kernel rescores
@@ -131,6 +138,13 @@ hipError_t search_occupancy(const SearchParams &p, int waves, size_t lds, int *b
 bool search_has_helpers(uint32_t dim, int sq8_order, bool generic);
 // whether a search of this shape has a two-waves-per-SIMD kernel (SearchParams::two_waves)
 bool search_has_two_waves(uint32_t dim, int sq8_order, bool generic);
+// whether a search of this shape has a screening kernel (SearchParams::screen): L2 on wide f32 rows
+bool search_has_screen(uint32_t dim, int sq8_order, bool generic, bool ip);
+// The screening copy of rows [first, first + count): out_rows[r] = f16(base[r]) (stride halfs per
+// row) and out_err[r] >= ||base[r] - f16(base[r])||_2, +inf for a row with an element that is not
+// finite in f16.
+hipError_t launch_screen_rows(const float *base, uint64_t first, uint64_t count, uint32_t stride,
+                              uint16_t *out_rows, float *out_err, hipStream_t stream);
 hipError_t launch_search(const SearchParams &p, int grid, int waves, size_t lds, hipStream_t stream);
 // out[q * n + i] = dist(queries[q], base[ids[i]]) for q < nq (bit-exact device distance)
 hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint32_t n,

@@ -19,6 +19,7 @@
 #include <cfloat>
 #include <cstdint>
 
+#include "screen_bound.h"
 #include "search_kernels.h"
 #include "search_device.h"
 
@@ -597,6 +598,13 @@ __global__ void __launch_bounds__(256)
   constexpr bool kCheck = (kMode & 2) != 0;
   constexpr bool kHelp = (kMode & 4) != 0;
   constexpr int kRows = (kMode & 8) != 0 ? 1 : 0;
+  // Candidate screen (f32 L2 rows of d >= 512, no helpers): rows per lane group of the f16 pass --
+  // 4 (32 candidates, a whole expansion of an R = 32 graph, in 2 kChunks float4 of registers), or 2
+  // in the two-waves-per-SIMD kernels' half register budget.
+  constexpr bool kScreen = (kMode & 16) != 0;
+  static_assert(!kScreen || (kSpace == 0 && !kIP && !kHelp && kChunks >= 16 && kChunks % 2 == 0), "screen: wide f32 L2 rows");
+  constexpr int kScreenRows = (kMode & 8) != 0 ? 2 : 4;
+  uint32_t n_screened = 0, n_screened_out = 0;  // wave-uniform, over the searcher's queries
   const int lane = lane_id();
   const int wave = static_cast<int>(threadIdx.x >> 6);
   const int W = static_cast<int>(blockDim.x >> 6);
@@ -801,14 +809,60 @@ __global__ void __launch_bounds__(256)
           }
         }
       };
-      if (!kHelp || compute) {
+      // Screen (kMode 16).  With the pool full, tau = its worst distance now is >= its worst distance
+      // at every later point of the sequential LinearPool::insert order, so a candidate whose exact
+      // distance is >= tau is rejected by the reference ("full and d >= last") and changes nothing:
+      // not the pool, not cur, not on_next.  One pass over the f16 copies of all nf rows gives d~;
+      // a candidate whose proven lower bound on the exact f32 distance (screen_bound.h) reaches tau
+      // is dropped from the list here -- it stays visited and stays counted in n_dist, as in the
+      // reference -- and only the others, still in adjacency order, read their f32 rows below, so
+      // every distance that can enter the pool has the bits it always had.
+      int nd = nf;  // candidates whose f32 row is read
+      if constexpr (kScreen) {
+        if (ps.size == ps.ef) {
+          const float tau = L.pd[ps.size - 1];
+          const bool in = lane < nf;
+          const uint32_t c = in ? L.cid[lane] : 0u;
+          float e_row = 0.f;
+          if (in) e_row = p.screen_err[c];
+          screen_distances<kChunks, kScreenRows>(p, L.q, L.cid, nf, L.cd, second_level_prefetch);
+          bool keep = false;
+          if (in) {
+            const float lb = screen_lower_bound(L.cd[lane], e_row, p.dim);
+            keep = !(lb > 0.f && lb >= tau);  // lb == 0: no bound (never screened out)
+          }
+          const uint64_t km = ballot(keep);
+          nd = __popcll(km);
+          n_screened += static_cast<uint32_t>(nf);
+          n_screened_out += static_cast<uint32_t>(nf - nd);
+          // (every lane read its id before screen_distances' closing wave_sync)
+          if (keep) L.cid[__popcll(km & ((1ull << lane) - 1ull))] = c;
+          wave_sync();
+          if (nd == 0) {
+            stamp(3);
+            n_dist += nf;
+            continue;
+          }
+        }
+      }
+      if constexpr (kScreen) {
+        // few survivors: a pass of one or two rows per lane group issues no more chunks than it needs
+        constexpr int kFull = RowPass<kChunks, kRows>::kR;
+        if (nd <= 8) {
+          space_distances<kIP, kChunks, kSpace, false, 1>(p, L, L.cid, nd, L.cd);
+        } else if (kFull > 2 && nd <= 16) {
+          space_distances<kIP, kChunks, kSpace, false, 2>(p, L, L.cid, nd, L.cd);
+        } else {  // (the second-level prefetch hook is empty for f32 rows)
+          space_distances<kIP, kChunks, kSpace, false, kRows>(p, L, L.cid, nd, L.cd);
+        }
+      } else if (!kHelp || compute) {
         space_distances<kIP, kChunks, kSpace, kHelp, kRows>(p, L, dist_ids, nf, L.cd, second_level_prefetch);
       } else {
         second_level_prefetch();
       }
       stamp(3);
       n_dist += nf;
-      const bool has = lane < nf;
+      const bool has = lane < nd;
       const uint32_t cid = has ? L.cid[lane] : 0u;
       const float cd = has ? L.cd[lane] : 0.f;
       wave_sync();
@@ -846,6 +900,54 @@ __global__ void __launch_bounds__(256)
       p.help_stats[3 * slot] = board->own[wave].hits;
       p.help_stats[3 * slot + 1] = board->own[wave].skips;
       p.help_stats[3 * slot + 2] = board->own[wave].rows;
+    }
+  }
+  if constexpr (kScreen) {  // every searcher of the launch writes its slot
+    if (p.screen_stats != nullptr && lane == 0) {
+      p.screen_stats[2 * slot] = n_screened;
+      p.screen_stats[2 * slot + 1] = n_screened_out;
+    }
+  }
+}
+
+// The screening copy of the base (launch_screen_rows): one wave per row.  err = an over-estimate of
+// ||x - f16(x)||_2: the f32 sum of squared differences is at least (1 - (stride + 2) u) of the exact
+// one minus the underflow of tiny squares (<= 2 stride 2^-126), so it is scaled up by the bound's
+// slack (screen_gamma), its root by 1 + 2^-19 (the sqrt's and the products' roundings), and 2^-50
+// covers the root of the underflow.  A row with an element that f16 cannot hold as a finite value
+// gets +inf and is never screened out.
+__global__ void __launch_bounds__(256) screen_rows_kernel(const float *base, uint64_t first, uint64_t count,
+                                                          uint32_t stride, uint16_t *out_rows, float *out_err) {
+  const int lane = lane_id();
+  const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (blockDim.x >> 6);
+  for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6); r < count; r += waves) {
+    const float *row = base + (first + r) * stride;
+    uint16_t *dst = out_rows + (first + r) * stride;
+    float sum = 0.f;
+    bool bad = false;
+    for (uint32_t e = 2 * lane; e < stride; e += 128) {  // stride is a multiple of 32
+      const float2 x = *reinterpret_cast<const float2 *>(row + e);
+      const _Float16 h0 = static_cast<_Float16>(x.x), h1 = static_cast<_Float16>(x.y);  // round to nearest even
+      const float y0 = static_cast<float>(h0), y1 = static_cast<float>(h1);
+      bad = bad || !(fabsf(y0) <= 65504.f) || !(fabsf(y1) <= 65504.f) || !(fabsf(x.x) <= FLT_MAX) ||
+            !(fabsf(x.y) <= FLT_MAX);
+      const float d0 = x.x - y0, d1 = x.y - y1;
+      sum = fmaf(d0, d0, sum);
+      sum = fmaf(d1, d1, sum);
+      const half2_t h = {h0, h1};
+      *reinterpret_cast<uint32_t *>(dst + e) = __builtin_bit_cast(uint32_t, h);
+    }
+    sum += lane_xor<1>(sum);
+    sum += lane_xor<2>(sum);
+    sum += lane_xor<4>(sum);
+    sum += lane_xor<8>(sum);
+    sum += lane_xor<16>(sum);
+    sum = read_lane(sum, 0) + read_lane(sum, 32);
+    const bool any_bad = ballot(bad) != 0ull;
+    if (lane == 0) {
+      float err = sqrtf(sum * (1.0f + screen_gamma(stride))) * (1.0f + 1.9073486328125e-6f) + 8.8817841970012523e-16f;
+      if (any_bad || !(err <= kScreenHuge)) err = __builtin_inff();
+      out_err[first + r] = err;
     }
   }
 }
@@ -1048,11 +1150,35 @@ bool search_has_helpers(uint32_t dim, int sq8_order, bool generic) {
   return chunks == 4 || chunks == 8;
 }
 
+// Whether a search has a screening kernel (kMode 16): L2 on the wide f32 rows, d = 512 / 768 / 960 /
+// 1024 -- the bandwidth-bound shapes.  The small-row kernels are latency-bound (a dependent second
+// pass would only add to the chain); IP and COS have no proven bound here.
+bool search_has_screen(uint32_t dim, int sq8_order, bool generic, bool ip) {
+  return sq8_order == 0 && !generic && !ip && (dim == 16 * 32 || dim == 24 * 32 || dim == 30 * 32 || dim == 32 * 32);
+}
+
+hipError_t launch_screen_rows(const float *base, uint64_t first, uint64_t count, uint32_t stride,
+                              uint16_t *out_rows, float *out_err, hipStream_t stream) {
+  if (count == 0) return hipSuccess;
+  const int grid = static_cast<int>(std::min<uint64_t>((count + 3) / 4, 16384));
+  hipLaunchKernelGGL(screen_rows_kernel, dim3(grid), dim3(256), 0, stream, base, first, count, stride, out_rows,
+                     out_err);
+  return hipGetLastError();
+}
+
 const void *search_kernel_symbol(bool ip, uint32_t dim, bool stamped, int sq8_order, bool generic, bool check,
-                                 bool help, bool two_waves) {
+                                 bool help, bool two_waves, bool screen) {
   if (sq8_order == 2) return sq8_symbol<2>(ip, dim, stamped, check, help);
   if (sq8_order == 1) return sq8_symbol<1>(ip, dim, stamped, false, false);
   const uint32_t chunks = (!generic && dim % 32 == 0) ? dim / 32 : 0;  // generic order: the runtime-d kernel
+  if (screen && !stamped && !help && !ip) {
+    if (two_waves && chunks == 24) return kernel_ptr<false, 24, 24>();
+    if (two_waves && chunks == 30) return kernel_ptr<false, 30, 24>();
+    if (chunks == 16) return kernel_ptr<false, 16, 16>();
+    if (chunks == 24) return kernel_ptr<false, 24, 16>();
+    if (chunks == 30) return kernel_ptr<false, 30, 16>();
+    if (chunks == 32) return kernel_ptr<false, 32, 16>();
+  }
   if (stamped) {
     if (help && chunks == 4) return ip ? kernel_ptr<true, 4, 5>() : kernel_ptr<false, 4, 5>();
     if (chunks == 30) return ip ? kernel_ptr<true, 30, 1>() : kernel_ptr<false, 30, 1>();
@@ -1077,7 +1203,7 @@ const void *search_kernel_symbol(bool ip, uint32_t dim, bool stamped, int sq8_or
 
 hipError_t launch_search(const SearchParams &p, int grid, int waves, size_t lds, hipStream_t stream) {
   const void *fn = search_kernel_symbol(p.ip, p.dim, p.stamps != nullptr, p.sq8_order, p.generic,
-                                        (p.spill_flags & 256u) != 0, p.help != 0, p.two_waves != 0);
+                                        (p.spill_flags & 256u) != 0, p.help != 0, p.two_waves != 0, p.screen != 0);
   SearchParams arg = p;
   void *args[] = {&arg};
   return hipLaunchKernel(fn, dim3(grid), dim3(64 * waves), args, lds, stream);
@@ -1097,7 +1223,7 @@ hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint
 
 hipError_t search_occupancy(const SearchParams &p, int waves, size_t lds, int *blocks_per_cu) {
   const void *fn = search_kernel_symbol(p.ip, p.dim, p.stamps != nullptr, p.sq8_order, p.generic,
-                                        (p.spill_flags & 256u) != 0, p.help != 0, p.two_waves != 0);
+                                        (p.spill_flags & 256u) != 0, p.help != 0, p.two_waves != 0, p.screen != 0);
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, 64 * waves, lds);
 }
 

@@ -255,6 +255,19 @@ int alaya_index_set_visited_mode(alaya_index *ix, int mode);
 int alaya_index_set_helpers(alaya_index *ix, int mode);
 int alaya_index_help_stats(alaya_index *ix, uint64_t *memo_dists, uint64_t *memo_expansions,
                            uint64_t *helper_rows);
+/* Candidate screen of the wide-row f32 L2 graph search (d = 512 / 768 / 960 / 1024; environment
+ * ALAYA_SEARCH_SCREEN = 0 / 1 forces it off / on per launch): once a query's pool is full, the fresh
+ * candidates of an expansion are first measured on an f16 copy of their rows (built at the first
+ * search that uses it: n x stride x 2 bytes + 4 bytes per row, freed with the base), and only those
+ * whose proven lower bound on the exact distance is below the pool's worst distance read their f32
+ * row.  Results and counters never depend on it.  alaya_index_screen_stats: of the last graph search,
+ * how many candidates were screened and how many of those were screened out (waits for that search;
+ * 0, 0 when it did not screen). */
+int alaya_index_screen_stats(alaya_index *ix, uint64_t *screened, uint64_t *screened_out);
+/* The screen's bound, evaluated on the host by the function the kernel calls (screen_bound.h):
+ * out[i] <= the reference's f32 L2 distance of any q, x of `dim` elements for which d_tilde[i] is an
+ * f32 sum in any order of (q_j - y_j)^2 over a copy y of x, and e_row[i] >= ||x - y||_2. */
+int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t n, uint32_t dim, float *out);
 /* The last graph search's launch shape: persistent workgroups and searchers (waves) per workgroup --
  * workgroups x waves is the number of queries the launch runs at once (introspection). */
 int alaya_index_last_launch(const alaya_index *ix, uint32_t *workgroups, uint32_t *waves_per_group);
