@@ -324,7 +324,7 @@ uint64_t max_search_waves_per_cu() {
   return kMaxSearchWavesPerCu;
 }
 
-// Distance helpers (search kernel kMode 4, search_has_helpers): with helpers every search runs 4-wave
+// Distance helpers (search kernel kModeHelp, search_has_helpers): with helpers every search runs 4-wave
 // workgroups, and a batch smaller than the resident searchers still fills the CUs, so each workgroup
 // has idle waves to help from the start.  Automatic policy, from the measurements in DESIGN.md
 // (round 5, "distance helpers"): on for the SQ8 kernels (config 5: 1k queries 3.75 -> 3.54 ms, 10k
@@ -339,7 +339,8 @@ bool helpers_requested(const alaya_index *ix, const SearchParams &p, uint64_t nq
   return nq > max_search_waves_per_cu() * cus;
 }
 
-uint32_t size_visited(alaya_index *ix, SearchParams &p, uint64_t nq, uint32_t ef, int W = 1) {
+uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchVariant &v, uint64_t nq, uint32_t ef,
+                      int W = 1) {
   const uint32_t lbits = std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2)));
   const int mode = ix->visited_mode_override;  // 0 auto, 1 compact, 2 wide, 3 compact + short probes
   auto set_mode = [&](uint32_t l, bool compact) {
@@ -383,7 +384,7 @@ uint32_t size_visited(alaya_index *ix, SearchParams &p, uint64_t nq, uint32_t ef
   // set_mode(7) above.
   const bool stab = p.stab_log2 != 0;  // set by do_search (spill_table_log2)
   int vgpr_blocks = 0;
-  hip_check(alaya_amd::search_occupancy(p, W, shared + W * (wave_fixed + (stab ? 1024 : 4096)), &vgpr_blocks),
+  hip_check(alaya_amd::search_occupancy(v, p.ip, W, shared + W * (wave_fixed + (stab ? 1024 : 4096)), &vgpr_blocks),
             "occupancy");
   const uint64_t vgpr_waves = static_cast<uint64_t>(std::max(1, vgpr_blocks)) * W;
   const uint64_t max_waves = std::max<uint64_t>(W, max_search_waves_per_cu());
@@ -440,6 +441,110 @@ int stream_cus(const alaya_index *ix, hipStream_t s) {
 
 bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStream_t stream);
 
+// What policy wants of a search's kernel: the features (kMode bits, search_variants.h) of one launch,
+// decided in the order they depend on each other -- stamps and the prefetch check come with the
+// call, helpers rule out two waves, and any of those but the check rules out the screen.
+alaya_amd::SearchRequest search_request(alaya_index *ix, const SearchParams &p, uint64_t nq, uint32_t ef,
+                                        hipStream_t stream) {
+  using namespace alaya_amd;
+  SearchRequest r{ix->dim, p.ip, p.sq8_order, ix->generic, p.stamps != nullptr ? kModeStamp : 0};
+  // diagnostics flags (prepare_spill hands them to the kernel); bit 8 asks for the prefetch-check kernel
+  if (const char *e = std::getenv("ALAYA_SPILL_FLAGS"))
+    if ((std::strtoul(e, nullptr, 10) & 256u) != 0) r.want |= kModeCheck;
+  // distance helpers (4-wave workgroups; a helper's memo of 4 x R entries lives in its pool and
+  // visited table, checked by plan_search)
+  if (helpers_requested(ix, p, nq, static_cast<uint64_t>(stream_cus(ix, stream))) && ix->R <= 64 &&
+      search_has_helpers(ix->dim, p.sq8_order, ix->generic))
+    r.want |= kModeHelp;
+  // Wide f32 rows (d = 768 / 960) run one searcher per SIMD; a batch a little larger than that
+  // (config 4's S = 1 layout: 1,250 queries per rank on 1,024 searchers) would leave most of a
+  // second round idle, so it runs the two-waves-per-SIMD kernel instead (one row per lane group):
+  // GIST-shaped 1M, ef 373, 1,250 queries 8.92 -> 7.44 ms, <= 1,024 queries equal, 2,048 and more
+  // slower (profiles/r05/gist_rounds/).  ALAYA_TWO_WAVES = 0 / 1 forces it off / on.
+  const bool plain = (r.want & (kModeHelp | kModeStamp)) == 0;
+  if (plain && search_has_two_waves(ix->dim, p.sq8_order, ix->generic)) {
+    const char *e = std::getenv("ALAYA_TWO_WAVES");
+    const int force = e ? std::atoi(e) : -1;
+    if (force == 1) {
+      r.want |= kModeTwoWaves;
+    } else if (force != 0) {
+      int b1 = 0;  // resident searchers of the one-wave kernel: the request as it stands
+      const size_t probe = search_wave_lds_bytes(ix->stride, ef, 12, true);
+      hip_check(search_occupancy(resolve_search_variant(r), p.ip, 1, probe, &b1), "occupancy");
+      const uint64_t resident1 = static_cast<uint64_t>(std::max(1, b1)) * static_cast<uint64_t>(stream_cus(ix, stream));
+      if (nq > resident1 && 2 * nq <= 3 * resident1) r.want |= kModeTwoWaves;
+    }
+  }
+  // candidate screen on an f16 row copy (wide f32 L2 rows), built here at the first launch that screens
+  if (ensure_screen(ix, p, p.sq8_order == 0 && plain, stream)) r.want |= kModeScreen;
+  return r;
+}
+
+// One search launch: the kernel variant its request resolved to and the shape sized for that kernel.
+struct SearchPlan {
+  const alaya_amd::SearchVariant *variant;
+  int W;       // waves (searchers) per workgroup
+  size_t lds;  // bytes per workgroup
+  int grid;    // persistent workgroups
+};
+
+// Resolves the request and sizes the launch for the kernel it got, so a feature that has no kernel
+// for this shape is planned as absent: sets p.help / p.two_waves / p.screen, the visited table
+// (p.hash_log2, p.vis_*), p.wave_lds and p.memo_off.  A stamped call whose shape has no stamped
+// kernel is an error (its stamps would all be zero).
+SearchPlan plan_search(alaya_index *ix, SearchParams &p, alaya_amd::SearchRequest r, uint64_t nq, uint32_t ef,
+                       hipStream_t stream) {
+  using namespace alaya_amd;
+  SearchPlan plan{};
+  // waves per workgroup: never more than the batch needs (helpers: always 4).  A plan with helpers
+  // that does not fit (the memo, or four waves' LDS with a forced large visited table) falls back
+  // to the search without them.
+  for (;;) {
+    plan.variant = &resolve_search_variant(r);
+    const int mode = plan.variant->mode;
+    if ((r.want & kModeStamp) != 0 && (mode & kModeStamp) == 0)
+      throw ArgError("no stamped search kernel for dim " + std::to_string(ix->dim) +
+                     (p.sq8_order ? " SQ8 (order " + std::to_string(p.sq8_order) + ")" : std::string(" f32")) +
+                     ": see the variant list in search_variants.h");
+    p.help = (mode & kModeHelp) != 0;
+    p.two_waves = (mode & kModeTwoWaves) != 0;
+    p.screen = (mode & kModeScreen) != 0;
+    plan.W = p.help ? 4 : search_waves(p);
+    while (!p.help && plan.W > 1 && static_cast<uint64_t>(plan.W) > nq) plan.W /= 2;
+    p.hash_log2 = size_visited(ix, p, *plan.variant, nq, ef, plan.W);
+    const bool compact = p.vis_rbits != kVisWide;
+    p.wave_lds = static_cast<uint32_t>(search_wave_lds_bytes(ix->stride, ef, p.hash_log2, compact, p.sq8_order));
+    bool fits = true;
+    if (p.help) {
+      // the memo (W searchers x kHelpMemoSlots requests x R entries of 8 bytes) overlays the memo
+      // wave's query vector, or else its pool and visited table (past the query and the three
+      // 64-entry lists the helper still uses)
+      const size_t need = static_cast<size_t>(plan.W) * kHelpMemoSlots * ix->R * 8;
+      const size_t q_bytes = search_query_lds_bytes(ix->stride, p.sq8_order);
+      if (q_bytes >= need) {
+        p.memo_off = 0;
+      } else if (p.wave_lds >= q_bytes + 3 * 64 * 4 + need) {
+        p.memo_off = static_cast<uint32_t>(q_bytes + 3 * 64 * 4);
+      } else {
+        fits = false;
+      }
+    }
+    plan.lds = search_shared_lds_bytes(ix->stride, p.sq8_order != 0) + static_cast<size_t>(plan.W) * p.wave_lds +
+               (p.help ? kHelpBoardBytes : 0);
+    if (!p.help || (fits && plan.lds <= kLdsPerCu)) break;
+    r.want &= ~kModeHelp;
+  }
+  if (plan.lds > kLdsPerCu) throw ArgError("ef / dim too large for the LDS budget");
+  int per_cu = 0;
+  hip_check(search_occupancy(*plan.variant, p.ip, plan.W, plan.lds, &per_cu), "occupancy");
+  per_cu = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(per_cu, max_search_waves_per_cu() / plan.W)));
+  // with helpers the grid fills the CUs whatever the batch (idle waves help from the start)
+  const uint64_t cus = static_cast<uint64_t>(stream_cus(ix, stream));
+  const uint64_t blocks_needed = p.help ? static_cast<uint64_t>(per_cu) * cus : (nq + plan.W - 1) / plan.W;
+  plan.grid = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(blocks_needed, static_cast<uint64_t>(per_cu) * cus)));
+  return plan;
+}
+
 void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef,
                uint32_t *d_ids, float *d_dists, uint32_t *d_cnt, hipStream_t stream,
                uint64_t *d_stamps = nullptr, bool sq8 = false, uint32_t fill_id = 0) {
@@ -477,106 +582,33 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
     p.sq_min = ix->sq_min.as<float>();
     p.sq_max = ix->sq_max.as<float>();
   }
-  // diagnostics flags (read again by prepare_spill); bit 8 selects the prefetch-check kernel, so it
-  // must be known before the occupancy probes
-  if (const char *e = std::getenv("ALAYA_SPILL_FLAGS")) p.spill_flags = static_cast<uint32_t>(std::strtoul(e, nullptr, 10));
   // the visited second level: spill table or bitset
   p.stab_log2 = spill_table_log2(p.sq8_order, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2))), ef);
-  // distance helpers (4-wave workgroups; a helper's memo of 4 x R entries lives in its pool and
-  // visited table, checked below)
-  p.help = (helpers_requested(ix, p, nq, static_cast<uint64_t>(stream_cus(ix, stream))) && ix->R <= 64 &&
-            alaya_amd::search_has_helpers(ix->dim, p.sq8_order, ix->generic)) ? 1u : 0u;
   if (const char *e = std::getenv("ALAYA_HELP_FLAGS")) p.help_flags = static_cast<uint32_t>(std::strtoul(e, nullptr, 10));
-  // Wide f32 rows (d = 768 / 960) run one searcher per SIMD; a batch a little larger than that
-  // (config 4's S = 1 layout: 1,250 queries per rank on 1,024 searchers) would leave most of a
-  // second round idle, so it runs the two-waves-per-SIMD kernel instead (one row per lane group):
-  // GIST-shaped 1M, ef 373, 1,250 queries 8.92 -> 7.44 ms, <= 1,024 queries equal, 2,048 and more
-  // slower (profiles/r05/gist_rounds/).  ALAYA_TWO_WAVES = 0 / 1 forces it off / on.
-  p.two_waves = 0;
-  if (!p.help && d_stamps == nullptr && alaya_amd::search_has_two_waves(ix->dim, p.sq8_order, ix->generic)) {
-    const char *e = std::getenv("ALAYA_TWO_WAVES");
-    const int force = e ? std::atoi(e) : -1;
-    if (force == 1) {
-      p.two_waves = 1;
-    } else if (force != 0) {
-      int b1 = 0;
-      const size_t probe = alaya_amd::search_wave_lds_bytes(ix->stride, ef, 12, true);
-      hip_check(alaya_amd::search_occupancy(p, 1, probe, &b1), "occupancy");
-      const uint64_t resident1 = static_cast<uint64_t>(std::max(1, b1)) * static_cast<uint64_t>(stream_cus(ix, stream));
-      p.two_waves = (nq > resident1 && 2 * nq <= 3 * resident1) ? 1u : 0u;
-    }
-  }
-  // candidate screen on an f16 row copy (wide f32 L2 rows); it selects the kernel, so it is decided
-  // before the launch shape
-  p.screen = ensure_screen(ix, p, !sq8 && !p.help && d_stamps == nullptr, stream) ? 1u : 0u;
+  const SearchPlan plan = plan_search(ix, p, search_request(ix, p, nq, ef, stream), nq, ef, stream);
   if (p.screen) {
     p.screen_rows = ix->screen_rows.as<uint16_t>();
     p.screen_err = ix->screen_err.as<float>();
   }
-  // waves per workgroup: never more than the batch needs (helpers: always 4).  A plan with helpers
-  // that does not fit (the memo, or four waves' LDS with a forced large visited table) falls back
-  // to the search without them.
-  int W = 1;
-  size_t lds = 0;
-  for (;;) {
-    W = p.help ? 4 : search_waves(p);
-    while (!p.help && W > 1 && static_cast<uint64_t>(W) > nq) W /= 2;
-    p.hash_log2 = size_visited(ix, p, nq, ef, W);
-    const bool compact = p.vis_rbits != alaya_amd::kVisWide;
-    p.wave_lds = static_cast<uint32_t>(alaya_amd::search_wave_lds_bytes(ix->stride, ef, p.hash_log2, compact,
-                                                                        p.sq8_order));
-    bool fits = true;
-    if (p.help) {
-      // the memo (W searchers x kHelpMemoSlots requests x R entries of 8 bytes) overlays the memo
-      // wave's query vector, or else its pool and visited table (past the query and the three
-      // 64-entry lists the helper still uses)
-      const size_t need = static_cast<size_t>(W) * alaya_amd::kHelpMemoSlots * ix->R * 8;
-      const size_t q_bytes = alaya_amd::search_query_lds_bytes(ix->stride, p.sq8_order);
-      if (q_bytes >= need) {
-        p.memo_off = 0;
-      } else if (p.wave_lds >= q_bytes + 3 * 64 * 4 + need) {
-        p.memo_off = static_cast<uint32_t>(q_bytes + 3 * 64 * 4);
-      } else {
-        fits = false;
-      }
-    }
-    lds = alaya_amd::search_shared_lds_bytes(ix->stride, sq8) + static_cast<size_t>(W) * p.wave_lds +
-          (p.help ? alaya_amd::kHelpBoardBytes : 0);
-    if (p.help && (!fits || lds > kLdsPerCu)) {
-      p.help = 0;
-      continue;
-    }
-    break;
-  }
-  if (lds > kLdsPerCu) throw ArgError("ef / dim too large for the LDS budget");
-  int per_cu = 0;
-  hip_check(alaya_amd::search_occupancy(p, W, lds, &per_cu), "occupancy");
-  per_cu = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(per_cu, max_search_waves_per_cu() / W)));
-  // with helpers the grid fills the CUs whatever the batch (idle waves help from the start)
-  const uint64_t cus = static_cast<uint64_t>(stream_cus(ix, stream));
-  const uint64_t blocks_needed = p.help ? static_cast<uint64_t>(per_cu) * cus : (nq + W - 1) / W;
-  const uint64_t grid64 = std::min<uint64_t>(blocks_needed, static_cast<uint64_t>(per_cu) * cus);
-  const int grid = static_cast<int>(std::max<uint64_t>(1, grid64));
   scratch_acquire(ix, stream);
-  prepare_spill(ix, p, static_cast<uint64_t>(grid) * W, stream);
-  ix->last_grid = static_cast<uint32_t>(grid);
-  ix->last_waves = static_cast<uint32_t>(W);
-  ix->help_stats_slots = 0;
+  const uint64_t searchers = static_cast<uint64_t>(plan.grid) * plan.W;
+  prepare_spill(ix, p, searchers, stream);
+  ix->last_grid = static_cast<uint32_t>(plan.grid);
+  ix->last_waves = static_cast<uint32_t>(plan.W);
+  ix->help_stats_slots = p.help ? searchers : 0;
   if (p.help) {
-    ix->help_stats_slots = static_cast<uint64_t>(grid) * W;
-    ix->help_stats.reserve(ix->help_stats_slots * 12);
+    ix->help_stats.reserve(searchers * 12);
     p.help_stats = ix->help_stats.as<uint32_t>();
   }
-  ix->screen_stats_slots = 0;
+  ix->screen_stats_slots = p.screen ? searchers : 0;
   if (p.screen) {
-    ix->screen_stats_slots = static_cast<uint64_t>(grid) * W;
-    ix->screen_stats.reserve(ix->screen_stats_slots * 8);
+    ix->screen_stats.reserve(searchers * 8);
     p.screen_stats = ix->screen_stats.as<uint32_t>();
   }
   ix->work.reserve(4);
   p.work_counter = ix->work.as<uint32_t>();
   hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
-  hip_check(alaya_amd::launch_search(p, grid, W, lds, stream), "search launch");
+  hip_check(alaya_amd::launch_search(*plan.variant, p, plan.grid, plan.W, plan.lds, stream), "search launch");
   scratch_release(ix, stream);
 }
 
@@ -1548,7 +1580,8 @@ int alaya_index_build_graph(alaya_index *ix, uint32_t R, uint32_t ef_constructio
     // visited-set sizing and the spill area for the largest batch (sized once: kernels in flight)
     {
       SearchParams probe = bp.s;
-      const uint32_t hl = size_visited(ix, probe, bmax, ef);
+      const uint32_t hl = size_visited(ix, probe, alaya_amd::resolve_search_variant({ix->dim, probe.ip, 0, ix->generic, 0}),
+                                       bmax, ef);
       const size_t lds = alaya_amd::build_lds_bytes(ix->stride, ef, hl, probe.vis_rbits != alaya_amd::kVisWide);
       bp.s.hash_log2 = hl;
       bp.s.vis_rbits = probe.vis_rbits;
@@ -2130,6 +2163,35 @@ int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t 
   return guarded([&] {
     if (n && (!d_tilde || !e_row || !out)) throw ArgError("invalid arguments");
     for (uint64_t i = 0; i < n; ++i) out[i] = alaya_amd::screen_lower_bound(d_tilde[i], e_row[i], dim);
+  });
+}
+
+int alaya_search_variant(uint32_t dim, int ip, int sq8_order, int generic, uint32_t wanted_mode, int *space,
+                         uint32_t *chunks, uint32_t *mode, uint32_t *has_mode) {
+  return guarded([&] {
+    using namespace alaya_amd;
+    if (sq8_order < 0 || sq8_order > 2 || wanted_mode >= 32u) throw ArgError("invalid arguments");
+    const SearchVariant &v = resolve_search_variant({dim, ip != 0, sq8_order, generic != 0, static_cast<int>(wanted_mode)});
+    if (space) *space = v.space;
+    if (chunks) *chunks = static_cast<uint32_t>(v.chunks);
+    if (mode) *mode = static_cast<uint32_t>(v.mode);
+    if (has_mode)
+      *has_mode = (search_has_helpers(dim, sq8_order, generic != 0) ? kModeHelp : 0) |
+                  (search_has_two_waves(dim, sq8_order, generic != 0) ? kModeTwoWaves : 0) |
+                  (search_has_screen(dim, sq8_order, generic != 0, ip != 0) ? kModeScreen : 0);
+  });
+}
+
+int alaya_search_variant_at(uint32_t index, int *space, uint32_t *chunks, uint32_t *mode, int *l2_only,
+                            uint32_t *count) {
+  return guarded([&] {
+    if (count) *count = static_cast<uint32_t>(alaya_amd::kNumSearchVariants);
+    if (index >= alaya_amd::kNumSearchVariants) throw ArgError("variant index out of range");
+    const alaya_amd::SearchVariant &v = alaya_amd::kSearchVariants[index];
+    if (space) *space = v.space;
+    if (chunks) *chunks = static_cast<uint32_t>(v.chunks);
+    if (mode) *mode = static_cast<uint32_t>(v.mode);
+    if (l2_only) *l2_only = v.l2_only ? 1 : 0;
   });
 }
 

@@ -1045,6 +1045,25 @@ PYBIND11_MODULE(_alayalitepy, m) {
                                    out.mutable_data()));
     return out;
   });
+  // the search kernel chosen for a request: ((space, chunks, mode), features this shape has kernels for)
+  m.def("search_variant", [](uint32_t dim, bool ip, int sq8_order, bool generic, uint32_t wanted_mode) {
+    int space = 0;
+    uint32_t chunks = 0, mode = 0, has = 0;
+    check(alaya_search_variant(dim, ip, sq8_order, generic, wanted_mode, &space, &chunks, &mode, &has));
+    return py::make_tuple(py::make_tuple(space, chunks, mode), has);
+  }, py::arg("dim"), py::arg("ip"), py::arg("sq8_order"), py::arg("generic"), py::arg("wanted_mode"));
+  // the list of search kernel variants: (space, chunks, mode, l2_only) per row
+  m.def("search_variants", [] {
+    py::list rows;
+    uint32_t count = 1;
+    for (uint32_t i = 0; i < count; ++i) {
+      int space = 0, l2_only = 0;
+      uint32_t chunks = 0, mode = 0;
+      check(alaya_search_variant_at(i, &space, &chunks, &mode, &l2_only, &count));
+      rows.append(py::make_tuple(space, chunks, mode, l2_only != 0));
+    }
+    return rows;
+  });
   m.def("device_count", [] {
     int c = 0;
     check(alaya_device_count(&c));

@@ -199,7 +199,7 @@ __device__ __forceinline__ void issue_rows(const SearchParams &p, const uint32_t
 }
 
 // Distances of an issued pass -> out[base + g + 8r].  The kChunks > 0 kernels run only for
-// dim == 32 * kChunks (search_kernel_symbol / the build's dispatch pick them from dim % 32 == 0), so
+// dim == 32 * kChunks (resolve_search_variant / the build's dispatch pick them from dim % 32 == 0), so
 // there is no 8-block or scalar tail.  Row slots past n (wave-uniform) are skipped whole.
 template <bool kIP, int kChunks, int kRows = 0>
 __device__ __forceinline__ void finish_rows(const SearchParams &p, const float *q, int n, int base,

@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "search_variants.h"
+
 namespace alaya_amd {
 
 // Everything one search launch reads or writes.  All pointers are device pointers.
@@ -82,7 +84,7 @@ struct SearchParams {
                           // twice the resident searchers, each with half the rows in flight
   uint32_t *help_stats;   // nullable: per searcher, (fresh distances it took from a memo, expansions
                           // with every fresh distance from the memo, rows it computed as a helper)
-  // Candidate screen (search_has_screen; kMode 16): once the pool is full, an expansion's fresh
+  // Candidate screen (search_has_screen; kModeScreen): once the pool is full, an expansion's fresh
   // candidates are first measured on an f16 copy of their rows, and only those whose proven lower
   // bound (screen_bound.h) is below the pool's worst distance read their f32 row.
   uint32_t screen;             // 1 = the screening kernel
@@ -111,7 +113,7 @@ struct RerankParams {
 };
 
 constexpr uint32_t kVisWide = 0xffffffffu;
-constexpr size_t kHelpBoardBytes = 256;  // the helpers' request board (search kernel, kMode 4)
+constexpr size_t kHelpBoardBytes = 256;  // the helpers' request board (search kernel, kModeHelp)
 #ifndef ALAYA_HELP_DEPTH
 #define ALAYA_HELP_DEPTH 1
 #endif
@@ -133,19 +135,17 @@ __host__ __device__ inline size_t search_shared_lds_bytes(uint32_t stride, bool 
 }
 // rerank: p.base/p.queries are the raw f32 rows and the (normalised) f32 queries
 hipError_t launch_rerank(const SearchParams &p, const RerankParams &r, hipStream_t stream);
-hipError_t search_occupancy(const SearchParams &p, int waves, size_t lds, int *blocks_per_cu);
-// whether a search of this shape has a helper kernel (SearchParams::help)
-bool search_has_helpers(uint32_t dim, int sq8_order, bool generic);
-// whether a search of this shape has a two-waves-per-SIMD kernel (SearchParams::two_waves)
-bool search_has_two_waves(uint32_t dim, int sq8_order, bool generic);
-// whether a search of this shape has a screening kernel (SearchParams::screen): L2 on wide f32 rows
-bool search_has_screen(uint32_t dim, int sq8_order, bool generic, bool ip);
+// resident workgroups per CU of variant `v`'s kernel (search_variants.h) for the metric
+hipError_t search_occupancy(const SearchVariant &v, bool ip, int waves, size_t lds, int *blocks_per_cu);
 // The screening copy of rows [first, first + count): out_rows[r] = f16(base[r]) (stride halfs per
 // row) and out_err[r] >= ||base[r] - f16(base[r])||_2, +inf for a row with an element that is not
 // finite in f16.
 hipError_t launch_screen_rows(const float *base, uint64_t first, uint64_t count, uint32_t stride,
                               uint16_t *out_rows, float *out_err, hipStream_t stream);
-hipError_t launch_search(const SearchParams &p, int grid, int waves, size_t lds, hipStream_t stream);
+// launches variant `v`'s kernel: the one resolve_search_variant chose and p.help / p.two_waves /
+// p.screen / the LDS layout were planned for
+hipError_t launch_search(const SearchVariant &v, const SearchParams &p, int grid, int waves, size_t lds,
+                         hipStream_t stream);
 // out[q * n + i] = dist(queries[q], base[ids[i]]) for q < nq (bit-exact device distance)
 hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint32_t n,
                                 uint32_t nq, float *out, hipStream_t stream);

@@ -51,7 +51,7 @@ constexpr bool space_tab() { return kSpace == 2; }
 
 template <int kChunks, int kSpace, int kMode = 0>
 constexpr int search_min_waves() {
-  if constexpr ((kMode & 8) != 0) return 2;  // the two-waves-per-SIMD wide-row kernels
+  if constexpr ((kMode & alaya_amd::kModeTwoWaves) != 0) return 2;  // the two-waves-per-SIMD wide-row kernels
   if constexpr (space_sq8<kSpace>()) {
     if (ALAYA_MIN_WAVES_SQ8 >= 0) return ALAYA_MIN_WAVES_SQ8;
     return kSpace == 2 && kChunks > 0 ? 4 : 0;
@@ -578,14 +578,7 @@ __device__ void help_siblings(const SearchParams &p, unsigned char *smem, const 
 // --------------------------------------------------------------------------------------------
 // The search kernel.
 // --------------------------------------------------------------------------------------------
-// kMode bits: 1 = diagnostic build that accumulates s_memtime cycles per phase into p.stamps
-// (nq x 8): [0] init + overlay descent, [1] pop, [2] adjacency load + visited set, [3] distances,
-// [4] merge, [5] expansions after the visited table spilled, [6] whole query, [7] prefetch hits;
-// 2 = the spill-table prefetch check (ALAYA_SPILL_FLAGS bit 8: every bucket read one expansion ahead
-// is compared with a re-read at its use, and a stale one marks the query's counters);
-// 4 = distance helpers (SearchParams::help): a wave with no query left computes the distances of a
-// sibling's next expansion into a memo the sibling reads (help_siblings below);
-// 8 = two waves per SIMD for wide f32 rows (one row per lane group, SearchParams::two_waves).
+// kMode is a set of the kMode* bits of search_variants.h, which also lists the instantiations.
 // A workgroup holds blockDim.x / 64 waves (1 for wide f32 rows; 4 for SQ8, which share the
 // quantizer's scale / min, and for searches with helpers); each wave is an independent persistent
 // searcher with its own visited spill slot.  After fill_shared the waves never wait on each other.
@@ -594,16 +587,16 @@ __global__ void __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(search_min_waves<kChunks, kSpace, kMode>() ? search_min_waves<kChunks, kSpace, kMode>() : 1,
                                        8))) hnsw_search_kernel(SearchParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr bool kStamp = (kMode & 1) != 0;
-  constexpr bool kCheck = (kMode & 2) != 0;
-  constexpr bool kHelp = (kMode & 4) != 0;
-  constexpr int kRows = (kMode & 8) != 0 ? 1 : 0;
+  constexpr bool kStamp = (kMode & kModeStamp) != 0;
+  constexpr bool kCheck = (kMode & kModeCheck) != 0;
+  constexpr bool kHelp = (kMode & kModeHelp) != 0;
+  constexpr int kRows = (kMode & kModeTwoWaves) != 0 ? 1 : 0;
   // Candidate screen (f32 L2 rows of d >= 512, no helpers): rows per lane group of the f16 pass --
   // 4 (32 candidates, a whole expansion of an R = 32 graph, in 2 kChunks float4 of registers), or 2
   // in the two-waves-per-SIMD kernels' half register budget.
-  constexpr bool kScreen = (kMode & 16) != 0;
+  constexpr bool kScreen = (kMode & kModeScreen) != 0;
   static_assert(!kScreen || (kSpace == 0 && !kIP && !kHelp && kChunks >= 16 && kChunks % 2 == 0), "screen: wide f32 L2 rows");
-  constexpr int kScreenRows = (kMode & 8) != 0 ? 2 : 4;
+  constexpr int kScreenRows = (kMode & kModeTwoWaves) != 0 ? 2 : 4;
   uint32_t n_screened = 0, n_screened_out = 0;  // wave-uniform, over the searcher's queries
   const int lane = lane_id();
   const int wave = static_cast<int>(threadIdx.x >> 6);
@@ -1110,51 +1103,25 @@ hipError_t launch_rerank(const SearchParams &p, const RerankParams &r, hipStream
   return hipGetLastError();
 }
 
-template <bool kIP, int kChunks, int kMode = 0, int kSpace = 0>
+template <bool kIP, int kChunks, int kMode, int kSpace>
 static const void *kernel_ptr() {
   return reinterpret_cast<const void *>(&hnsw_search_kernel<kIP, kChunks, kMode, kSpace>);
 }
 
-template <int kSpace>
-static const void *sq8_symbol(bool ip, uint32_t dim, bool stamped, bool check, bool help) {
-  const uint32_t chunks = (dim % 32 == 0) ? dim / 32 : 0;
-  if constexpr (kSpace == 2) {  // stamped with helpers (tools/profile_phases.py)
-    if (stamped && help && chunks == 24) return ip ? kernel_ptr<true, 24, 5, kSpace>() : kernel_ptr<false, 24, 5, kSpace>();
-  }
-  if (stamped && chunks == 24) return ip ? kernel_ptr<true, 24, 1, kSpace>() : kernel_ptr<false, 24, 1, kSpace>();
-  if constexpr (kSpace == 2) {  // the spill-table prefetch check (config 5's d = 768 and d = 960)
-    if (check && chunks == 24) return ip ? kernel_ptr<true, 24, 2, kSpace>() : kernel_ptr<false, 24, 2, kSpace>();
-    if (check && chunks == 30) return ip ? kernel_ptr<true, 30, 2, kSpace>() : kernel_ptr<false, 30, 2, kSpace>();
-    if (help && chunks == 4) return ip ? kernel_ptr<true, 4, 4, kSpace>() : kernel_ptr<false, 4, 4, kSpace>();
-    if (help && chunks == 24) return ip ? kernel_ptr<true, 24, 4, kSpace>() : kernel_ptr<false, 24, 4, kSpace>();
-    if (help && chunks == 30) return ip ? kernel_ptr<true, 30, 4, kSpace>() : kernel_ptr<false, 30, 4, kSpace>();
-  }
-  if (chunks == 4) return ip ? kernel_ptr<true, 4, 0, kSpace>() : kernel_ptr<false, 4, 0, kSpace>();
-  if (chunks == 24) return ip ? kernel_ptr<true, 24, 0, kSpace>() : kernel_ptr<false, 24, 0, kSpace>();
-  if (chunks == 30) return ip ? kernel_ptr<true, 30, 0, kSpace>() : kernel_ptr<false, 30, 0, kSpace>();
-  return ip ? kernel_ptr<true, 0, 0, kSpace>() : kernel_ptr<false, 0, 0, kSpace>();
-}
+// The kernels of search_variants.h's list, row for row.
+struct SearchKernels {
+  const void *ip, *l2;
+};
+#define ALAYA_IP_both(S, C, M) kernel_ptr<true, C, M, S>()
+#define ALAYA_IP_l2(S, C, M) nullptr
+#define ALAYA_KERNEL_ROW(S, C, M, METRICS) {ALAYA_IP_##METRICS(S, C, M), kernel_ptr<false, C, M, S>()},
+static const SearchKernels kSearchKernels[] = {ALAYA_SEARCH_VARIANTS(ALAYA_KERNEL_ROW)};
+#undef ALAYA_KERNEL_ROW
+static_assert(sizeof(kSearchKernels) / sizeof(kSearchKernels[0]) == kNumSearchVariants, "one kernel row per variant");
 
-// Whether a search has a helper kernel (kMode 4): the small-row f32 kernels (d = 128 / 256, the
-// latency-bound SIFT shape) and the AVX-512-order SQ8 kernels with a compile-time chunk count.  The
-// wide f32 rows (GIST, the headline) are bandwidth-bound: helpers would add bytes, not overlap.
-bool search_has_two_waves(uint32_t dim, int sq8_order, bool generic) {
-  return sq8_order == 0 && !generic && (dim == 24 * 32 || dim == 30 * 32);
-}
-
-bool search_has_helpers(uint32_t dim, int sq8_order, bool generic) {
-  if (generic || dim % 32 != 0) return false;
-  const uint32_t chunks = dim / 32;
-  if (sq8_order == 2) return chunks == 4 || chunks == 24 || chunks == 30;
-  if (sq8_order == 1) return false;
-  return chunks == 4 || chunks == 8;
-}
-
-// Whether a search has a screening kernel (kMode 16): L2 on the wide f32 rows, d = 512 / 768 / 960 /
-// 1024 -- the bandwidth-bound shapes.  The small-row kernels are latency-bound (a dependent second
-// pass would only add to the chain); IP and COS have no proven bound here.
-bool search_has_screen(uint32_t dim, int sq8_order, bool generic, bool ip) {
-  return sq8_order == 0 && !generic && !ip && (dim == 16 * 32 || dim == 24 * 32 || dim == 30 * 32 || dim == 32 * 32);
+static const void *search_kernel_symbol(const SearchVariant &v, bool ip) {
+  const SearchKernels &k = kSearchKernels[&v - kSearchVariants];
+  return ip ? k.ip : k.l2;
 }
 
 hipError_t launch_screen_rows(const float *base, uint64_t first, uint64_t count, uint32_t stride,
@@ -1166,47 +1133,11 @@ hipError_t launch_screen_rows(const float *base, uint64_t first, uint64_t count,
   return hipGetLastError();
 }
 
-const void *search_kernel_symbol(bool ip, uint32_t dim, bool stamped, int sq8_order, bool generic, bool check,
-                                 bool help, bool two_waves, bool screen) {
-  if (sq8_order == 2) return sq8_symbol<2>(ip, dim, stamped, check, help);
-  if (sq8_order == 1) return sq8_symbol<1>(ip, dim, stamped, false, false);
-  const uint32_t chunks = (!generic && dim % 32 == 0) ? dim / 32 : 0;  // generic order: the runtime-d kernel
-  if (screen && !stamped && !help && !ip) {
-    if (two_waves && chunks == 24) return kernel_ptr<false, 24, 24>();
-    if (two_waves && chunks == 30) return kernel_ptr<false, 30, 24>();
-    if (chunks == 16) return kernel_ptr<false, 16, 16>();
-    if (chunks == 24) return kernel_ptr<false, 24, 16>();
-    if (chunks == 30) return kernel_ptr<false, 30, 16>();
-    if (chunks == 32) return kernel_ptr<false, 32, 16>();
-  }
-  if (stamped) {
-    if (help && chunks == 4) return ip ? kernel_ptr<true, 4, 5>() : kernel_ptr<false, 4, 5>();
-    if (chunks == 30) return ip ? kernel_ptr<true, 30, 1>() : kernel_ptr<false, 30, 1>();
-    if (chunks == 4) return ip ? kernel_ptr<true, 4, 1>() : kernel_ptr<false, 4, 1>();
-    return ip ? kernel_ptr<true, 0, 1>() : kernel_ptr<false, 0, 1>();
-  }
-  if (help && chunks == 4) return ip ? kernel_ptr<true, 4, 4>() : kernel_ptr<false, 4, 4>();
-  if (help && chunks == 8) return ip ? kernel_ptr<true, 8, 4>() : kernel_ptr<false, 8, 4>();
-  if (two_waves && chunks == 24) return ip ? kernel_ptr<true, 24, 8>() : kernel_ptr<false, 24, 8>();
-  if (two_waves && chunks == 30) return ip ? kernel_ptr<true, 30, 8>() : kernel_ptr<false, 30, 8>();
-#define ALAYA_CASE(C)                                                        \
-  if (chunks == C) return ip ? kernel_ptr<true, C>() : kernel_ptr<false, C>();
-  ALAYA_CASE(4)
-  ALAYA_CASE(8)
-  ALAYA_CASE(16)
-  ALAYA_CASE(24)
-  ALAYA_CASE(30)
-  ALAYA_CASE(32)
-#undef ALAYA_CASE
-  return ip ? kernel_ptr<true, 0>() : kernel_ptr<false, 0>();
-}
-
-hipError_t launch_search(const SearchParams &p, int grid, int waves, size_t lds, hipStream_t stream) {
-  const void *fn = search_kernel_symbol(p.ip, p.dim, p.stamps != nullptr, p.sq8_order, p.generic,
-                                        (p.spill_flags & 256u) != 0, p.help != 0, p.two_waves != 0, p.screen != 0);
+hipError_t launch_search(const SearchVariant &v, const SearchParams &p, int grid, int waves, size_t lds,
+                         hipStream_t stream) {
   SearchParams arg = p;
   void *args[] = {&arg};
-  return hipLaunchKernel(fn, dim3(grid), dim3(64 * waves), args, lds, stream);
+  return hipLaunchKernel(search_kernel_symbol(v, p.ip), dim3(grid), dim3(64 * waves), args, lds, stream);
 }
 
 hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint32_t n,
@@ -1221,10 +1152,8 @@ hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint
   return hipGetLastError();
 }
 
-hipError_t search_occupancy(const SearchParams &p, int waves, size_t lds, int *blocks_per_cu) {
-  const void *fn = search_kernel_symbol(p.ip, p.dim, p.stamps != nullptr, p.sq8_order, p.generic,
-                                        (p.spill_flags & 256u) != 0, p.help != 0, p.two_waves != 0, p.screen != 0);
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, 64 * waves, lds);
+hipError_t search_occupancy(const SearchVariant &v, bool ip, int waves, size_t lds, int *blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, search_kernel_symbol(v, ip), 64 * waves, lds);
 }
 
 }  // namespace alaya_amd

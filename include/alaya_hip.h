@@ -268,6 +268,17 @@ int alaya_index_screen_stats(alaya_index *ix, uint64_t *screened, uint64_t *scre
  * out[i] <= the reference's f32 L2 distance of any q, x of `dim` elements for which d_tilde[i] is an
  * f32 sum in any order of (q_j - y_j)^2 over a copy y of x, and e_row[i] >= ||x - y||_2. */
 int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t n, uint32_t dim, float *out);
+/* Which graph-search kernel a request gets, evaluated on the host from the list every launch is
+ * planned from (csrc/search_variants.h).  A kernel variant is (space: 0 = f32 rows, 1 / 2 = SQ8 codes
+ * in the AVX2 / AVX-512 order; chunks: dim / 32, 0 = the runtime-d kernel; mode: a set of feature bits
+ * -- 1 phase stamps, 2 spill-table prefetch check, 4 distance helpers, 8 two waves per SIMD, 16
+ * candidate screen).  alaya_search_variant: the variant chosen for a search that wants the features
+ * `wanted_mode` (its mode is a subset of them), and in *has_mode the bits 4 / 8 / 16 for which this
+ * shape has a kernel at all.  alaya_search_variant_at: row `index` of the list, *count its length. */
+int alaya_search_variant(uint32_t dim, int ip, int sq8_order, int generic, uint32_t wanted_mode, int *space,
+                         uint32_t *chunks, uint32_t *mode, uint32_t *has_mode);
+int alaya_search_variant_at(uint32_t index, int *space, uint32_t *chunks, uint32_t *mode, int *l2_only,
+                            uint32_t *count);
 /* The last graph search's launch shape: persistent workgroups and searchers (waves) per workgroup --
  * workgroups x waves is the number of queries the launch runs at once (introspection). */
 int alaya_index_last_launch(const alaya_index *ix, uint32_t *workgroups, uint32_t *waves_per_group);

@@ -114,3 +114,14 @@ def test_two_waves_wide_row_kernels(census, kernel):
     assert r["restores_in_expansion_loops"] == 0, r
     one = census[kernel.replace("stamp=8", "stamp=0")]
     assert one["Occupancy"] == 1 and one.get("ScratchSize", 0) == 0, one
+
+
+# Occupancy (waves per SIMD) and scratch bytes of the d = 960 screening kernels, read from the
+# compiler's resource comments in the assembly of the commit that added them (the screen, round 7):
+# 256 VGPRs + 176 AGPRs at one wave, 197 VGPRs at two.
+@pytest.mark.parametrize("kernel, occupancy, scratch", [("l2 chunks=30 stamp=16 space=f32", 1, 0),
+                                                        ("l2 chunks=30 stamp=24 space=f32", 2, 0)])
+def test_screening_kernels_are_in_the_census(census, kernel, occupancy, scratch):
+    """kMode 16 / 24 (two-digit modes): the headline's screening kernels by their census names."""
+    r = census[kernel]
+    assert r["Occupancy"] == occupancy and r.get("ScratchSize", 0) == scratch, r
