@@ -18,6 +18,7 @@
 #include "build_kernels.h"
 #include "graph_update.h"
 #include "hnsw_build.h"
+#include "flat_bound.h"
 #include "flat_kernels.h"
 #include <cstdlib>
 #include "screen_bound.h"
@@ -117,6 +118,7 @@ struct alaya_index {
   DevBuf codes, sq_min, sq_max, rr_q_buf, sq_ids, sq_d;
   // flat path
   DevBuf norms, cand_d, cand_i, flat_tau, flag_buf, iota, flat_q;
+  DevBuf flat_bias;  // IP / COS: the scans' per-row bias, zeros in place of |b|^2 (ensure_norms)
   int flat_contraction = -1;  // the last flat search's: 0 = f32, 1 = bf16 hi/lo split, 2 = single-pass f16
   bool norms_ready = false;
   // single-role f16 flat scan: the base's tile records (alaya_amd::launch_flat_tiles), built at the
@@ -124,6 +126,7 @@ struct alaya_index {
   DevBuf flat_tiles, tiles_cand, tiles_qexp;  // the records; the scan's candidate buffers, query scales
   bool tiles_ready = false;
   int tiles_exp = 0;
+  int tiles_metric = -1;  // the metric whose bias the records' tails carry
   float max_norm = 0.f;
   // scratch
   DevBuf work, overflow, dirty, stab, q_buf, id_buf, dist_buf, cnt_buf, dlist_buf, dout_buf;
@@ -674,6 +677,11 @@ void ensure_norms(alaya_index *ix, hipStream_t stream) {
   float mx = 0.f;
   for (float v : h) mx = std::max(mx, v);
   ix->max_norm = std::sqrt(mx) * 1.0001f;
+  if (ix->metric != ALAYA_METRIC_L2) {
+    // inner products rank by the contraction alone: the scans read zeros where L2 reads |b|^2
+    ix->flat_bias.reserve(std::max<uint64_t>(ix->n, 1) * 4);
+    hip_check(hipMemsetAsync(ix->flat_bias.ptr, 0, std::max<uint64_t>(ix->n, 1) * 4, stream), "flat bias");
+  }
   ix->norms_ready = true;
 }
 
@@ -708,16 +716,23 @@ int flat_tiles_chunks(alaya_index *ix, uint64_t nq, uint64_t scan_tiles) {
   return static_cast<int>(best);
 }
 
+// the flat scans' per-row bias: |b|^2 for L2, zeros for IP / COS
+const float *flat_bias(const alaya_index *ix) {
+  return ix->metric == ALAYA_METRIC_L2 ? ix->norms.as<float>() : ix->flat_bias.as<float>();
+}
+
 void ensure_tiles(alaya_index *ix, int base_exp, hipStream_t stream) {
-  if (ix->tiles_ready && ix->tiles_exp == base_exp) return;
+  // records built for another metric carry the wrong bias: never reused (set_base also drops them)
+  if (ix->tiles_ready && ix->tiles_exp == base_exp && ix->tiles_metric == ix->metric) return;
   const size_t bytes = alaya_amd::flat_tiles_bytes(ix->stride, ix->n);
   ix->flat_tiles.reserve(std::max<size_t>(bytes, 256));
-  hip_check(alaya_amd::launch_flat_tiles(ix->base.as<float>(), ix->n, ix->stride, ix->norms.as<float>(),
+  hip_check(alaya_amd::launch_flat_tiles(ix->base.as<float>(), ix->n, ix->stride, flat_bias(ix),
                                          ix->has_valid ? ix->valid.as<uint32_t>() : nullptr, base_exp,
                                          ix->flat_tiles.as<unsigned char>(), stream),
             "flat tile records");
   ix->tiles_ready = true;
   ix->tiles_exp = base_exp;
+  ix->tiles_metric = ix->metric;
 }
 
 // Prescan: the same scan over rows 0, S, 2S, ... (S = ALAYA_FLAT_PRESCAN; default 0 = off: on
@@ -792,7 +807,8 @@ alaya_amd::FlatParams flat_params(alaya_index *ix, const float *d_q, uint64_t nq
                                   float *d_dists, uint32_t *d_flags, int *blocks, hipStream_t stream,
                                   bool no_single = false) {
   if (!ix->base.ptr) throw ArgError("index has no base vectors");
-  if (ix->metric != ALAYA_METRIC_L2) throw ArgError("the flat MFMA path supports the L2 metric");
+  if (ix->metric != ALAYA_METRIC_L2 && ix->metric != ALAYA_METRIC_IP && ix->metric != ALAYA_METRIC_COS)
+    throw ArgError("the flat MFMA path supports the L2, IP and COS metrics");
   if (ix->generic) throw ArgError("the flat MFMA path ranks float32 rows (not the generic non-float order)");
   if (alaya_amd::flat_scan_lds(ix->stride) == 0) throw ArgError("no flat MFMA scan for this row stride");
   if (k == 0 || k > static_cast<uint32_t>(alaya_amd::flat_max_k()))
@@ -802,7 +818,8 @@ alaya_amd::FlatParams flat_params(alaya_index *ix, const float *d_q, uint64_t nq
   p.n = ix->n;
   p.dim = ix->dim;
   p.stride = ix->stride;
-  p.norms = ix->norms.as<float>();
+  p.norms = flat_bias(ix);
+  p.ip = ix->metric != ALAYA_METRIC_L2;
   p.valid = ix->has_valid ? ix->valid.as<uint32_t>() : nullptr;
   p.max_norm = ix->max_norm;
   // The contraction that ranks the shortlist (all three feed the same exact rescoring and proof):
@@ -2163,6 +2180,22 @@ int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t 
   return guarded([&] {
     if (n && (!d_tilde || !e_row || !out)) throw ArgError("invalid arguments");
     for (uint64_t i = 0; i < n; ++i) out[i] = alaya_amd::screen_lower_bound(d_tilde[i], e_row[i], dim);
+  });
+}
+
+int alaya_flat_ip_slack(int contraction, uint32_t k_acc, const float *q_norm2, const int *q_exp, uint64_t n,
+                        float b_max, int base_exp, float *out) {
+  return guarded([&] {
+    if (contraction < 0 || contraction > 2 || (n && (!q_norm2 || !out))) throw ArgError("invalid arguments");
+    for (uint64_t i = 0; i < n; ++i)
+      out[i] = alaya_amd::flat_ip_slack(contraction, k_acc, q_norm2[i], q_exp ? q_exp[i] : 0, b_max, base_exp);
+  });
+}
+
+int alaya_flat_ip_proven(const float *kth_d, const float *cutoff, const float *slack, uint64_t n, uint8_t *out) {
+  return guarded([&] {
+    if (n && (!kth_d || !cutoff || !slack || !out)) throw ArgError("invalid arguments");
+    for (uint64_t i = 0; i < n; ++i) out[i] = alaya_amd::flat_ip_proven(kth_d[i], cutoff[i], slack[i]) ? 1 : 0;
   });
 }
 

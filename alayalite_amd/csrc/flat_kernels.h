@@ -12,7 +12,7 @@ struct FlatParams {
   uint64_t n;
   uint32_t dim;
   uint32_t stride;     // multiple of 32
-  const float *norms;  // |b|^2 per row
+  const float *norms;  // |b|^2 per row (ip: zeros)
   const uint32_t *valid;  // validity bitmap (bit i of word i/32), nullable = all rows valid;
                           // removed / invalid rows are never returned
   float max_norm;      // max |b|
@@ -45,6 +45,10 @@ struct FlatParams {
   uint32_t tile_step;          // 1 = every record; the prescan's sample takes every tile_step-th
   uint64_t *tiles_buf;         // its candidate buffers: blocks x flat_tiles_queries() x flat_tiles_buf() entries
   int *tiles_qexp;             // its scale exponent t per query (one per wave of 32 queries), for the merge's bound
+  int ip;                      // 1 = inner product (IP, or COS on normalised rows): rank by -(q.b).  `norms` (and the
+                               // tile records' tails) then hold a zero bias, so every scan ranks -2 C~ with its L2
+                               // code; max_norm stays max |b|.  The merge rescores with the reference's IP order
+                               // and proves the shortlist with flat_bound.h
 };
 
 int flat_shortlist();

@@ -5,7 +5,9 @@
 // Result contract: the k nearest rows by the reference metric function (l2_sqr_avx2 order, the same
 // device function as the graph search) with ties broken by id, plus a per-query flag that is set
 // when the shortlist cannot be proven to contain them (error bound below) -- the host then
-// recomputes that query exhaustively.
+// recomputes that query exhaustively.  Inner products (FlatParams::ip; COS is IP on normalised rows)
+// run the same scans with a zero bias in place of |b|^2, so they rank -2 q.b; the merge then rescores
+// in the ip_sqr_avx2 order and proves the shortlist with flat_bound.h's bound.
 //
 // flat_scan_kernel: 256 threads = 4 waves, 128 queries per block (32 per wave), one base chunk per
 // block.  Each wave holds its 32 queries as MFMA A fragments in VGPRs: lane l owns query (l & 31),
@@ -26,6 +28,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "flat_bound.h"
 #include "flat_kernels.h"
 
 namespace alaya_amd {
@@ -60,7 +63,7 @@ __device__ __forceinline__ void split_bf16(float x, __bf16 &hi, __bf16 &lo) {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 constexpr int kF16Top = 15;    // scaled operands stay below 2^15 (f16 max 65504)
-constexpr int kF16MaxExp = 100;  // |s + t| beyond this: the query is flagged (its scale-back leaves f32's range)
+constexpr int kF16MaxExp = kFlatF16MaxExp;  // |s + t| beyond this: the query is flagged (its scale-back leaves f32's range)
 // 2^t with |x| 2^t < 2^kF16Top for every |x| <= maxabs (0 for a zero or non-finite maxabs)
 __device__ __host__ __forceinline__ int f16_exp(float maxabs) {
   if (!(maxabs > 0.f) || !(maxabs < 3.0e38f)) return 0;
@@ -1533,6 +1536,34 @@ __device__ float exact_l2(const FlatParams &p, const float *q, uint32_t id, int 
   return res;
 }
 
+// The same for the inner-product distance (ip_sqr_avx2 order: the products fused into the
+// accumulators, the same combine tree and tails, negated last -- a zero query gives -0.0f).
+__device__ float exact_ip(const FlatParams &p, const float *q, uint32_t id, int m) {
+  const float *row = p.base + static_cast<uint64_t>(id) * p.stride;
+  const int T = static_cast<int>(p.dim >> 5);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (int t = 0; t < T; ++t) {
+    const float4 x = *reinterpret_cast<const float4 *>(q + 32 * t + 4 * m);
+    const float4 y = *reinterpret_cast<const float4 *>(row + 32 * t + 4 * m);
+    a0 = fmaf(x.x, y.x, a0); a1 = fmaf(x.y, y.y, a1); a2 = fmaf(x.z, y.z, a2); a3 = fmaf(x.w, y.w, a3);
+  }
+  const int nb8 = (static_cast<int>(p.dim) - 32 * T) >> 3;
+  if (m < 2) {
+    for (int bb = 0; bb < nb8; ++bb) {
+      const float4 x = *reinterpret_cast<const float4 *>(q + 32 * T + 8 * bb + 4 * m);
+      const float4 y = *reinterpret_cast<const float4 *>(row + 32 * T + 8 * bb + 4 * m);
+      a0 = fmaf(x.x, y.x, a0); a1 = fmaf(x.y, y.y, a1); a2 = fmaf(x.z, y.z, a2); a3 = fmaf(x.w, y.w, a3);
+    }
+  }
+  a0 += __shfl_xor(a0, 2); a1 += __shfl_xor(a1, 2); a2 += __shfl_xor(a2, 2); a3 += __shfl_xor(a3, 2);
+  a0 += __shfl_xor(a0, 4); a1 += __shfl_xor(a1, 4); a2 += __shfl_xor(a2, 4); a3 += __shfl_xor(a3, 4);
+  const float s0 = a0 + __shfl_xor(a0, 1), s1 = a1 + __shfl_xor(a1, 1);
+  const float s2 = a2 + __shfl_xor(a2, 1), s3 = a3 + __shfl_xor(a3, 1);
+  float res = (s0 + s1) + (s2 + s3);
+  for (int e = 32 * T + 8 * nb8; e < static_cast<int>(p.dim); ++e) res = fmaf(q[e], row[e], res);
+  return -res;
+}
+
 // The shortlist bound's slack on one query: rows outside the shortlist have true distance >=
 // cutoff + |q|^2 - eps, and the exact k-th result is within gam of its f32 value.  The shortlist
 // GEMM error is <= gam * (|q|^2 + max|b|^2 + 2|q| max|b|), gam = 2 k_acc u (u = 2^-24, conservative);
@@ -1566,8 +1597,36 @@ __device__ __forceinline__ float shortlist_eps(const FlatParams &p, float qn, fl
   return eps;
 }
 
+// Whether the merged shortlist provably holds the query's exact top-k (the flag is its negation):
+// the L2 bound above, or for inner products flat_bound.h's (the scans then rank -2 C~: p.norms is a
+// zero bias).  The merge kernels are compiled once per metric (kIp), so the L2 instantiations keep
+// the code they had before inner products existed.
+template <bool kIp>
+__device__ __forceinline__ bool shortlist_proven(const FlatParams &p, float qn, float qmax, uint64_t qi, float kth_d,
+                                                 float cutoff) {
+  if constexpr (kIp) {
+    const int t = p.single ? (p.tiles_qexp ? p.tiles_qexp[qi] : f16_exp(qmax)) : 0;
+    const float slack = flat_ip_slack(p.single ? kFlatF16 : (p.split ? kFlatSplit : kFlatF32), p.k_acc, qn, t,
+                                      p.max_norm, p.base_exp);
+    return flat_ip_proven(kth_d, cutoff, slack);
+  } else {
+    float gam = 0.f;
+    bool ok = true;
+    const float eps = shortlist_eps(p, qn, qmax, gam, ok, qi);
+    return ok && (kth_d * (1.0f + gam) < cutoff + qn - eps || cutoff == FLT_MAX);
+  }
+}
+
+// exact rescoring with the metric's reference order
+template <bool kIp>
+__device__ __forceinline__ float exact_dist(const FlatParams &p, const float *q, uint32_t id, int m) {
+  if constexpr (kIp) return exact_ip(p, q, id, m);
+  else return exact_l2(p, q, id, m);
+}
+
 // One wave per query: merge the chunk shortlists (approximate distances), rescore the best kL
 // exactly, sort by (exact distance, id), emit k, flag the query if the bound does not hold.
+template <bool kIp>
 __global__ void __launch_bounds__(64) flat_merge_kernel(FlatParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float *q = reinterpret_cast<float *>(smem);
@@ -1618,7 +1677,7 @@ __global__ void __launch_bounds__(64) flat_merge_kernel(FlatParams p) {
     for (int base = 0; base < kL; base += 8) {
       const uint32_t id = li[base + g];
       const bool ok = id != 0xffffffffu;
-      const float d = exact_l2(p, q, ok ? id : 0u, m);
+      const float d = exact_dist<kIp>(p, q, ok ? id : 0u, m);
       if (m == 0) ed[base + g] = ok ? d : FLT_MAX;
     }
     wave_fence();
@@ -1646,10 +1705,7 @@ __global__ void __launch_bounds__(64) flat_merge_kernel(FlatParams p) {
       const uint64_t mk = __ballot(lane < kL && rank == p.k - 1);
       kth_d = mk ? __shfl(dv, __ffsll(static_cast<unsigned long long>(mk)) - 1) : FLT_MAX;
     }
-    float gam = 0.f;
-    bool ok = true;
-    const float eps = shortlist_eps(p, qn, qmax, gam, ok, qi);
-    const bool exact = ok && (kth_d * (1.0f + gam) < cutoff + qn - eps || cutoff == FLT_MAX);
+    const bool exact = shortlist_proven<kIp>(p, qn, qmax, qi, kth_d, cutoff);
     if (lane == 0 && p.flags) p.flags[qi] = exact ? 0u : 1u;
     wave_fence();
   }
@@ -1731,7 +1787,7 @@ __device__ __forceinline__ void fold_big(VF<R> &L, VU<R> &Li, const VF<R> &c, co
   for (int J = 32 * R; J > 0; J >>= 1) bitonic_stage<R>(L, Li, 64 * R, J);
 }
 
-template <int R>
+template <int R, bool kIp>
 __global__ void __launch_bounds__(64) flat_merge_big_kernel(FlatParams p) {
   constexpr int M = 64 * R;
   constexpr int kPerFold = M / kL;  // chunk lists per fold
@@ -1791,7 +1847,7 @@ __global__ void __launch_bounds__(64) flat_merge_big_kernel(FlatParams p) {
     for (int base = 0; base < M; base += 8) {
       const uint32_t id = lid[base + g];
       const bool ok = id != 0xffffffffu;
-      const float dd = exact_l2(p, q, ok ? id : 0u, m);
+      const float dd = exact_dist<kIp>(p, q, ok ? id : 0u, m);
       if (m == 0) led[base + g] = ok ? dd : FLT_MAX;
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1812,10 +1868,7 @@ __global__ void __launch_bounds__(64) flat_merge_big_kernel(FlatParams p) {
 #pragma unroll
     for (int r = 0; r < R; ++r)
       if ((p.k - 1) / 64 == static_cast<uint32_t>(r)) kth_d = __shfl(E[r], (p.k - 1) & 63);
-    float gam = 0.f;
-    bool ok = true;
-    const float eps = shortlist_eps(p, qn, qmax, gam, ok, qi);
-    const bool exact = ok && (kth_d * (1.0f + gam) < cutoff + qn - eps || cutoff == FLT_MAX);
+    const bool exact = shortlist_proven<kIp>(p, qn, qmax, qi, kth_d, cutoff);
     if (lane == 0 && p.flags) p.flags[qi] = exact ? 0u : 1u;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -2104,13 +2157,16 @@ hipError_t launch_flat_merge(const FlatParams &p, hipStream_t s) {
   const int grid = static_cast<int>(p.nq < 4096 ? p.nq : 4096);
   if (p.k <= static_cast<uint32_t>(kL - 8)) {
     const size_t lds = (static_cast<size_t>(std::max(p.stride, p.q_stride)) + 3 * kL + 2 * kBuf) * 4 + 64;
-    hipLaunchKernelGGL(flat_merge_kernel, dim3(grid), dim3(64), lds, s, p);
+    if (p.ip) hipLaunchKernelGGL(flat_merge_kernel<true>, dim3(grid), dim3(64), lds, s, p);
+    else hipLaunchKernelGGL(flat_merge_kernel<false>, dim3(grid), dim3(64), lds, s, p);
   } else if (p.k <= 128 - 28) {
     const size_t lds = (static_cast<size_t>(std::max(p.stride, p.q_stride)) + 2 * 128) * 4 + 64;
-    hipLaunchKernelGGL(flat_merge_big_kernel<2>, dim3(grid), dim3(64), lds, s, p);
+    if (p.ip) hipLaunchKernelGGL((flat_merge_big_kernel<2, true>), dim3(grid), dim3(64), lds, s, p);
+    else hipLaunchKernelGGL((flat_merge_big_kernel<2, false>), dim3(grid), dim3(64), lds, s, p);
   } else if (p.k <= static_cast<uint32_t>(flat_max_k())) {
     const size_t lds = (static_cast<size_t>(std::max(p.stride, p.q_stride)) + 2 * 256) * 4 + 64;
-    hipLaunchKernelGGL(flat_merge_big_kernel<4>, dim3(grid), dim3(64), lds, s, p);
+    if (p.ip) hipLaunchKernelGGL((flat_merge_big_kernel<4, true>), dim3(grid), dim3(64), lds, s, p);
+    else hipLaunchKernelGGL((flat_merge_big_kernel<4, false>), dim3(grid), dim3(64), lds, s, p);
   } else {
     return hipErrorInvalidValue;
   }

@@ -184,6 +184,30 @@ class PyIndexInterface {
     return py::make_tuple(r.first, r.second);
   }
 
+  // --- extra (not in the reference binding): the exact top-k over the index's own device rows (the
+  // flat search: every valid row, the index's metric, ties by id) -- what a recall measurement of
+  // batch_search at some ef needs.  Empty slots hold (the id type's maximum, FLT_MAX).
+  py::object exact_search(py::array queries, uint32_t topk) {
+    if (!graph_) throw std::runtime_error("Index is not init yet");
+    py::array q = prepare_queries(queries);
+    const uint64_t nq = q.shape(0);
+    std::vector<uint32_t> ids32(nq * topk);
+    py::array_t<float> dists({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_flat_search(ix_, static_cast<const float *>(q.data()), nq, topk, ids32.data(),
+                                    dists.mutable_data(), nullptr));
+    }
+    py::array ids(params_.id_type_, std::vector<py::ssize_t>{static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    if (id_bytes_ == 4) {
+      std::memcpy(ids.mutable_data(), ids32.data(), ids32.size() * 4);
+    } else {
+      auto *o = static_cast<uint64_t *>(ids.mutable_data());
+      for (size_t i = 0; i < ids32.size(); ++i) o[i] = ids32[i] == 0xffffffffu ? UINT64_MAX : ids32[i];
+    }
+    return py::make_tuple(ids, dists);
+  }
+
   py::array get_data_by_id(uint32_t id) {
     if (n_ == 0) throw std::runtime_error("space is nullptr");
     if (id >= n_) throw std::runtime_error("id out of range");
@@ -967,6 +991,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
            py::arg("ef"), py::arg("num_threads"))
       .def("batch_search_with_distance", &PyIndexInterface::batch_search_with_distance,
            py::arg("queries"), py::arg("topk"), py::arg("ef"), py::arg("num_threads"))
+      .def("exact_search", &PyIndexInterface::exact_search, py::arg("queries"), py::arg("topk"))
       .def("save", &PyIndexInterface::save, py::arg("index_path"), py::arg("data_path"),
            py::arg("quant_path") = std::string())
       .def("load", &PyIndexInterface::load, py::arg("index_path"), py::arg("data_path"),
@@ -1045,6 +1070,35 @@ PYBIND11_MODULE(_alayalitepy, m) {
                                    out.mutable_data()));
     return out;
   });
+  // the flat search's inner-product bound on the host (flat_bound.h): slack per query, and the test
+  m.def("flat_ip_slack", [](int contraction, uint32_t k_acc,
+                            py::array_t<float, py::array::c_style | py::array::forcecast> q_norm2,
+                            py::array_t<int, py::array::c_style | py::array::forcecast> q_exp, float b_max, int base_exp) {
+    if (q_exp.size() != 0 && q_exp.size() != q_norm2.size()) throw std::invalid_argument("q_norm2 and q_exp differ in size");
+    py::array_t<float> out(q_norm2.size());
+    check(alaya_flat_ip_slack(contraction, k_acc, q_norm2.data(), q_exp.size() ? q_exp.data() : nullptr,
+                              static_cast<uint64_t>(q_norm2.size()), b_max, base_exp, out.mutable_data()));
+    return out;
+  }, py::arg("contraction"), py::arg("k_acc"), py::arg("q_norm2"), py::arg("q_exp"), py::arg("b_max"),
+     py::arg("base_exp") = 0);
+  m.def("flat_ip_proven", [](py::array_t<float, py::array::c_style | py::array::forcecast> kth_d,
+                             py::array_t<float, py::array::c_style | py::array::forcecast> cutoff,
+                             py::array_t<float, py::array::c_style | py::array::forcecast> slack) {
+    if (kth_d.size() != cutoff.size() || kth_d.size() != slack.size()) throw std::invalid_argument("sizes differ");
+    py::array_t<uint8_t> out(kth_d.size());
+    check(alaya_flat_ip_proven(kth_d.data(), cutoff.data(), slack.data(), static_cast<uint64_t>(kth_d.size()),
+                               out.mutable_data()));
+    return out;
+  }, py::arg("kth_d"), py::arg("cutoff"), py::arg("slack"));
+  // a float32 copy with each row normalised as fit does for COS (alaya_amd::normalize_row)
+  m.def("normalize_rows", [](py::array_t<float, py::array::c_style | py::array::forcecast> a) {
+    if (a.ndim() != 2) throw std::invalid_argument("normalize_rows needs a 2D array");
+    py::array_t<float> out({a.shape(0), a.shape(1)});
+    if (a.size()) std::memcpy(out.mutable_data(), a.data(), static_cast<size_t>(a.size()) * 4);
+    for (py::ssize_t i = 0; i < a.shape(0); ++i)
+      alaya_amd::normalize_row(out.mutable_data() + i * a.shape(1), static_cast<size_t>(a.shape(1)));
+    return out;
+  }, py::arg("array"));
   // the search kernel chosen for a request: ((space, chunks, mode), features this shape has kernels for)
   m.def("search_variant", [](uint32_t dim, bool ip, int sq8_order, bool generic, uint32_t wanted_mode) {
     int space = 0;

@@ -100,6 +100,14 @@ class Index:
         """The underlying PyIndexInterface (device counters, graph arrays, tuning)."""
         return self.__index
 
+    def exact_search(self, queries: VectorLikeBatch, topk: int):
+        """The exact top-k of each query over the rows the index holds (valid rows only, the index's
+        metric in f32, ties by id): the flat MFMA search on the device rows -- the ground truth for
+        the recall of ``batch_search`` at some ``ef_search``.  Returns (ids, distances); slots past the
+        valid rows hold (the id type's maximum, FLT_MAX).  1 <= topk <= 224, float32 data."""
+        self._check_queries(queries, 2, "queries")
+        return self.__index.exact_search(queries, topk)
+
     def save(self, url) -> dict:
         os.makedirs(url, exist_ok=True)
         p = self.__params

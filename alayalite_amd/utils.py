@@ -45,17 +45,27 @@ def calc_gt(data, query, topk):
     return gt
 
 
-def calc_gt_device(data, query, topk, device=0):
-    """Exact top-k L2 on the MI355X: the flat MFMA path (IndexType::FLAT has no implementation in the
+_GT_METRICS = {"l2": 0, "ip": 1, "cos": 2}
+
+
+def calc_gt_device(data, query, topk, device=0, metric="l2"):
+    """Exact top-k on the MI355X: the flat MFMA path (IndexType::FLAT has no implementation in the
     reference; this is its exact search, find_exact_gt in include/utils/evaluate.hpp:29-62: the f32
     l2_sqr metric, ties by id).  Any dimension, 1 <= topk <= 224.  Returns (ids int32, distances
-    float32).  Differs from calc_gt (float64 norms) only where two rows tie within f32 rounding."""
+    float32).  Differs from calc_gt (float64 norms) only where two rows tie within f32 rounding.
+    metric "ip" ranks by the f32 ip_sqr distance -(q.b); "cos" does the same on copies of both
+    arrays normalised row by row as ``fit`` normalises them."""
+    if metric not in _GT_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_GT_METRICS)}, got {metric!r}")
     from . import _native
 
     data = np.ascontiguousarray(data, dtype=np.float32)
     query = np.ascontiguousarray(query, dtype=np.float32)
+    if metric == "cos":
+        data = _native._ext.normalize_rows(data)
+        query = _native._ext.normalize_rows(query)
     ix = _native._ext.DeviceIndex(device)
-    ix.set_base(data, 0)
+    ix.set_base(data, _GT_METRICS[metric])
     ids, dists, _ = ix.flat_search(query, topk)
     return ids.astype(np.int32), dists
 

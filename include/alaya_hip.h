@@ -209,10 +209,11 @@ int alaya_index_batch_search_sq8_device(alaya_index *ix, const float *d_queries,
 int alaya_index_shard_search_sq8_device(alaya_index *ix, const float *d_queries, const float *d_rerank_queries,
                                         uint64_t nq, uint32_t k, uint32_t ef, int holds_row0, uint32_t *d_ids,
                                         float *d_dists, uint32_t *d_counters, void *stream);
-/* ---- flat (exhaustive) exact k-NN, L2, any dim, 1 <= k <= 224 -----------------------------------
+/* ---- flat (exhaustive) exact k-NN, L2 / IP / COS, any dim, 1 <= k <= 224 ------------------------
  * No reference implementation (IndexType::FLAT is enum-only, include/index/index_type.hpp:28); the
  * analogue is find_exact_gt (include/utils/evaluate.hpp:29-62).  An MFMA pass ranks every row
- * by |b|^2 - 2 q.b and keeps a shortlist -- q.b from a single-pass f16 contraction on power-of-two
+ * by |b|^2 - 2 q.b (L2) or by -2 q.b (IP, and COS: as for the graph search the caller has normalised
+ * the rows and the queries; ALAYA_DIST_GENERIC bases are refused) and keeps a shortlist -- q.b from a single-pass f16 contraction on power-of-two
  * scaled operands (rows of <= 224 floats) or a bf16 hi/lo split (3 bf16 MFMAs; wider rows), each
  * error bounded and folded into the proof below (alaya_index_flat_last_contraction; environment
  * ALAYA_FLAT_CONTRACTION selects one, ALAYA_FLAT_F32=1 the f32 MFMA form); rows wider than 224
@@ -221,8 +222,9 @@ int alaya_index_shard_search_sq8_device(alaya_index *ix, const float *d_queries,
  * 1M x 128), rebuilding them after any change to the rows, their count or the validity bitmap;
  * a prescan over a sample of them seeds every query's threshold.  The shortlist (32 per row chunk,
  * folded into a 128/256-entry list for k > 24) is rescored with the exact device metric
- * (l2_sqr_avx2 order) and sorted by (distance, id).  A query whose shortlist cannot be proven to
- * hold the exact top-k (error bound in flat_kernels.hip) is flagged; the host API recomputes it
+ * (l2_sqr_avx2 / ip_sqr_avx2 order; IP distances are -(q.b)) and sorted by (distance, id).  A query
+ * whose shortlist cannot be proven to hold the exact top-k (error bound in flat_kernels.hip for L2,
+ * flat_bound.h for inner products) is flagged; the host API recomputes it
  * exhaustively and reports how many it did.  The device variant is asynchronous on `stream` and
  * only writes d_flags[q] = 1 for such a query (its d_ids row is then not proven exact): the caller
  * recomputes it, e.g. through alaya_index_flat_search. */
@@ -268,6 +270,16 @@ int alaya_index_screen_stats(alaya_index *ix, uint64_t *screened, uint64_t *scre
  * out[i] <= the reference's f32 L2 distance of any q, x of `dim` elements for which d_tilde[i] is an
  * f32 sum in any order of (q_j - y_j)^2 over a copy y of x, and e_row[i] >= ||x - y||_2. */
 int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t n, uint32_t dim, float *out);
+/* The flat search's inner-product bound, evaluated on the host by the functions the merge kernels
+ * call (flat_bound.h).  alaya_flat_ip_slack: out[i] >= |d_ref + C~| for the reference's f32 distance
+ * d_ref = -(q.b) (ip_sqr_avx2) and the scan's contraction C~ (0 = f32 MFMA, 1 = bf16 hi/lo split, 2 =
+ * single-pass f16 with the query's scale exponent q_exp[i] -- NULL = 0 -- and the rows' base_exp) over
+ * k_acc columns, of any query with |q|^2 = q_norm2[i] and any row with |b| <= b_max; +inf = no bound.
+ * alaya_flat_ip_proven: out[i] = 1 when a k-th reference distance kth_d[i] is proven strictly below
+ * every row whose scan value -2 C~ is >= cutoff[i], given slack[i]. */
+int alaya_flat_ip_slack(int contraction, uint32_t k_acc, const float *q_norm2, const int *q_exp, uint64_t n,
+                        float b_max, int base_exp, float *out);
+int alaya_flat_ip_proven(const float *kth_d, const float *cutoff, const float *slack, uint64_t n, uint8_t *out);
 /* Which graph-search kernel a request gets, evaluated on the host from the list every launch is
  * planned from (csrc/search_variants.h).  A kernel variant is (space: 0 = f32 rows, 1 / 2 = SQ8 codes
  * in the AVX2 / AVX-512 order; chunks: dim / 32, 0 = the runtime-d kernel; mode: a set of feature bits
