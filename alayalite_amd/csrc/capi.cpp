@@ -136,13 +136,20 @@ struct alaya_index {
   int helpers_mode = -1;          // distance helpers: -1 automatic, 0 off, 1 on (alaya_index_set_helpers)
   DevBuf help_stats;              // per searcher of the last helper launch: (memo distances, memo expansions)
   uint64_t help_stats_slots = 0;
-  // candidate screen of the wide-row f32 L2 graph search: the rows as f16 and, per row, an upper
-  // bound on ||x - f16(x)|| (alaya_amd::launch_screen_rows).  Built at the first search that uses it,
+  // candidate screen of the wide-row f32 L2 graph search, one copy of the base per format
+  // (SearchParams::screen): [0] the rows as f16 and, per row, an upper bound on ||x - f16(x)||
+  // (alaya_amd::launch_screen_rows); [1] the 8-bit records, `err` unused
+  // (alaya_amd::launch_screen_rows_u8).  Each is built at the first search that uses its format,
   // kept current by row writes, freed with the base it describes.
-  DevBuf screen_rows, screen_err, screen_stats;
-  uint64_t screen_cap = 0;        // rows the two buffers hold
-  bool screen_ready = false;      // rows [0, n) are current
-  bool screen_failed = false;     // the buffers could not be allocated for this base: plain kernel
+  struct ScreenCopy {
+    DevBuf rows, err;
+    uint64_t cap = 0;     // rows the buffers hold
+    bool ready = false;   // rows [0, n) are current
+    bool failed = false;  // the buffers could not be allocated for this base: plain kernel
+  };
+  ScreenCopy screen_copy[2];
+  uint32_t screen_format = 0;     // SearchParams::screen of the launch being planned (ensure_screen)
+  DevBuf screen_stats;
   uint64_t screen_stats_slots = 0;  // searchers of the last launch, 0 = it did not screen
   uint32_t last_grid = 0, last_waves = 0;  // the last search launch's workgroups and waves per workgroup
   int visited_mode_override = 0;  // 0 auto, 1 compact 16-bit slots, 2 wide 32-bit slots,
@@ -511,7 +518,7 @@ SearchPlan plan_search(alaya_index *ix, SearchParams &p, alaya_amd::SearchReques
                      ": see the variant list in search_variants.h");
     p.help = (mode & kModeHelp) != 0;
     p.two_waves = (mode & kModeTwoWaves) != 0;
-    p.screen = (mode & kModeScreen) != 0;
+    p.screen = (mode & kModeScreen) != 0 ? ix->screen_format : 0u;
     plan.W = p.help ? 4 : search_waves(p);
     while (!p.help && plan.W > 1 && static_cast<uint64_t>(plan.W) > nq) plan.W /= 2;
     p.hash_log2 = size_visited(ix, p, *plan.variant, nq, ef, plan.W);
@@ -589,9 +596,11 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   p.stab_log2 = spill_table_log2(p.sq8_order, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2))), ef);
   if (const char *e = std::getenv("ALAYA_HELP_FLAGS")) p.help_flags = static_cast<uint32_t>(std::strtoul(e, nullptr, 10));
   const SearchPlan plan = plan_search(ix, p, search_request(ix, p, nq, ef, stream), nq, ef, stream);
-  if (p.screen) {
-    p.screen_rows = ix->screen_rows.as<uint16_t>();
-    p.screen_err = ix->screen_err.as<float>();
+  if (p.screen == 2) {
+    p.screen_u8 = ix->screen_copy[1].rows.as<uint8_t>();
+  } else if (p.screen) {
+    p.screen_rows = ix->screen_copy[0].rows.as<uint16_t>();
+    p.screen_err = ix->screen_copy[0].err.as<float>();
   }
   scratch_acquire(ix, stream);
   const uint64_t searchers = static_cast<uint64_t>(plan.grid) * plan.W;
@@ -619,50 +628,79 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
 // MI355X against the plain kernel (GIST-shaped 1k queries, d = 512 +7 %,
 // 768 +12 %, 960 +29 %, 1024 +27 %; the two-waves-per-SIMD batches +18 % / +41 %) -- every width
 // that has a screening kernel.
-bool screen_default(uint32_t dim) { return dim == 512 || dim == 768 || dim == 960 || dim == 1024; }
+// The format (SearchParams::screen: 1 = f16, 2 = 8-bit records) is the one that measured faster for
+// the width ("Round 8": 8-bit records against the f16 copy d = 768 +16 %,
+// 960 +11 %, 1024 +16 %, the two-waves-per-SIMD batches +4 % / +7 %; d = 512 equal, so it keeps f16).
+uint32_t screen_default(uint32_t dim) {
+  if (dim == 768 || dim == 960 || dim == 1024) return 2u;
+  return dim == 512 ? 1u : 0u;
+}
 
-// Whether this launch screens: the shape has a screening kernel, ALAYA_SEARCH_SCREEN (0 / 1, read per
-// launch; unset = screen_default) allows it, and the f16 copy exists or can be built now, on the
-// search's stream.  An allocation failure is not an error: the search runs the plain kernel.
+// Rows [first, first + count) of the base into the screening copy of `format`.
+void screen_fill(alaya_index *ix, uint32_t format, uint64_t first, uint64_t count, hipStream_t stream) {
+  alaya_index::ScreenCopy &c = ix->screen_copy[format - 1];
+  hip_check(format == 2 ? alaya_amd::launch_screen_rows_u8(ix->base.as<float>(), first, count, ix->stride,
+                                                           c.rows.as<uint8_t>(), stream)
+                        : alaya_amd::launch_screen_rows(ix->base.as<float>(), first, count, ix->stride,
+                                                        c.rows.as<uint16_t>(), c.err.as<float>(), stream),
+            "screening copy");
+}
+
+// Whether this launch screens, and on which copy: the shape has a screening kernel,
+// ALAYA_SEARCH_SCREEN (0 = off, 8 = the 8-bit records, anything else = f16; read per launch; unset =
+// screen_default) names a format, and that format's copy exists or can be built now, on the search's
+// stream.  Sets ix->screen_format.  An allocation failure is not an error: the search runs the plain
+// kernel.
 bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStream_t stream) {
+  ix->screen_format = 0;
   if (!eligible || !alaya_amd::search_has_screen(ix->dim, p.sq8_order, ix->generic, p.ip)) return false;
   const char *e = std::getenv("ALAYA_SEARCH_SCREEN");
-  if (!(e && e[0] ? std::atoi(e) != 0 : screen_default(ix->dim))) return false;
-  if (ix->screen_ready) return true;
-  if (ix->screen_failed) return false;
-  const uint64_t rows = std::max<uint64_t>(std::max(ix->capacity, ix->n), 1);
-  try {
-    if (rows > ix->screen_cap) {
-      ix->screen_rows.release();
-      ix->screen_err.release();
-      ix->screen_cap = 0;
-      ix->screen_rows.reserve(rows * ix->stride * 2);
-      ix->screen_err.reserve(rows * 4);
-      ix->screen_cap = rows;
+  const int asked = e && e[0] ? std::atoi(e) : -1;
+  const uint32_t format = asked < 0 ? screen_default(ix->dim) : (asked == 0 ? 0u : (asked == 8 ? 2u : 1u));
+  if (format == 0) return false;
+  alaya_index::ScreenCopy &c = ix->screen_copy[format - 1];
+  if (c.failed) return false;
+  if (!c.ready) {
+    const uint64_t rows = std::max<uint64_t>(std::max(ix->capacity, ix->n), 1);
+    try {
+      if (rows > c.cap) {
+        c.rows.release();
+        c.err.release();
+        c.cap = 0;
+        if (format == 2) {
+          c.rows.reserve(rows * alaya_amd::screen_u8_record_bytes(ix->stride));
+        } else {
+          c.rows.reserve(rows * ix->stride * 2);
+          c.err.reserve(rows * 4);
+        }
+        c.cap = rows;
+      }
+    } catch (const DeviceError &) {
+      (void)hipGetLastError();
+      c.rows.release();
+      c.err.release();
+      c.cap = 0;
+      c.failed = true;
+      return false;
     }
-  } catch (const DeviceError &) {
-    (void)hipGetLastError();
-    ix->screen_rows.release();
-    ix->screen_err.release();
-    ix->screen_cap = 0;
-    ix->screen_failed = true;
-    return false;
+    scratch_acquire(ix, stream);  // after every earlier launch that may still read the buffers
+    screen_fill(ix, format, 0, ix->n, stream);
+    c.ready = true;
   }
-  scratch_acquire(ix, stream);  // after every earlier launch that may still read the buffers
-  hip_check(alaya_amd::launch_screen_rows(ix->base.as<float>(), 0, ix->n, ix->stride, ix->screen_rows.as<uint16_t>(),
-                                          ix->screen_err.as<float>(), stream),
-            "screening copy");
-  ix->screen_ready = true;
+  ix->screen_format = format;
   return true;
 }
 
-// The base is gone or replaced: nothing keeps its screening copy alive.
+// The base is gone or replaced: nothing keeps its screening copies alive.
 void screen_drop(alaya_index *ix) {
-  ix->screen_rows.release();
-  ix->screen_err.release();
-  ix->screen_cap = 0;
-  ix->screen_ready = false;
-  ix->screen_failed = false;
+  for (alaya_index::ScreenCopy &c : ix->screen_copy) {
+    c.rows.release();
+    c.err.release();
+    c.cap = 0;
+    c.ready = false;
+    c.failed = false;
+  }
+  ix->screen_format = 0;
   ix->screen_stats_slots = 0;
 }
 
@@ -1239,15 +1277,15 @@ void write_rows_locked(alaya_index *ix, uint64_t first, const float *rows, uint6
   ix->n = std::max(ix->n, first + count);
   ix->norms_ready = false;
   ix->tiles_ready = false;
-  // the screening copy follows the written rows; rows past what it holds mark it for a rebuild
-  if (ix->screen_ready) {
-    if (first + count <= ix->screen_cap) {
-      hip_check(alaya_amd::launch_screen_rows(ix->base.as<float>(), first, count, ix->stride,
-                                              ix->screen_rows.as<uint16_t>(), ix->screen_err.as<float>(), ix->stream),
-                "screening copy");
+  // the screening copies follow the written rows; rows past what one holds mark it for a rebuild
+  for (uint32_t format = 1; format <= 2; ++format) {
+    alaya_index::ScreenCopy &c = ix->screen_copy[format - 1];
+    if (!c.ready) continue;
+    if (first + count <= c.cap) {
+      screen_fill(ix, format, first, count, ix->stream);
       hip_check(hipStreamSynchronize(ix->stream), "sync");
     } else {
-      ix->screen_ready = false;
+      c.ready = false;
     }
   }
 }
@@ -2180,6 +2218,42 @@ int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t 
   return guarded([&] {
     if (n && (!d_tilde || !e_row || !out)) throw ArgError("invalid arguments");
     for (uint64_t i = 0; i < n; ++i) out[i] = alaya_amd::screen_lower_bound(d_tilde[i], e_row[i], dim);
+  });
+}
+
+int alaya_screen_u8_quantize(const float *rows, uint64_t n, uint32_t dim, uint8_t *codes, float *header,
+                             float *values) {
+  return guarded([&] {
+    using namespace alaya_amd;
+    if (n && dim && (!rows || !codes || !header || !values)) throw ArgError("invalid arguments");
+    for (uint64_t r = 0; r < n; ++r) {
+      const float *x = rows + r * dim;
+      float lo = FLT_MAX, hi = -FLT_MAX;
+      bool bad = false;
+      for (uint32_t j = 0; j < dim; ++j) {
+        bad = bad || !screen_finite(x[j]);
+        lo = fminf(lo, x[j]);
+        hi = fmaxf(hi, x[j]);
+      }
+      float scale = screen_u8_scale(lo, hi);
+      if (bad || !screen_finite(scale)) {
+        bad = true;
+        lo = scale = 0.f;
+      }
+      float sum = 0.f;
+      for (uint32_t j = 0; j < dim; ++j) {
+        const uint32_t c = screen_u8_code(x[j], lo, scale);
+        const float y = screen_u8_value(c, lo, scale);
+        const float d = x[j] - y;
+        if (!bad) sum = fmaf(d, d, sum);
+        codes[r * dim + j] = static_cast<uint8_t>(c);
+        values[r * dim + j] = y;
+      }
+      header[4 * r] = screen_u8_err(sum, dim, bad);
+      header[4 * r + 1] = lo;
+      header[4 * r + 2] = scale;
+      header[4 * r + 3] = 0.f;
+    }
   });
 }
 

@@ -1070,6 +1070,16 @@ PYBIND11_MODULE(_alayalitepy, m) {
                                    out.mutable_data()));
     return out;
   });
+  // the 8-bit screening copy on the host: (codes, header (e_row, lo, scale, 0), values the codes stand for)
+  m.def("screen_u8_quantize", [](py::array_t<float, py::array::c_style | py::array::forcecast> rows) {
+    if (rows.ndim() != 2) throw std::invalid_argument("rows must be 2-D");
+    py::array_t<uint8_t> codes({rows.shape(0), rows.shape(1)});
+    py::array_t<float> header({rows.shape(0), static_cast<py::ssize_t>(4)});
+    py::array_t<float> values({rows.shape(0), rows.shape(1)});
+    check(alaya_screen_u8_quantize(rows.data(), static_cast<uint64_t>(rows.shape(0)), static_cast<uint32_t>(rows.shape(1)),
+                                   codes.mutable_data(), header.mutable_data(), values.mutable_data()));
+    return py::make_tuple(codes, header, values);
+  });
   // the flat search's inner-product bound on the host (flat_bound.h): slack per query, and the test
   m.def("flat_ip_slack", [](int contraction, uint32_t k_acc,
                             py::array_t<float, py::array::c_style | py::array::forcecast> q_norm2,

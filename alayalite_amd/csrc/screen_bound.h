@@ -44,4 +44,37 @@ ALAYA_HD inline float screen_lower_bound(float d_tilde, float e_row, uint32_t di
   return r >= kScreenTiny ? r : 0.f;
 }
 
+// ---- The 8-bit screening copy ("Round 8") -----------------------------------
+// One record per row: a 16-byte header {e_row, lo, scale, 0} and then `stride` codes, padded to a
+// multiple of 64 bytes, so a candidate's e_row and its codes come from one place.
+constexpr uint32_t kScreenU8Header = 16;
+ALAYA_HD inline uint32_t screen_u8_record_bytes(uint32_t stride) { return (kScreenU8Header + stride + 63u) & ~63u; }
+
+// The f32 value y_j that code c stands for.  The copy kernel (for e_row), the search kernel (for d~)
+// and the host test all call this one function, and fmaf is one rounding whatever the compiler
+// contracts elsewhere, so y_j is the same f32 everywhere.
+ALAYA_HD inline float screen_u8_value(uint32_t c, float lo, float scale) {
+  return fmaf(static_cast<float>(c), scale, lo);
+}
+
+// The quantiser: lo = the row's min, scale = (max - min) / 255, c = clamp(rint((x - lo) / scale)); a
+// constant row has scale 0 and codes 0.  Its quality decides how many candidates the screen drops,
+// never whether a drop is right: e_row is measured against the values the codes stand for.
+ALAYA_HD inline float screen_u8_scale(float lo, float hi) { return (hi - lo) / 255.0f; }
+ALAYA_HD inline uint32_t screen_u8_code(float x, float lo, float scale) {
+  if (!(scale > 0.f)) return 0u;
+  const float c = rintf((x - lo) / scale);
+  return c >= 255.f ? 255u : (c >= 0.f ? static_cast<uint32_t>(c) : 0u);  // NaN -> 0
+}
+
+// e_row from `sum`, an f32 sum in any order of fl(fl(x_j - y_j)^2) over the row's `stride` elements:
+// an over-estimate of ||x - y||_2 by the same slacks as the f16 copy's (1 + screen_gamma on the
+// sum, 1 + 2^-19 on its root, 2^-50 for the root of the squares that underflow).  `bad` = an element,
+// lo or scale is not finite: +inf, the row is never screened out.
+ALAYA_HD inline float screen_u8_err(float sum, uint32_t stride, bool bad) {
+  const float err = sqrtf(sum * (1.0f + screen_gamma(stride))) * (1.0f + 1.9073486328125e-6f) + 8.8817841970012523e-16f;
+  return (bad || !(err <= kScreenHuge)) ? INFINITY : err;
+}
+ALAYA_HD inline bool screen_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }
+
 }  // namespace alaya_amd

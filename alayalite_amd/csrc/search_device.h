@@ -8,6 +8,7 @@
 #include <cfloat>
 #include <cstdint>
 
+#include "screen_bound.h"
 #include "search_kernels.h"
 
 namespace alaya_amd {
@@ -386,6 +387,105 @@ __device__ __forceinline__ void screen_distances(const SearchParams &p, const fl
       for (int r = 0; r < kRows; ++r) {
         if (r >= live) break;
         screen_accumulate(qa, qb, P.y[r][t], a[r][0], a[r][1]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      if (r >= live) break;
+      float s = a[r][0] + a[r][1];
+      s += lane_xor<1>(s);
+      s += lane_xor<2>(s);
+      s += lane_xor<4>(s);
+      const int idx = base + g + 8 * r;
+      if (idx < n && m == 0) out[idx] = s;
+    }
+  }
+  wave_sync();
+}
+
+// --------------------------------------------------------------------------------------------
+// The screen pass on the 8-bit records (SearchParams::screen == 2, screen_bound.h): the same d~ over
+// y_j = screen_u8_value(code_j, lo, scale).  A 128 B chunk holds 128 codes, 16 per lane -- lane m
+// takes elements 128 t + 16 m .. + 15 -- so a row is kChunks / 4 loads of 16 B per lane, half the
+// registers of the f16 pass; where kChunks is no multiple of 4 (d = 960: 7.5 chunks) only the first
+// kTailLanes lanes of a group load and sum the last chunk, so no lane reads past the record or the
+// query.  The row's (lo, scale) come with its header, one 16 B load per lane group and row.
+// --------------------------------------------------------------------------------------------
+template <int kChunks, int kRows>
+struct ScreenPassU8 {
+  static constexpr int kT = (kChunks + 3) / 4;
+  static constexpr int kTailLanes = (kChunks % 4) * 2;  // lanes of the last chunk that hold codes; 0 = all
+  uint4 y[kRows][kT];
+  float4 head[kRows];
+};
+
+__device__ __forceinline__ void screen_u8_word(float4 q, uint32_t w, float lo, float scale, float &a0, float &a1) {
+  const float d0 = q.x - screen_u8_value(w & 0xffu, lo, scale);
+  const float d1 = q.y - screen_u8_value((w >> 8) & 0xffu, lo, scale);
+  const float d2 = q.z - screen_u8_value((w >> 16) & 0xffu, lo, scale);
+  const float d3 = q.w - screen_u8_value(w >> 24, lo, scale);
+  a0 = fmaf(d0, d0, a0); a1 = fmaf(d1, d1, a1);
+  a0 = fmaf(d2, d2, a0); a1 = fmaf(d3, d3, a1);
+}
+
+template <int kChunks, int kRows, typename Hook>
+__device__ __forceinline__ void screen_distances_u8(const SearchParams &p, const float *q, const uint32_t *ids,
+                                                    int n, float *out, Hook after_issue) {
+  using SP = ScreenPassU8<kChunks, kRows>;
+  const int lane = lane_id();
+  const int g = lane >> 3, m = lane & 7;
+  const uint32_t rec = screen_u8_record_bytes(p.stride);
+  const bool tail_lane = SP::kTailLanes == 0 || m < SP::kTailLanes;
+  for (int base = 0; base < n; base += 8 * kRows) {
+    SP P;
+    const uint32_t id0 = ids[base];
+    const uint4 *hp[kRows];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      const int idx = base + g + 8 * r;
+      const uint32_t id = idx < n ? ids[idx] : id0;  // a group past n reloads the pass's first row
+      hp[r] = reinterpret_cast<const uint4 *>(p.screen_u8 + static_cast<uint64_t>(id) * rec);
+      P.head[r] = *reinterpret_cast<const float4 *>(hp[r]);
+    }
+    // Chunk-major, the order the sums below consume them in: loads retire in issue order, so chunk
+    // t's arithmetic runs while the later chunks are still on their way.  Branch-free: a row slot
+    // past n loads the first row's record again (a cache hit whose result is dropped).
+#pragma unroll
+    for (int t = 0; t < SP::kT; ++t) {
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) {
+        const uint4 *rp = hp[r] + 1 + m + 8 * t;
+        if (t + 1 < SP::kT || SP::kTailLanes == 0) {
+          P.y[r][t] = *rp;
+        } else {
+          P.y[r][t] = make_uint4(0u, 0u, 0u, 0u);
+          if (tail_lane) P.y[r][t] = *rp;
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);  // (the scheduler would otherwise issue them row by row)
+    }
+    if (base == 0) after_issue();
+    int live = 0;  // wave-uniform number of row slots in use
+    float a[kRows][2];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      a[r][0] = a[r][1] = 0.f;
+      live += base + 8 * r < n ? 1 : 0;
+    }
+    const float4 *qp = reinterpret_cast<const float4 *>(q) + 4 * m;
+#pragma unroll
+    for (int t = 0; t < SP::kT; ++t) {
+      if (t + 1 < SP::kT || tail_lane) {
+        const float4 q0 = qp[32 * t], q1 = qp[32 * t + 1], q2 = qp[32 * t + 2], q3 = qp[32 * t + 3];
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+          if (r >= live) break;
+          const float lo = P.head[r].y, scale = P.head[r].z;
+          screen_u8_word(q0, P.y[r][t].x, lo, scale, a[r][0], a[r][1]);
+          screen_u8_word(q1, P.y[r][t].y, lo, scale, a[r][0], a[r][1]);
+          screen_u8_word(q2, P.y[r][t].z, lo, scale, a[r][0], a[r][1]);
+          screen_u8_word(q3, P.y[r][t].w, lo, scale, a[r][0], a[r][1]);
+        }
       }
     }
 #pragma unroll

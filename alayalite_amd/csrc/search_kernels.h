@@ -85,11 +85,13 @@ struct SearchParams {
   uint32_t *help_stats;   // nullable: per searcher, (fresh distances it took from a memo, expansions
                           // with every fresh distance from the memo, rows it computed as a helper)
   // Candidate screen (search_has_screen; kModeScreen): once the pool is full, an expansion's fresh
-  // candidates are first measured on an f16 copy of their rows, and only those whose proven lower
-  // bound (screen_bound.h) is below the pool's worst distance read their f32 row.
-  uint32_t screen;             // 1 = the screening kernel
-  const uint16_t *screen_rows; // n rows of `stride` f16 values (stride * 2 bytes, a multiple of 64)
-  const float *screen_err;     // per row, >= ||x - f16(x)||_2; +inf = never screened out
+  // candidates are first measured on a low-precision copy of their rows, and only those whose proven
+  // lower bound (screen_bound.h) is below the pool's worst distance read their f32 row.
+  uint32_t screen;             // the screening kernel's copy: 0 = none, 1 = f16, 2 = 8-bit records
+  const uint16_t *screen_rows; // f16: n rows of `stride` f16 values (stride * 2 bytes, a multiple of 64)
+  const float *screen_err;     // f16: per row, >= ||x - f16(x)||_2; +inf = never screened out
+  const uint8_t *screen_u8;    // 8-bit: n records of screen_u8_record_bytes(stride) bytes (screen_bound.h):
+                               // {e_row, lo, scale, 0} and `stride` codes
   uint32_t *screen_stats;      // per searcher: (candidates screened, candidates screened out)
 };
 
@@ -142,6 +144,12 @@ hipError_t search_occupancy(const SearchVariant &v, bool ip, int waves, size_t l
 // finite in f16.
 hipError_t launch_screen_rows(const float *base, uint64_t first, uint64_t count, uint32_t stride,
                               uint16_t *out_rows, float *out_err, hipStream_t stream);
+// The 8-bit screening copy of rows [first, first + count): record r of out_recs (screen_bound.h:
+// screen_u8_record_bytes(stride) bytes each) = {e_row, lo, scale, 0} and the row's codes, with
+// e_row >= ||base[r] - y||_2 for y_j = screen_u8_value(code_j, lo, scale); +inf for a row that is not
+// finite.
+hipError_t launch_screen_rows_u8(const float *base, uint64_t first, uint64_t count, uint32_t stride,
+                                 uint8_t *out_recs, hipStream_t stream);
 // launches variant `v`'s kernel: the one resolve_search_variant chose and p.help / p.two_waves /
 // p.screen / the LDS layout were planned for
 hipError_t launch_search(const SearchVariant &v, const SearchParams &p, int grid, int waves, size_t lds,

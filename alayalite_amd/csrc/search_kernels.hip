@@ -597,6 +597,8 @@ __global__ void __launch_bounds__(256)
   constexpr bool kScreen = (kMode & kModeScreen) != 0;
   static_assert(!kScreen || (kSpace == 0 && !kIP && !kHelp && kChunks >= 16 && kChunks % 2 == 0), "screen: wide f32 L2 rows");
   constexpr int kScreenRows = (kMode & kModeTwoWaves) != 0 ? 2 : 4;
+  // the 8-bit records (p.screen == 2) hold a row in half the registers: 4 rows in both kernels
+  constexpr int kScreenRowsU8 = 4;
   uint32_t n_screened = 0, n_screened_out = 0;  // wave-uniform, over the searcher's queries
   const int lane = lane_id();
   const int wave = static_cast<int>(threadIdx.x >> 6);
@@ -805,7 +807,8 @@ __global__ void __launch_bounds__(256)
       // Screen (kMode 16).  With the pool full, tau = its worst distance now is >= its worst distance
       // at every later point of the sequential LinearPool::insert order, so a candidate whose exact
       // distance is >= tau is rejected by the reference ("full and d >= last") and changes nothing:
-      // not the pool, not cur, not on_next.  One pass over the f16 copies of all nf rows gives d~;
+      // not the pool, not cur, not on_next.  One pass over the copies (f16 rows or 8-bit records,
+      // p.screen) of all nf rows gives d~;
       // a candidate whose proven lower bound on the exact f32 distance (screen_bound.h) reaches tau
       // is dropped from the list here -- it stays visited and stays counted in n_dist, as in the
       // reference -- and only the others, still in adjacency order, read their f32 rows below, so
@@ -817,8 +820,13 @@ __global__ void __launch_bounds__(256)
           const bool in = lane < nf;
           const uint32_t c = in ? L.cid[lane] : 0u;
           float e_row = 0.f;
-          if (in) e_row = p.screen_err[c];
-          screen_distances<kChunks, kScreenRows>(p, L.q, L.cid, nf, L.cd, second_level_prefetch);
+          if (p.screen == 2) {  // wave-uniform: the 8-bit records, e_row in the header of each
+            if (in) e_row = *reinterpret_cast<const float *>(p.screen_u8 + static_cast<uint64_t>(c) * screen_u8_record_bytes(p.stride));
+            screen_distances_u8<kChunks, kScreenRowsU8>(p, L.q, L.cid, nf, L.cd, second_level_prefetch);
+          } else {
+            if (in) e_row = p.screen_err[c];
+            screen_distances<kChunks, kScreenRows>(p, L.q, L.cid, nf, L.cd, second_level_prefetch);
+          }
           bool keep = false;
           if (in) {
             const float lb = screen_lower_bound(L.cd[lane], e_row, p.dim);
@@ -942,6 +950,62 @@ __global__ void __launch_bounds__(256) screen_rows_kernel(const float *base, uin
       if (any_bad || !(err <= kScreenHuge)) err = __builtin_inff();
       out_err[first + r] = err;
     }
+  }
+}
+
+// The 8-bit screening copy (launch_screen_rows_u8; record layout, quantiser and e_row in
+// screen_bound.h): one wave per row, lane l takes elements 4 l + 256 k.  First the row's min and max,
+// then its codes and the f32 sum of (x_j - y_j)^2 over the values the codes stand for.
+__global__ void __launch_bounds__(256) screen_rows_u8_kernel(const float *base, uint64_t first, uint64_t count,
+                                                             uint32_t stride, uint8_t *out_recs) {
+  const int lane = lane_id();
+  const uint32_t rec = screen_u8_record_bytes(stride);
+  const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (blockDim.x >> 6);
+  for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6); r < count; r += waves) {
+    const float *row = base + (first + r) * stride;
+    uint8_t *dst = out_recs + (first + r) * rec;
+    float lo = FLT_MAX, hi = -FLT_MAX;
+    bool bad = false;
+    for (uint32_t e = 4 * lane; e < stride; e += 256) {  // stride is a multiple of 32
+      const float4 x = *reinterpret_cast<const float4 *>(row + e);
+      bad = bad || !screen_finite(x.x) || !screen_finite(x.y) || !screen_finite(x.z) || !screen_finite(x.w);
+      lo = fminf(fminf(lo, x.x), fminf(fminf(x.y, x.z), x.w));
+      hi = fmaxf(fmaxf(hi, x.x), fmaxf(fmaxf(x.y, x.z), x.w));
+    }
+    lo = fminf(lo, lane_xor<1>(lo)); hi = fmaxf(hi, lane_xor<1>(hi));
+    lo = fminf(lo, lane_xor<2>(lo)); hi = fmaxf(hi, lane_xor<2>(hi));
+    lo = fminf(lo, lane_xor<4>(lo)); hi = fmaxf(hi, lane_xor<4>(hi));
+    lo = fminf(lo, lane_xor<8>(lo)); hi = fmaxf(hi, lane_xor<8>(hi));
+    lo = fminf(lo, lane_xor<16>(lo)); hi = fmaxf(hi, lane_xor<16>(hi));
+    lo = fminf(read_lane(lo, 0), read_lane(lo, 32));
+    hi = fmaxf(read_lane(hi, 0), read_lane(hi, 32));
+    float scale = screen_u8_scale(lo, hi);
+    if (ballot(bad) != 0ull || !screen_finite(scale)) {  // (hi - lo can overflow); codes 0 stand for 0
+      bad = true;
+      lo = scale = 0.f;
+    }
+    float sum = 0.f;
+    for (uint32_t e = 4 * lane; e < stride; e += 256) {
+      const float4 x = *reinterpret_cast<const float4 *>(row + e);
+      const uint32_t c0 = screen_u8_code(x.x, lo, scale), c1 = screen_u8_code(x.y, lo, scale);
+      const uint32_t c2 = screen_u8_code(x.z, lo, scale), c3 = screen_u8_code(x.w, lo, scale);
+      const float d0 = x.x - screen_u8_value(c0, lo, scale), d1 = x.y - screen_u8_value(c1, lo, scale);
+      const float d2 = x.z - screen_u8_value(c2, lo, scale), d3 = x.w - screen_u8_value(c3, lo, scale);
+      if (!bad) {
+        sum = fmaf(d0, d0, sum);
+        sum = fmaf(d1, d1, sum);
+        sum = fmaf(d2, d2, sum);
+        sum = fmaf(d3, d3, sum);
+      }
+      *reinterpret_cast<uint32_t *>(dst + kScreenU8Header + e) = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+    }
+    sum += lane_xor<1>(sum);
+    sum += lane_xor<2>(sum);
+    sum += lane_xor<4>(sum);
+    sum += lane_xor<8>(sum);
+    sum += lane_xor<16>(sum);
+    sum = read_lane(sum, 0) + read_lane(sum, 32);
+    if (lane == 0) *reinterpret_cast<float4 *>(dst) = make_float4(screen_u8_err(sum, stride, bad), lo, scale, 0.f);
   }
 }
 
@@ -1130,6 +1194,14 @@ hipError_t launch_screen_rows(const float *base, uint64_t first, uint64_t count,
   const int grid = static_cast<int>(std::min<uint64_t>((count + 3) / 4, 16384));
   hipLaunchKernelGGL(screen_rows_kernel, dim3(grid), dim3(256), 0, stream, base, first, count, stride, out_rows,
                      out_err);
+  return hipGetLastError();
+}
+
+hipError_t launch_screen_rows_u8(const float *base, uint64_t first, uint64_t count, uint32_t stride,
+                                 uint8_t *out_recs, hipStream_t stream) {
+  if (count == 0) return hipSuccess;
+  const int grid = static_cast<int>(std::min<uint64_t>((count + 3) / 4, 16384));
+  hipLaunchKernelGGL(screen_rows_u8_kernel, dim3(grid), dim3(256), 0, stream, base, first, count, stride, out_recs);
   return hipGetLastError();
 }
 

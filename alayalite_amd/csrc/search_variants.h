@@ -17,7 +17,8 @@ namespace alaya_amd {
 // kModeHelp: distance helpers (SearchParams::help): a wave with no query left computes the distances
 // of a sibling's next expansion into a memo the sibling reads (help_siblings);
 // kModeTwoWaves: two waves per SIMD for wide f32 rows (one row per lane group, SearchParams::two_waves);
-// kModeScreen: the candidate screen on an f16 row copy (SearchParams::screen; wide f32 L2 rows).
+// kModeScreen: the candidate screen on a low-precision row copy (wide f32 L2 rows); which copy --
+// f16 rows or 8-bit records -- is SearchParams::screen at run time, not a variant.
 constexpr int kModeStamp = 1;
 constexpr int kModeCheck = 2;
 constexpr int kModeHelp = 4;

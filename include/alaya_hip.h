@@ -257,12 +257,15 @@ int alaya_index_set_visited_mode(alaya_index *ix, int mode);
 int alaya_index_set_helpers(alaya_index *ix, int mode);
 int alaya_index_help_stats(alaya_index *ix, uint64_t *memo_dists, uint64_t *memo_expansions,
                            uint64_t *helper_rows);
-/* Candidate screen of the wide-row f32 L2 graph search (d = 512 / 768 / 960 / 1024; environment
- * ALAYA_SEARCH_SCREEN = 0 / 1 forces it off / on per launch): once a query's pool is full, the fresh
- * candidates of an expansion are first measured on an f16 copy of their rows (built at the first
- * search that uses it: n x stride x 2 bytes + 4 bytes per row, freed with the base), and only those
- * whose proven lower bound on the exact distance is below the pool's worst distance read their f32
- * row.  Results and counters never depend on it.  alaya_index_screen_stats: of the last graph search,
+/* Candidate screen of the wide-row f32 L2 graph search (d = 512 / 768 / 960 / 1024): once a query's
+ * pool is full, the fresh candidates of an expansion are first measured on a low-precision copy of
+ * their rows, and only those whose proven lower bound on the exact distance is below the pool's worst
+ * distance read their f32 row.  Two copies exist, each built at the first search that uses it and
+ * freed with the base: the rows as f16 (n x stride x 2 bytes + 4 bytes per row), and 8-bit records
+ * (per row a 16-byte header {e_row, lo, scale, 0} and stride codes for lo + code x scale, padded to
+ * a multiple of 64 bytes: 1024 bytes at d = 960).  Environment ALAYA_SEARCH_SCREEN, read per launch:
+ * 0 = no screen, 1 = the f16 copy, 8 = the 8-bit records, unset = the default of the width.
+ * Results and counters never depend on it.  alaya_index_screen_stats: of the last graph search,
  * how many candidates were screened and how many of those were screened out (waits for that search;
  * 0, 0 when it did not screen). */
 int alaya_index_screen_stats(alaya_index *ix, uint64_t *screened, uint64_t *screened_out);
@@ -270,6 +273,11 @@ int alaya_index_screen_stats(alaya_index *ix, uint64_t *screened, uint64_t *scre
  * out[i] <= the reference's f32 L2 distance of any q, x of `dim` elements for which d_tilde[i] is an
  * f32 sum in any order of (q_j - y_j)^2 over a copy y of x, and e_row[i] >= ||x - y||_2. */
 int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t n, uint32_t dim, float *out);
+/* The 8-bit screening copy of n rows of dim elements, made on the host by the functions the device
+ * uses (screen_bound.h): codes (n x dim), header (n x 4: e_row, lo, scale, 0) and values (n x dim: the
+ * f32 value each code stands for).  e_row >= ||row - values||_2, +inf for a row that is not finite. */
+int alaya_screen_u8_quantize(const float *rows, uint64_t n, uint32_t dim, uint8_t *codes, float *header,
+                             float *values);
 /* The flat search's inner-product bound, evaluated on the host by the functions the merge kernels
  * call (flat_bound.h).  alaya_flat_ip_slack: out[i] >= |d_ref + C~| for the reference's f32 distance
  * d_ref = -(q.b) (ip_sqr_avx2) and the scan's contraction C~ (0 = f32 MFMA, 1 = bf16 hi/lo split, 2 =
