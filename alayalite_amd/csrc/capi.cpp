@@ -596,7 +596,7 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   p.stab_log2 = spill_table_log2(p.sq8_order, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2))), ef);
   if (const char *e = std::getenv("ALAYA_HELP_FLAGS")) p.help_flags = static_cast<uint32_t>(std::strtoul(e, nullptr, 10));
   const SearchPlan plan = plan_search(ix, p, search_request(ix, p, nq, ef, stream), nq, ef, stream);
-  if (p.screen == 2) {
+  if (p.screen >= 2) {  // 2 and 3 read the same records
     p.screen_u8 = ix->screen_copy[1].rows.as<uint8_t>();
   } else if (p.screen) {
     p.screen_rows = ix->screen_copy[0].rows.as<uint16_t>();
@@ -628,12 +628,14 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
 // MI355X against the plain kernel (GIST-shaped 1k queries, d = 512 +7 %,
 // 768 +12 %, 960 +29 %, 1024 +27 %; the two-waves-per-SIMD batches +18 % / +41 %) -- every width
 // that has a screening kernel.
-// The format (SearchParams::screen: 1 = f16, 2 = 8-bit records) is the one that measured faster for
-// the width ("Round 8": 8-bit records against the f16 copy d = 768 +16 %,
-// 960 +11 %, 1024 +16 %, the two-waves-per-SIMD batches +4 % / +7 %; d = 512 equal, so it keeps f16).
+// The format (SearchParams::screen: 1 = f16, 2 = 8-bit records in f32 arithmetic, 3 = the same records
+// under integer dot products) is the one that measured fastest for the width.  Round 8: the records
+// against the f16 copy d = 768 +16 %, 960 +11 %, 1024 +16 %, d = 512 equal.  Round 10 (DESIGN.md
+// section 3, profiles/r10/shapes_ab.jsonl): the integer pass against the width's previous default
+// d = 512 +13 %, 768 +8 %, 960 +18 %, 1024 +16 %, the two-waves-per-SIMD batches +15 % / +22 % -- every
+// screened width.  ALAYA_SEARCH_SCREEN = 8 / 1 still ask for the other two.
 uint32_t screen_default(uint32_t dim) {
-  if (dim == 768 || dim == 960 || dim == 1024) return 2u;
-  return dim == 512 ? 1u : 0u;
+  return (dim == 512 || dim == 768 || dim == 960 || dim == 1024) ? 3u : 0u;
 }
 
 // Rows [first, first + count) of the base into the screening copy of `format`.
@@ -647,7 +649,8 @@ void screen_fill(alaya_index *ix, uint32_t format, uint64_t first, uint64_t coun
 }
 
 // Whether this launch screens, and on which copy: the shape has a screening kernel,
-// ALAYA_SEARCH_SCREEN (0 = off, 8 = the 8-bit records, anything else = f16; read per launch; unset =
+// ALAYA_SEARCH_SCREEN (0 = off, 8 = the 8-bit records in f32 arithmetic, 9 = the same records under
+// integer dot products with the query's own codes, anything else = f16; read per launch; unset =
 // screen_default) names a format, and that format's copy exists or can be built now, on the search's
 // stream.  Sets ix->screen_format.  An allocation failure is not an error: the search runs the plain
 // kernel.
@@ -656,9 +659,11 @@ bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStr
   if (!eligible || !alaya_amd::search_has_screen(ix->dim, p.sq8_order, ix->generic, p.ip)) return false;
   const char *e = std::getenv("ALAYA_SEARCH_SCREEN");
   const int asked = e && e[0] ? std::atoi(e) : -1;
-  const uint32_t format = asked < 0 ? screen_default(ix->dim) : (asked == 0 ? 0u : (asked == 8 ? 2u : 1u));
+  const uint32_t format =
+      asked < 0 ? screen_default(ix->dim) : (asked == 0 ? 0u : (asked == 9 ? 3u : (asked == 8 ? 2u : 1u)));
   if (format == 0) return false;
-  alaya_index::ScreenCopy &c = ix->screen_copy[format - 1];
+  const uint32_t copy = format == 3 ? 2u : format;  // the integer pass reads format 2's records
+  alaya_index::ScreenCopy &c = ix->screen_copy[copy - 1];
   if (c.failed) return false;
   if (!c.ready) {
     const uint64_t rows = std::max<uint64_t>(std::max(ix->capacity, ix->n), 1);
@@ -667,7 +672,7 @@ bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStr
         c.rows.release();
         c.err.release();
         c.cap = 0;
-        if (format == 2) {
+        if (copy == 2) {
           c.rows.reserve(rows * alaya_amd::screen_u8_record_bytes(ix->stride));
         } else {
           c.rows.reserve(rows * ix->stride * 2);
@@ -684,7 +689,7 @@ bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStr
       return false;
     }
     scratch_acquire(ix, stream);  // after every earlier launch that may still read the buffers
-    screen_fill(ix, format, 0, ix->n, stream);
+    screen_fill(ix, copy, 0, ix->n, stream);
     c.ready = true;
   }
   ix->screen_format = format;
@@ -2221,38 +2226,72 @@ int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t 
   });
 }
 
+namespace {
+// One vector through the 8-bit screening quantiser, as screen_rows_u8_kernel runs it on a row and
+// screen_query_codes on a query: codes, header {err, lo, scale, 0} and, where asked for, the f32
+// values the codes stand for.
+void screen_u8_quantize_one(const float *x, uint32_t dim, uint8_t *codes, float *header, float *values) {
+  using namespace alaya_amd;
+  float lo = FLT_MAX, hi = -FLT_MAX;
+  bool bad = false;
+  for (uint32_t j = 0; j < dim; ++j) {
+    bad = bad || !screen_finite(x[j]);
+    lo = fminf(lo, x[j]);
+    hi = fmaxf(hi, x[j]);
+  }
+  float scale = screen_u8_scale(lo, hi);
+  if (bad || !screen_finite(scale)) {
+    bad = true;
+    lo = scale = 0.f;
+  }
+  float sum = 0.f;
+  for (uint32_t j = 0; j < dim; ++j) {
+    const uint32_t c = screen_u8_code(x[j], lo, scale);
+    const float y = screen_u8_value(c, lo, scale);
+    const float d = x[j] - y;
+    if (!bad) sum = fmaf(d, d, sum);
+    codes[j] = static_cast<uint8_t>(c);
+    if (values) values[j] = y;
+  }
+  header[0] = screen_u8_err(sum, dim, bad);
+  header[1] = lo;
+  header[2] = scale;
+  header[3] = 0.f;
+}
+}  // namespace
+
 int alaya_screen_u8_quantize(const float *rows, uint64_t n, uint32_t dim, uint8_t *codes, float *header,
                              float *values) {
   return guarded([&] {
-    using namespace alaya_amd;
     if (n && dim && (!rows || !codes || !header || !values)) throw ArgError("invalid arguments");
-    for (uint64_t r = 0; r < n; ++r) {
-      const float *x = rows + r * dim;
-      float lo = FLT_MAX, hi = -FLT_MAX;
-      bool bad = false;
+    for (uint64_t r = 0; r < n; ++r)
+      screen_u8_quantize_one(rows + r * dim, dim, codes + r * dim, header + 4 * r, values + r * dim);
+  });
+}
+
+int alaya_screen_int_bound(const float *queries, const float *rows, uint64_t n, uint32_t dim, float *d_in,
+                           float *e_sum, float *bound, uint32_t *sums) {
+  return guarded([&] {
+    using namespace alaya_amd;
+    if (dim == 0 || dim > 4096) throw ArgError("dim must be in 1 .. 4096");
+    if (n && (!queries || !rows || !d_in || !e_sum || !bound || !sums)) throw ArgError("invalid arguments");
+    std::vector<uint8_t> a(dim), c(dim);
+    for (uint64_t i = 0; i < n; ++i) {
+      float qh[4], rh[4];
+      screen_u8_quantize_one(queries + i * dim, dim, a.data(), qh, nullptr);
+      screen_u8_quantize_one(rows + i * dim, dim, c.data(), rh, nullptr);
+      uint32_t a1 = 0, a2 = 0, c1 = 0, c2 = 0, ac = 0;
       for (uint32_t j = 0; j < dim; ++j) {
-        bad = bad || !screen_finite(x[j]);
-        lo = fminf(lo, x[j]);
-        hi = fmaxf(hi, x[j]);
+        const uint32_t aj = a[j], cj = c[j];
+        a1 += aj; a2 += aj * aj;
+        c1 += cj; c2 += cj * cj;
+        ac += aj * cj;
       }
-      float scale = screen_u8_scale(lo, hi);
-      if (bad || !screen_finite(scale)) {
-        bad = true;
-        lo = scale = 0.f;
-      }
-      float sum = 0.f;
-      for (uint32_t j = 0; j < dim; ++j) {
-        const uint32_t c = screen_u8_code(x[j], lo, scale);
-        const float y = screen_u8_value(c, lo, scale);
-        const float d = x[j] - y;
-        if (!bad) sum = fmaf(d, d, sum);
-        codes[r * dim + j] = static_cast<uint8_t>(c);
-        values[r * dim + j] = y;
-      }
-      header[4 * r] = screen_u8_err(sum, dim, bad);
-      header[4 * r + 1] = lo;
-      header[4 * r + 2] = scale;
-      header[4 * r + 3] = 0.f;
+      d_in[i] = screen_int_distance(dim, qh[1], qh[2], a1, a2, rh[1], rh[2], c1, c2, ac);
+      e_sum[i] = screen_int_err(rh[0], rh[1], rh[2], qh[0], qh[1], qh[2]);
+      bound[i] = screen_int_bound(dim, qh[0], qh[1], qh[2], a1, a2, rh[0], rh[1], rh[2], c1, c2, ac);
+      uint32_t *s = sums + 5 * i;
+      s[0] = a1; s[1] = a2; s[2] = c1; s[3] = c2; s[4] = ac;
     }
   });
 }

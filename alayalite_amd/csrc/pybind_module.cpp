@@ -1080,6 +1080,19 @@ PYBIND11_MODULE(_alayalitepy, m) {
                                    codes.mutable_data(), header.mutable_data(), values.mutable_data()));
     return py::make_tuple(codes, header, values);
   });
+  // the integer screen's bound on the host, pair i = (queries[i], rows[i]): (d_in <= ||q^ - y^||^2,
+  // e_sum >= ||x - y^|| + ||q - q^||, the bound, sums (n x 5: A1, A2, C1, C2, AC))
+  m.def("screen_int_bound", [](py::array_t<float, py::array::c_style | py::array::forcecast> queries,
+                               py::array_t<float, py::array::c_style | py::array::forcecast> rows) {
+    if (rows.ndim() != 2 || queries.ndim() != 2 || rows.shape(0) != queries.shape(0) || rows.shape(1) != queries.shape(1))
+      throw std::invalid_argument("queries and rows must be 2-D of one shape");
+    py::array_t<float> d_in(rows.shape(0)), e_sum(rows.shape(0)), bound(rows.shape(0));
+    py::array_t<uint32_t> sums({rows.shape(0), static_cast<py::ssize_t>(5)});
+    check(alaya_screen_int_bound(queries.data(), rows.data(), static_cast<uint64_t>(rows.shape(0)),
+                                 static_cast<uint32_t>(rows.shape(1)), d_in.mutable_data(), e_sum.mutable_data(),
+                                 bound.mutable_data(), sums.mutable_data()));
+    return py::make_tuple(d_in, e_sum, bound, sums);
+  });
   // the flat search's inner-product bound on the host (flat_bound.h): slack per query, and the test
   m.def("flat_ip_slack", [](int contraction, uint32_t k_acc,
                             py::array_t<float, py::array::c_style | py::array::forcecast> q_norm2,

@@ -77,4 +77,60 @@ ALAYA_HD inline float screen_u8_err(float sum, uint32_t stride, bool bad) {
 }
 ALAYA_HD inline bool screen_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }
 
+// ---- The integer screen over the 8-bit records ("Round 10") -------------------
+// The query is quantised once with the row functions above (qlo, qs, codes a_j, and e_q from
+// screen_u8_err), and a record carries its code sums C1 = sum c_j and C2 = sum c_j^2 as two u32 right
+// after its codes, in the padding every screened width has.
+ALAYA_HD inline uint32_t screen_u8_sums_offset(uint32_t stride) { return kScreenU8Header + stride; }
+
+// A value <= D^ = ||q^ - y^||^2 over the real-valued grids q^_j = qlo + qs a_j, y^_j = lo + s c_j of
+// n <= 4096 elements, from the exact integer sums A1 = sum a, A2 = sum a^2, C1 = sum c, C2 = sum c^2,
+// AC = sum a c (all below 2^28) and delta = qlo - lo:
+//   D^ = n delta^2 + 2 delta (qs A1 - s C1) + qs^2 A2 + s^2 C2 - 2 qs s AC.
+// Six terms in f64.  The products of two f32 values, and of an f32 value and an integer below 2^28,
+// are exact there, so a term carries at most 4 roundings (n delta delta: delta's own twice, two
+// products), the sum 5 more, the magnitude sum, its scaling and the subtraction 7 more: 16 units of
+// 2^-53 of sum |terms| = 2^-49 of it, subtracted explicitly, so cancellation between the terms cannot
+// hide them.  (1 - 2^-23) pays the rounding to f32.  0 = "no bound": not positive, or not finite.
+ALAYA_HD inline float screen_int_distance(uint32_t n, float qlo, float qs, uint32_t a1, uint32_t a2, float lo,
+                                          float s, uint32_t c1, uint32_t c2, uint32_t ac) {
+  const double delta = static_cast<double>(qlo) - static_cast<double>(lo);
+  const double dq = qs, dr = s;
+  const double t1 = (static_cast<double>(n) * delta) * delta;
+  const double t2 = (2.0 * delta) * (dq * static_cast<double>(a1));
+  const double t3 = (2.0 * delta) * (dr * static_cast<double>(c1));
+  const double t4 = (dq * dq) * static_cast<double>(a2);
+  const double t5 = (dr * dr) * static_cast<double>(c2);
+  const double t6 = (2.0 * (dq * dr)) * static_cast<double>(ac);
+  const double sum = ((t1 + t4) + t5) + ((t2 - t3) - t6);
+  const double mag = ((t1 + t4) + t5) + ((fabs(t2) + fabs(t3)) + t6);
+  const double d = (sum - mag * 1.7763568394002505e-15) * (1.0 - 1.1920928955078125e-7);  // 2^-49, 2^-23
+  if (!(d > 0.0) || !(d <= static_cast<double>(kScreenHuge))) return 0.f;
+  return static_cast<float>(d);
+}
+
+// A value >= ||x - y^|| + ||q - q^||, the two triangle steps from the grids to the row and the query.
+// e_row and e_q (screen_u8_err) are measured against the f32 values y_j = screen_u8_value(c_j, lo, s),
+// one rounding away from the grid: |y_j - y^_j| <= 2^-24 |y^_j| (or 2^-126 where the f32 result is not
+// normal) and |y^_j| <= M = max(|lo|, |lo + 255 s|), so ||y - y^|| <= sqrt(n) (2^-24 M + 2^-126)
+// <= 2^-18 M + 2^-120 for n <= 4096; the same for the query.  2^-100 pays both floors, (1 + 2^-22)
+// the f64 roundings (under ten) and the rounding to f32.  +inf or NaN in = the same out = no bound.
+ALAYA_HD inline float screen_int_err(float e_row, float lo, float s, float e_q, float qlo, float qs) {
+  const double m_row = fmax(fabs(static_cast<double>(lo)), fabs(static_cast<double>(lo) + 255.0 * static_cast<double>(s)));
+  const double m_q = fmax(fabs(static_cast<double>(qlo)), fabs(static_cast<double>(qlo) + 255.0 * static_cast<double>(qs)));
+  const double e = ((static_cast<double>(e_row) + static_cast<double>(e_q)) + ((m_row + m_q) * 3.814697265625e-6 +
+                                                                            7.888609052210118e-31)) *
+                   (1.0 + 2.384185791015625e-7);  // 2^-18, 2^-100, 2^-22
+  return static_cast<float>(e);
+}
+
+// The integer screen's bound: <= the reference's f32 L2 distance of q and x.  screen_lower_bound needs
+// of its first argument only that it is <= D~ (1 + u)^(n + 2) for the D~ its e_row belongs to; here
+// D~ = D^ and screen_int_distance is <= D^ itself.
+ALAYA_HD inline float screen_int_bound(uint32_t n, float e_q, float qlo, float qs, uint32_t a1, uint32_t a2, float e_row,
+                                       float lo, float s, uint32_t c1, uint32_t c2, uint32_t ac) {
+  return screen_lower_bound(screen_int_distance(n, qlo, qs, a1, a2, lo, s, c1, c2, ac),
+                            screen_int_err(e_row, lo, s, e_q, qlo, qs), n);
+}
+
 }  // namespace alaya_amd

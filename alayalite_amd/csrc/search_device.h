@@ -503,6 +503,152 @@ __device__ __forceinline__ void screen_distances_u8(const SearchParams &p, const
 }
 
 // --------------------------------------------------------------------------------------------
+// The integer screen on the 8-bit records (SearchParams::screen == 3, screen_bound.h): the query is
+// quantised once per query with the rows' quantiser, and a candidate costs one integer dot product
+// AC = sum a_j c_j of the two code vectors (v_dot4_u32_u8, four codes per instruction); the record's
+// C1, C2 and the query's A1, A2 turn it into a lower bound on ||q^ - y^||^2 (screen_int_distance).
+//
+// A lane owns one 16-byte piece of every row -- lane l takes elements 16 l .. 16 l + 15, lanes past
+// the row (d = 960: 60 .. 63) hold query codes 0 -- so it needs only its own 16 query codes: 4 registers for the
+// whole query, no LDS (the wide-row launches have no LDS to spare: at d = 960, ef 387 the visited
+// table leaves 480 B of a wave's share, and the codes would halve it).  One load instruction reads
+// one record's codes, 1 KB contiguous, from a wave-uniform base (a v_readlane of the lane that holds
+// the id); a pass holds 32 rows, 16 B each, the registers of the f32-arithmetic pass.  The 32 partial
+// sums per lane are then summed over the 64 lanes by halving: at each of five steps a lane keeps half
+// of its sums and adds the partner lane's, so 31 exchanges leave one row's sum per lane, and the two
+// 32-lane halves meet in one ds_bpermute.
+// --------------------------------------------------------------------------------------------
+template <int kXor>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t v) {
+  return __builtin_bit_cast(uint32_t, lane_xor<kXor>(__builtin_bit_cast(float, v)));
+}
+
+struct ScreenQuery {
+  uint4 codes;      // the lane's 16 query codes (0 past the row)
+  uint32_t a1, a2;  // sum a_j, sum a_j^2                      (wave-uniform, as the three below)
+  float lo, scale;  // the query's grid
+  float err;        // e_q >= ||q - (the f32 values its codes stand for)||_2; +inf = no bound
+};
+
+// Quantises the query in LDS (`stride` f32 values, padding included, as the rows' records hold them)
+// the way screen_rows_u8_kernel quantises a row.
+template <int kChunks>
+__device__ __forceinline__ ScreenQuery screen_query_codes(const SearchParams &p, const float *q) {
+  constexpr int kPieces = 2 * kChunks;
+  static_assert(kPieces <= 64, "a lane per 16-element piece of the row");
+  const int lane = lane_id();
+  const bool has = lane < kPieces;
+  float x[16];
+  float lo = FLT_MAX, hi = -FLT_MAX;
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (has) {
+      v = reinterpret_cast<const float4 *>(q)[4 * lane + k];
+      bad = bad || !screen_finite(v.x) || !screen_finite(v.y) || !screen_finite(v.z) || !screen_finite(v.w);
+      lo = fminf(fminf(lo, v.x), fminf(fminf(v.y, v.z), v.w));
+      hi = fmaxf(fmaxf(hi, v.x), fmaxf(fmaxf(v.y, v.z), v.w));
+    }
+    x[4 * k] = v.x; x[4 * k + 1] = v.y; x[4 * k + 2] = v.z; x[4 * k + 3] = v.w;
+  }
+  lo = fminf(lo, lane_xor<1>(lo)); hi = fmaxf(hi, lane_xor<1>(hi));
+  lo = fminf(lo, lane_xor<2>(lo)); hi = fmaxf(hi, lane_xor<2>(hi));
+  lo = fminf(lo, lane_xor<4>(lo)); hi = fmaxf(hi, lane_xor<4>(hi));
+  lo = fminf(lo, lane_xor<8>(lo)); hi = fmaxf(hi, lane_xor<8>(hi));
+  lo = fminf(lo, lane_xor<16>(lo)); hi = fmaxf(hi, lane_xor<16>(hi));
+  lo = fminf(read_lane(lo, 0), read_lane(lo, 32));
+  hi = fmaxf(read_lane(hi, 0), read_lane(hi, 32));
+  float scale = screen_u8_scale(lo, hi);
+  bad = ballot(bad) != 0ull || !screen_finite(scale);
+  if (bad) lo = scale = 0.f;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  uint32_t a1 = 0u, a2 = 0u;
+  float sum = 0.f;
+  if (has) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const uint32_t c = screen_u8_code(x[j], lo, scale);
+      const float d = x[j] - screen_u8_value(c, lo, scale);
+      if (!bad) sum = fmaf(d, d, sum);
+      a1 += c;
+      a2 += c * c;
+      w[j >> 2] |= c << (8 * (j & 3));
+    }
+  }
+  sum += lane_xor<1>(sum); a1 += lane_xor<1>(a1); a2 += lane_xor<1>(a2);
+  sum += lane_xor<2>(sum); a1 += lane_xor<2>(a1); a2 += lane_xor<2>(a2);
+  sum += lane_xor<4>(sum); a1 += lane_xor<4>(a1); a2 += lane_xor<4>(a2);
+  sum += lane_xor<8>(sum); a1 += lane_xor<8>(a1); a2 += lane_xor<8>(a2);
+  sum += lane_xor<16>(sum); a1 += lane_xor<16>(a1); a2 += lane_xor<16>(a2);
+  ScreenQuery Q;
+  Q.codes = make_uint4(w[0], w[1], w[2], w[3]);
+  Q.a1 = read_lane(a1, 0) + read_lane(a1, 32);
+  Q.a2 = read_lane(a2, 0) + read_lane(a2, 32);
+  Q.lo = lo;
+  Q.scale = scale;
+  Q.err = screen_u8_err(read_lane(sum, 0) + read_lane(sum, 32), p.stride, bad);
+  return Q;
+}
+
+// One halving step of the 64-lane sum: v[0 .. kN) -> v[0 .. kN / 2).  A lane whose bit kXor is clear
+// keeps the lower half and takes the partner's lower half, a lane whose bit is set the upper halves.
+template <int kXor, int kN>
+__device__ __forceinline__ void screen_fold(uint32_t *v, bool upper) {
+#pragma unroll
+  for (int i = 0; i < kN / 2; ++i) {
+    const uint32_t keep = upper ? v[i + kN / 2] : v[i];
+    const uint32_t send = upper ? v[i] : v[i + kN / 2];
+    v[i] = keep + lane_xor<kXor>(send);
+  }
+}
+
+// AC of the query codes and the records of rows ids[0 .. n) -> out[0 .. n).
+// after_issue() runs once, right after the first pass's loads are issued (see sq8_distances).
+template <int kChunks, typename Hook>
+__device__ __forceinline__ void screen_dots_int(const SearchParams &p, const uint4 qc, const uint32_t *ids, int n,
+                                                uint32_t *out, Hook after_issue) {
+  constexpr int kPieces = 2 * kChunks;
+  const int lane = lane_id();
+  const uint32_t rec = screen_u8_record_bytes(p.stride);
+  // a lane past the row reads the row's last piece again, against query codes that are 0: no exec
+  // mask around the loads, and every address is a wave-uniform base plus one per-lane offset
+  const uint32_t piece = kScreenU8Header + 16u * static_cast<uint32_t>(lane < kPieces ? lane : kPieces - 1);
+  // after the five steps lane l holds the row whose index is l's low five bits reversed
+  const int mine = ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
+  for (int base = 0; base < n; base += 32) {
+    // lanes past the list hold the pass's first id: their rows are loaded again (cache hits whose
+    // sums are dropped), so the issue is branch-free
+    const uint32_t id = ids[base + lane < n ? base + lane : base];
+    uint4 y[32];
+#pragma unroll
+    for (int r = 0; r < 32; ++r) {
+      const uint8_t *rp = p.screen_u8 + static_cast<uint64_t>(read_lane(id, r)) * rec;
+      y[r] = *reinterpret_cast<const uint4 *>(rp + piece);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // every load of the pass before the first dot product
+    if (base == 0) after_issue();
+    uint32_t acc[32];
+#pragma unroll
+    for (int r = 0; r < 32; ++r) {  // loads retire in issue order: row r's sum runs while rows r + 1 .. arrive
+      uint32_t a = __builtin_amdgcn_udot4(qc.x, y[r].x, 0u, false);
+      a = __builtin_amdgcn_udot4(qc.y, y[r].y, a, false);
+      a = __builtin_amdgcn_udot4(qc.z, y[r].z, a, false);
+      acc[r] = __builtin_amdgcn_udot4(qc.w, y[r].w, a, false);
+      if ((r & 7) == 7) __builtin_amdgcn_sched_barrier(0);  // (the scheduler would start with the last rows)
+    }
+    screen_fold<1, 32>(acc, (lane & 1) != 0);
+    screen_fold<2, 16>(acc, (lane & 2) != 0);
+    screen_fold<4, 8>(acc, (lane & 4) != 0);
+    screen_fold<8, 4>(acc, (lane & 8) != 0);
+    screen_fold<16, 2>(acc, (lane & 16) != 0);
+    const uint32_t tot = acc[0] + static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, static_cast<int>(acc[0])));
+    if (lane < 32 && base + mine < n) out[base + mine] = tot;
+  }
+  wave_sync();
+}
+
+// --------------------------------------------------------------------------------------------
 // SQ8 distances (SQ8Space::QueryComputer over l2_sqr_sq8 / ip_sqr_sq8).  The reference picks the
 // AVX-512 kernel when the host has AVX-512F, else AVX2 (distance_l2.ipp:694-708,
 // distance_ip.ipp:703-716).  Both are "P partial sums, element P*t+j -> acc[j]":

@@ -87,7 +87,8 @@ struct SearchParams {
   // Candidate screen (search_has_screen; kModeScreen): once the pool is full, an expansion's fresh
   // candidates are first measured on a low-precision copy of their rows, and only those whose proven
   // lower bound (screen_bound.h) is below the pool's worst distance read their f32 row.
-  uint32_t screen;             // the screening kernel's copy: 0 = none, 1 = f16, 2 = 8-bit records
+  uint32_t screen;             // the screening kernel's copy: 0 = none, 1 = f16, 2 = 8-bit records,
+                               // 3 = the same records under integer dot products with the query's codes
   const uint16_t *screen_rows; // f16: n rows of `stride` f16 values (stride * 2 bytes, a multiple of 64)
   const float *screen_err;     // f16: per row, >= ||x - f16(x)||_2; +inf = never screened out
   const uint8_t *screen_u8;    // 8-bit: n records of screen_u8_record_bytes(stride) bytes (screen_bound.h):

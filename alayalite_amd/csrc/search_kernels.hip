@@ -654,6 +654,10 @@ __global__ void __launch_bounds__(256)
     PoolState ps;
     uint32_t n_dist = 0, n_expand = 0, n_dist_up = 0, n_hops_up = 0;
     query_begin<kIP, kChunks, kSpace, kRows>(p, L, qi, slot_bits, slot_dirty, slot_stab, vs, ps, n_dist_up, n_hops_up);
+    ScreenQuery sq{};  // the integer screen's view of the query (p.screen == 3), in registers
+    if constexpr (kScreen) {
+      if (p.screen == 3) sq = screen_query_codes<kChunks>(p, L.q);
+    }
 
     // ---- best-first expansion (graph_search_job.hpp:228-252 / 310-330) -----------------------
     stamp(0);
@@ -820,7 +824,18 @@ __global__ void __launch_bounds__(256)
           const bool in = lane < nf;
           const uint32_t c = in ? L.cid[lane] : 0u;
           float e_row = 0.f;
-          if (p.screen == 2) {  // wave-uniform: the 8-bit records, e_row in the header of each
+          float lb3 = 0.f;  // p.screen == 3: the bound itself
+          if (p.screen == 3) {  // wave-uniform: the 8-bit records under the integer dot product
+            // The lane's record header and code sums go out ahead of the pass's loads, in straight-line
+            // code (a lane past the list reads row 0's): under `if (in)` the compiler joined this block
+            // with the bound's and waited for both loads, two round trips, before the pass was issued.
+            const uint8_t *rp = p.screen_u8 + static_cast<uint64_t>(c) * screen_u8_record_bytes(p.stride);
+            const float4 head = *reinterpret_cast<const float4 *>(rp);
+            const uint2 sums = *reinterpret_cast<const uint2 *>(rp + screen_u8_sums_offset(p.stride));
+            screen_dots_int<kChunks>(p, sq.codes, L.cid, nf, reinterpret_cast<uint32_t *>(L.cd), second_level_prefetch);
+            lb3 = screen_int_bound(p.stride, sq.err, sq.lo, sq.scale, sq.a1, sq.a2, head.x, head.y, head.z, sums.x, sums.y,
+                                   __float_as_uint(L.cd[lane]));  // (past the list: a stale word, a bound nobody reads)
+          } else if (p.screen == 2) {  // the 8-bit records in f32 arithmetic, e_row in the header of each
             if (in) e_row = *reinterpret_cast<const float *>(p.screen_u8 + static_cast<uint64_t>(c) * screen_u8_record_bytes(p.stride));
             screen_distances_u8<kChunks, kScreenRowsU8>(p, L.q, L.cid, nf, L.cd, second_level_prefetch);
           } else {
@@ -829,7 +844,7 @@ __global__ void __launch_bounds__(256)
           }
           bool keep = false;
           if (in) {
-            const float lb = screen_lower_bound(L.cd[lane], e_row, p.dim);
+            const float lb = p.screen == 3 ? lb3 : screen_lower_bound(L.cd[lane], e_row, p.dim);
             keep = !(lb > 0.f && lb >= tau);  // lb == 0: no bound (never screened out)
           }
           const uint64_t km = ballot(keep);
@@ -985,10 +1000,13 @@ __global__ void __launch_bounds__(256) screen_rows_u8_kernel(const float *base, 
       lo = scale = 0.f;
     }
     float sum = 0.f;
+    uint32_t s1 = 0u, s2 = 0u;  // sum c, sum c^2: the integer screen's C1, C2
     for (uint32_t e = 4 * lane; e < stride; e += 256) {
       const float4 x = *reinterpret_cast<const float4 *>(row + e);
       const uint32_t c0 = screen_u8_code(x.x, lo, scale), c1 = screen_u8_code(x.y, lo, scale);
       const uint32_t c2 = screen_u8_code(x.z, lo, scale), c3 = screen_u8_code(x.w, lo, scale);
+      s1 += (c0 + c1) + (c2 + c3);
+      s2 += (c0 * c0 + c1 * c1) + (c2 * c2 + c3 * c3);
       const float d0 = x.x - screen_u8_value(c0, lo, scale), d1 = x.y - screen_u8_value(c1, lo, scale);
       const float d2 = x.z - screen_u8_value(c2, lo, scale), d3 = x.w - screen_u8_value(c3, lo, scale);
       if (!bad) {
@@ -1005,7 +1023,18 @@ __global__ void __launch_bounds__(256) screen_rows_u8_kernel(const float *base, 
     sum += lane_xor<8>(sum);
     sum += lane_xor<16>(sum);
     sum = read_lane(sum, 0) + read_lane(sum, 32);
-    if (lane == 0) *reinterpret_cast<float4 *>(dst) = make_float4(screen_u8_err(sum, stride, bad), lo, scale, 0.f);
+    s1 += lane_xor<1>(s1); s2 += lane_xor<1>(s2);
+    s1 += lane_xor<2>(s1); s2 += lane_xor<2>(s2);
+    s1 += lane_xor<4>(s1); s2 += lane_xor<4>(s2);
+    s1 += lane_xor<8>(s1); s2 += lane_xor<8>(s2);
+    s1 += lane_xor<16>(s1); s2 += lane_xor<16>(s2);
+    s1 = read_lane(s1, 0) + read_lane(s1, 32);
+    s2 = read_lane(s2, 0) + read_lane(s2, 32);
+    if (lane == 0) {
+      *reinterpret_cast<float4 *>(dst) = make_float4(screen_u8_err(sum, stride, bad), lo, scale, 0.f);
+      // in the record's padding (screen_u8_record_bytes: stride is a multiple of 32, so 16 or 48 bytes)
+      *reinterpret_cast<uint2 *>(dst + screen_u8_sums_offset(stride)) = make_uint2(s1, s2);
+    }
   }
 }
 

@@ -263,8 +263,10 @@ int alaya_index_help_stats(alaya_index *ix, uint64_t *memo_dists, uint64_t *memo
  * distance read their f32 row.  Two copies exist, each built at the first search that uses it and
  * freed with the base: the rows as f16 (n x stride x 2 bytes + 4 bytes per row), and 8-bit records
  * (per row a 16-byte header {e_row, lo, scale, 0} and stride codes for lo + code x scale, padded to
- * a multiple of 64 bytes: 1024 bytes at d = 960).  Environment ALAYA_SEARCH_SCREEN, read per launch:
- * 0 = no screen, 1 = the f16 copy, 8 = the 8-bit records, unset = the default of the width.
+ * a multiple of 64 bytes: 1024 bytes at d = 960; the first 8 bytes of the padding hold sum code and
+ * sum code^2 as u32).  Environment ALAYA_SEARCH_SCREEN, read per launch:
+ * 0 = no screen, 1 = the f16 copy, 8 = the 8-bit records in f32 arithmetic, 9 = the same records
+ * against the query's own 8-bit codes (integer dot products), unset = the default of the width.
  * Results and counters never depend on it.  alaya_index_screen_stats: of the last graph search,
  * how many candidates were screened and how many of those were screened out (waits for that search;
  * 0, 0 when it did not screen). */
@@ -278,6 +280,15 @@ int alaya_screen_lower_bound(const float *d_tilde, const float *e_row, uint64_t 
  * f32 value each code stands for).  e_row >= ||row - values||_2, +inf for a row that is not finite. */
 int alaya_screen_u8_quantize(const float *rows, uint64_t n, uint32_t dim, uint8_t *codes, float *header,
                              float *values);
+/* The integer screen's bound (ALAYA_SEARCH_SCREEN=9) for the n pairs (queries[i], rows[i]) of dim <= 4096
+ * elements, made on the host by the functions the kernel calls (screen_bound.h).  Both vectors go
+ * through the 8-bit quantiser above; with q^, y^ the real-valued grids lo + code x scale of the two,
+ * d_in[i] <= ||q^ - y^||^2 (0 = no bound), e_sum[i] >= ||x - y^|| + ||q - q^||, bound[i] <= the
+ * reference's f32 L2 distance of the pair, and sums (n x 5) holds the exact integers the kernel works
+ * from: sum a, sum a^2 (query codes), sum c, sum c^2 (row codes: the two u32 a record carries after
+ * its codes), sum a c. */
+int alaya_screen_int_bound(const float *queries, const float *rows, uint64_t n, uint32_t dim, float *d_in,
+                           float *e_sum, float *bound, uint32_t *sums);
 /* The flat search's inner-product bound, evaluated on the host by the functions the merge kernels
  * call (flat_bound.h).  alaya_flat_ip_slack: out[i] >= |d_ref + C~| for the reference's f32 distance
  * d_ref = -(q.b) (ip_sqr_avx2) and the scan's contraction C~ (0 = f32 MFMA, 1 = bf16 hi/lo split, 2 =
