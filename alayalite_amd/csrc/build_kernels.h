@@ -15,6 +15,7 @@
 // 1-4 on level 0 for the batch: the batch's points are now in the graph (reverse edges of step 4),
 // so each point re-selects its neighbours among old points and batch mates alike; apply skips
 // edges a list already holds.
+// Pinned bit for bit (graph and counters) to the CPU restatement oracle/oracle_build_batched.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

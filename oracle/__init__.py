@@ -55,7 +55,7 @@ class OrcCounters(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile liboracle.so with the committed Makefile (gcc only, no GPU)."""
-    srcs = [os.path.join(_HERE, f) for f in ("oracle.cpp", "oracle_build.cpp", "oracle.h", "Makefile")]
+    srcs = [os.path.join(_HERE, f) for f in ("oracle.cpp", "oracle_build.cpp", "oracle_build_batched.cpp", "oracle.h", "Makefile")]
     if force or not os.path.exists(_LIB_PATH) or any(os.path.getmtime(_LIB_PATH) < os.path.getmtime(f) for f in srcs):
         subprocess.run(["make", "-s", "-C", _HERE], check=True)
     return _LIB_PATH
@@ -125,6 +125,13 @@ def lib():
         _lib.orc_hnsw_upper_slots.argtypes = [p]
         _lib.orc_hnsw_export.argtypes = [p, p, p, p, p, p]
         _lib.orc_hnsw_free.argtypes = [p]
+        _lib.orc_hnsw_batched_build.restype = p
+        _lib.orc_hnsw_batched_build.argtypes = [p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32,
+                                                C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
+        _lib.orc_hnsw_batched_upper_slots.restype = C.c_uint64
+        _lib.orc_hnsw_batched_upper_slots.argtypes = [p]
+        _lib.orc_hnsw_batched_export.argtypes = [p, p, p, p, p, p, p]
+        _lib.orc_hnsw_batched_free.argtypes = [p]
         _lib.orc_cpu_has_avx2_fma.restype = C.c_int
         _lib.orc_cpu_has_avx512f.restype = C.c_int
     return _lib
@@ -330,6 +337,34 @@ def build_hnsw(base, metric=L2, R=32, ef_construction=100, seed=100, generic=Fal
     finally:
         lib().orc_hnsw_free(h)
     return l0, levels, off, ue[:slots], int(ep[0]), R
+
+
+_BATCHED_STATS = ("batches", "max_batch", "max_level", "prunes", "appends", "heuristic_dists", "max_incoming",
+                  "steps")
+
+
+def build_hnsw_batched(base, metric=L2, R=32, ef_construction=100, seed=100, batch_div=0, max_batch=0, refine=2,
+                       generic=False):
+    """The engine's batched device build restated on the CPU (oracle_build_batched.cpp).  Returns
+    (l0[n, R], levels[n], upper_off[n], upper_edges, ep, upper_R, stats) in the engine's
+    Graph.arrays() layout; stats is a dict of the counters the device build reports plus
+    max_incoming and steps."""
+    b = np.ascontiguousarray(base, np.float32)
+    n, dim = b.shape
+    h = lib().orc_hnsw_batched_build(_ptr(b), n, dim, metric, 1 if generic else 0, R, ef_construction, seed,
+                                     batch_div, max_batch, refine)
+    try:
+        slots = lib().orc_hnsw_batched_upper_slots(h)
+        l0 = np.zeros((n, R), np.uint32)
+        levels = np.zeros(n, np.uint32)
+        off = np.zeros(n, np.uint64)
+        ue = np.zeros(max(slots, 1), np.uint32)
+        ep = np.zeros(1, np.uint32)
+        st = np.zeros(len(_BATCHED_STATS), np.uint64)
+        lib().orc_hnsw_batched_export(h, _ptr(l0), _ptr(levels), _ptr(off), _ptr(ue), _ptr(ep), _ptr(st))
+    finally:
+        lib().orc_hnsw_batched_free(h)
+    return l0, levels, off, ue[:slots], int(ep[0]), R, dict(zip(_BATCHED_STATS, (int(v) for v in st)))
 
 
 def sq8_fit(data):

@@ -24,6 +24,8 @@
  *                                   (job_context.hpp:25-29), Graph/RawSpace insert + remove
  *   orc_hnsw_*                      HNSWBuilder::build_graph, one thread (oracle_build.cpp:
  *                                   hnsw_builder.hpp:98-194, hnswlib.hpp:87-751)
+ *   orc_hnsw_batched_*              no reference routine: the engine's own batched insertion
+ *                                   (build_kernels.h), restated in oracle_build_batched.cpp
  *   orc_sq8_*                       SQ8Quantizer (space/quant/sq8.hpp:99-143) and the AVX-512 /
  *                                   AVX2 SQ8 kernels (distance_l2.ipp:244-408, distance_ip.ipp:198-366)
  *
@@ -143,6 +145,22 @@ uint64_t orc_hnsw_upper_slots(const orc_hnsw *o);
 void orc_hnsw_export(const orc_hnsw *o, uint32_t *l0, uint32_t *levels, uint64_t *upper_off,
                      uint32_t *upper_edges, uint32_t *ep);
 void orc_hnsw_free(orc_hnsw *o);
+
+/* ---- batched HNSW construction (oracle_build_batched.cpp) -------------------------------------
+ * The engine's batched device build (alayalite_amd/csrc/build_kernels.h) restated with plain loops;
+ * the rules are spelled out at the top of oracle_build_batched.cpp.  batch_div / max_batch = 0 take
+ * the defaults 16 / 65536; batch_div = max_batch = 1, refine = 0 is the sequential algorithm.
+ * export: the arrays of orc_hnsw_export plus stats[8] = batches, max_batch (largest step), max_level,
+ * prunes, appends, heuristic_dists, max_incoming (most reverse edges one destination received in
+ * one step), steps. */
+typedef struct orc_hnsw_batched orc_hnsw_batched;
+orc_hnsw_batched *orc_hnsw_batched_build(const float *rows, uint64_t n, uint32_t dim, int metric, int generic,
+                                         uint32_t R, uint32_t ef_construction, uint64_t seed, uint32_t batch_div,
+                                         uint32_t max_batch, uint32_t refine);
+uint64_t orc_hnsw_batched_upper_slots(const orc_hnsw_batched *o);
+void orc_hnsw_batched_export(const orc_hnsw_batched *o, uint32_t *l0, uint32_t *levels, uint64_t *upper_off,
+                             uint32_t *upper_edges, uint32_t *ep, uint64_t *stats);
+void orc_hnsw_batched_free(orc_hnsw_batched *o);
 
 /* ---- SQ8 ---------------------------------------------------------------------------------- */
 /* find_exact_gt (include/utils/evaluate.hpp:29-62): per query, l2_sqr to every row, std::sort of

@@ -13,6 +13,7 @@ The device build is batched insertion, so its graph is not the sequential one; w
 
 import numpy as np
 import pytest
+from build_common import check_structure
 
 pytestmark = pytest.mark.gpu
 
@@ -47,23 +48,7 @@ def _build(native, base, metric=0, R=32, efc=100, batch_div=0, max_batch=0, refi
 
 
 def _check_structure(g, n, R):
-    l0, levels, off, ue, ep, upper_r, _ = g.arrays()
-    assert l0.shape == (n, R) and upper_r == R
-    for i in range(n):
-        row = l0[i]
-        cnt = int(np.argmax(row == 0xFFFFFFFF)) if (row == 0xFFFFFFFF).any() else R
-        assert (row[cnt:] == 0xFFFFFFFF).all(), i
-        live = row[:cnt]
-        assert (live < n).all() and i not in live and len(set(live.tolist())) == cnt, i
-    top = int(levels.max())
-    assert levels[ep] == top
-    for i in np.nonzero(levels)[0]:
-        for lv in range(1, int(levels[i]) + 1):
-            lst = ue[off[i] + (lv - 1) * R: off[i] + lv * R]
-            live = lst[lst != 0xFFFFFFFF]
-            assert len(live) <= R // 2 and (lst[len(live):] == 0xFFFFFFFF).all()
-            assert i not in live and all(levels[v] >= lv for v in live), (i, lv)
-    return l0, levels
+    return check_structure(g.arrays(), n, R)
 
 
 def test_structure_levels_and_determinism(native):
