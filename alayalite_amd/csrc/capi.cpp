@@ -152,6 +152,11 @@ struct alaya_index {
   DevBuf screen_stats;
   uint64_t screen_stats_slots = 0;  // searchers of the last launch, 0 = it did not screen
   uint32_t last_grid = 0, last_waves = 0;  // the last search launch's workgroups and waves per workgroup
+  // the rest of its plan (alaya_index_last_plan): LDS bytes per workgroup, visited-table log2 slots and
+  // layout, searchers per CU, SearchParams::scout
+  uint32_t last_lds = 0, last_hash_log2 = 0, last_compact = 0, last_per_cu = 0, last_scout = 0;
+  DevBuf scout_stats;
+  uint64_t scout_stats_slots = 0;   // searchers of the last launch, 0 = it had no scouts
   int visited_mode_override = 0;  // 0 auto, 1 compact 16-bit slots, 2 wide 32-bit slots,
                                   // 3 compact with probes capped at 2 (exercises the probe spill)
   int num_cus = 0;
@@ -496,7 +501,28 @@ struct SearchPlan {
   int W;       // waves (searchers) per workgroup
   size_t lds;  // bytes per workgroup
   int grid;    // persistent workgroups
+  int per_cu;  // resident workgroups per CU
 };
+
+// ALAYA_SEARCH_SCOUT (0 = off, 1 = on, 2 = on and every memo hit verified against the searcher's own
+// bounds; unset = scout_default) and the diagnostics flag ALAYA_SEARCH_SCOUT_MISS=1 (no answer ever
+// matches: every expansion takes the fallback) as SearchParams::scout.
+// Default per width: on where the scouted search measured faster on MI355X than the same launch
+// without scouts, and than the parent build, by the project's rule (the slowest new run above the
+// fastest old one by more than 3x the old one's min-max spread): d = 768 and d = 960, GIST-shaped, 1k
+// queries.  The runs and their figures are in profiles/r11/README.md and DESIGN.md section 3, "Round 11".
+uint32_t scout_default(uint32_t dim) { return (dim == 768 || dim == 960) ? alaya_amd::kScoutOn : 0u; }
+
+uint32_t scout_requested(uint32_t dim) {
+  const char *e = std::getenv("ALAYA_SEARCH_SCOUT");
+  const int asked = e && e[0] ? std::atoi(e) : -1;
+  uint32_t f = asked < 0 ? scout_default(dim) : (asked == 1 ? alaya_amd::kScoutOn : (asked == 2 ? alaya_amd::kScoutOn | alaya_amd::kScoutVerify : 0u));
+  if (f != 0u) {
+    const char *m = std::getenv("ALAYA_SEARCH_SCOUT_MISS");
+    if (m && std::atoi(m) != 0) f |= alaya_amd::kScoutMiss;
+  }
+  return f;
+}
 
 // Resolves the request and sizes the launch for the kernel it got, so a feature that has no kernel
 // for this shape is planned as absent: sets p.help / p.two_waves / p.screen, the visited table
@@ -552,6 +578,35 @@ SearchPlan plan_search(alaya_index *ix, SearchParams &p, alaya_amd::SearchReques
   const uint64_t cus = static_cast<uint64_t>(stream_cus(ix, stream));
   const uint64_t blocks_needed = p.help ? static_cast<uint64_t>(per_cu) * cus : (nq + plan.W - 1) / plan.W;
   plan.grid = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(blocks_needed, static_cast<uint64_t>(per_cu) * cus)));
+  plan.per_cu = per_cu;
+  // Scout: a launch that would run the one-wave kernel under the integer screen at d = 768 / 960, one
+  // searcher per workgroup, moves to the two-waves kernel with a scout wave beside every searcher --
+  // the second wave per SIMD that the batch leaves idle.  Only if nothing else changes: the visited
+  // table and the searcher's LDS region are the ones planned above, the board fits beside them without
+  // costing a resident workgroup, and the batch runs in one round (a larger batch's second wave per
+  // SIMD belongs to another searcher).  Otherwise the plan stands as it is: never half on.
+  p.scout = 0u;
+  const uint32_t scout = scout_requested(ix->dim);
+  if (scout != 0u && p.screen == 3u && !p.ip && !p.two_waves && !p.help && plan.W == 1 && ix->R <= kScoutR &&
+      (plan.variant->mode & ~kModeScreen) == 0 && search_has_two_waves(ix->dim, p.sq8_order, ix->generic) &&
+      !helpers_requested(ix, p, nq, cus)) {
+    SearchRequest r2 = r;
+    r2.want |= kModeTwoWaves;
+    const SearchVariant &v2 = resolve_search_variant(r2);
+    const size_t lds2 = plan.lds + kScoutBoardBytes;
+    int per_cu2 = 0;
+    if (v2.mode == (kModeScreen | kModeTwoWaves) && lds2 <= kLdsPerCu)
+      hip_check(search_occupancy(v2, false, 2, lds2, &per_cu2), "occupancy");
+    if (per_cu2 >= per_cu && nq <= static_cast<uint64_t>(per_cu) * cus) {
+      plan.variant = &v2;
+      plan.lds = lds2;
+      p.scout = scout;
+      // diagnostics (ALAYA_SEARCH_SCOUT_GRID, include/alaya_hip.h): fewer workgroups than queries, so every
+      // searcher -- and its scout -- runs several queries of the launch, one after the other
+      if (const char *e = std::getenv("ALAYA_SEARCH_SCOUT_GRID"))
+        plan.grid = std::max(1, std::min(plan.grid, std::atoi(e)));
+    }
+  }
   return plan;
 }
 
@@ -606,7 +661,18 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   const uint64_t searchers = static_cast<uint64_t>(plan.grid) * plan.W;
   prepare_spill(ix, p, searchers, stream);
   ix->last_grid = static_cast<uint32_t>(plan.grid);
-  ix->last_waves = static_cast<uint32_t>(plan.W);
+  const int wg_waves = p.scout ? 2 * plan.W : plan.W;  // a scout wave beside every searcher
+  ix->last_waves = static_cast<uint32_t>(wg_waves);
+  ix->last_lds = static_cast<uint32_t>(plan.lds);
+  ix->last_hash_log2 = p.hash_log2;
+  ix->last_compact = p.vis_rbits != alaya_amd::kVisWide ? 1u : 0u;
+  ix->last_per_cu = static_cast<uint32_t>(plan.per_cu);
+  ix->last_scout = p.scout;
+  ix->scout_stats_slots = p.scout ? searchers : 0;
+  if (p.scout) {
+    ix->scout_stats.reserve(searchers * 16);
+    p.scout_stats = ix->scout_stats.as<uint32_t>();
+  }
   ix->help_stats_slots = p.help ? searchers : 0;
   if (p.help) {
     ix->help_stats.reserve(searchers * 12);
@@ -620,7 +686,7 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   ix->work.reserve(4);
   p.work_counter = ix->work.as<uint32_t>();
   hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
-  hip_check(alaya_amd::launch_search(*plan.variant, p, plan.grid, plan.W, plan.lds, stream), "search launch");
+  hip_check(alaya_amd::launch_search(*plan.variant, p, plan.grid, wg_waves, plan.lds, stream), "search launch");
   scratch_release(ix, stream);
 }
 
@@ -2187,6 +2253,37 @@ int alaya_index_last_launch(const alaya_index *ix, uint32_t *workgroups, uint32_
     if (!ix) throw ArgError("null index");
     if (workgroups) *workgroups = ix->last_grid;
     if (waves_per_group) *waves_per_group = ix->last_waves;
+  });
+}
+
+int alaya_index_last_plan(const alaya_index *ix, uint32_t *lds_bytes, uint32_t *hash_log2, uint32_t *compact,
+                          uint32_t *groups_per_cu, uint32_t *scout) {
+  return guarded([&] {
+    if (!ix) throw ArgError("null index");
+    if (lds_bytes) *lds_bytes = ix->last_lds;
+    if (hash_log2) *hash_log2 = ix->last_hash_log2;
+    if (compact) *compact = ix->last_compact;
+    if (groups_per_cu) *groups_per_cu = ix->last_per_cu;
+    if (scout) *scout = ix->last_scout;
+  });
+}
+
+int alaya_index_scout_stats(alaya_index *ix, uint64_t *expansions, uint64_t *hits, uint64_t *records,
+                            uint64_t *mismatches) {
+  return guarded_scratch(ix, [&] {
+    if (!ix) throw ArgError("null index");
+    uint64_t t[4] = {0, 0, 0, 0};
+    if (ix->scout_stats_slots) {
+      set_device(ix);
+      scratch_drain(ix);
+      std::vector<uint32_t> h(4 * ix->scout_stats_slots);
+      hip_check(hipMemcpy(h.data(), ix->scout_stats.ptr, h.size() * 4, hipMemcpyDeviceToHost), "D2H");
+      for (uint64_t i = 0; i < h.size(); ++i) t[i & 3] += h[i];
+    }
+    if (expansions) *expansions = t[0];
+    if (hits) *hits = t[1];
+    if (records) *records = t[2];
+    if (mismatches) *mismatches = t[3];
   });
 }
 

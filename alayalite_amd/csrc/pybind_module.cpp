@@ -321,6 +321,25 @@ class PyIndexInterface {
     check(alaya_index_screen_stats(ix_, &a, &b));
     return py::make_tuple(a, b);
   }
+  py::tuple scout_stats() {
+    uint64_t e = 0, h = 0, r = 0, m = 0;
+    check(alaya_index_scout_stats(ix_, &e, &h, &r, &m));
+    return py::make_tuple(e, h, r, m);
+  }
+  py::dict last_plan() {
+    uint32_t g = 0, w = 0, lds = 0, hl = 0, c = 0, pc = 0, sc = 0;
+    check(alaya_index_last_launch(ix_, &g, &w));
+    check(alaya_index_last_plan(ix_, &lds, &hl, &c, &pc, &sc));
+    py::dict d;
+    d["workgroups"] = g;
+    d["waves_per_group"] = w;
+    d["lds_bytes"] = lds;
+    d["hash_log2"] = hl;
+    d["compact"] = c != 0;
+    d["groups_per_cu"] = pc;
+    d["scout"] = sc;
+    return d;
+  }
   // SQ8 batch_search rerank: 1 = the reference's PyIndex::rerank (default), 2 = corrected (whole ef pool)
   void set_rerank_mode(int m) {
     if (m != 1 && m != 2) throw std::invalid_argument("rerank mode must be 1 (reference) or 2 (corrected)");
@@ -909,6 +928,25 @@ class DeviceIndex {
     check(alaya_index_screen_stats(ix_, &a, &b));
     return py::make_tuple(a, b);
   }
+  py::tuple scout_stats() {
+    uint64_t e = 0, h = 0, r = 0, m = 0;
+    check(alaya_index_scout_stats(ix_, &e, &h, &r, &m));
+    return py::make_tuple(e, h, r, m);
+  }
+  py::dict last_plan() {
+    uint32_t g = 0, w = 0, lds = 0, hl = 0, c = 0, pc = 0, sc = 0;
+    check(alaya_index_last_launch(ix_, &g, &w));
+    check(alaya_index_last_plan(ix_, &lds, &hl, &c, &pc, &sc));
+    py::dict d;
+    d["workgroups"] = g;
+    d["waves_per_group"] = w;
+    d["lds_bytes"] = lds;
+    d["hash_log2"] = hl;
+    d["compact"] = c != 0;
+    d["groups_per_cu"] = pc;
+    d["scout"] = sc;
+    return d;
+  }
   py::tuple profile_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k,
                            uint32_t ef, int space) {
     const uint64_t nq = q.shape(0);
@@ -1004,6 +1042,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("last_launch", &PyIndexInterface::last_launch)
       .def("help_stats", &PyIndexInterface::help_stats)
       .def("screen_stats", &PyIndexInterface::screen_stats)
+      .def("scout_stats", &PyIndexInterface::scout_stats)
+      .def("last_plan", &PyIndexInterface::last_plan)
       .def("set_rerank_mode", &PyIndexInterface::set_rerank_mode)
       .def("rerank_mode", &PyIndexInterface::rerank_mode)
       .def("device_distances", &PyIndexInterface::device_distances)
@@ -1034,6 +1074,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("last_launch", &DeviceIndex::last_launch)
       .def("help_stats", &DeviceIndex::help_stats)
       .def("screen_stats", &DeviceIndex::screen_stats)
+      .def("scout_stats", &DeviceIndex::scout_stats)
+      .def("last_plan", &DeviceIndex::last_plan)
       .def("flat_search", &DeviceIndex::flat_search, py::arg("queries"), py::arg("k"))
       .def("flat_search_device", &DeviceIndex::flat_search_device)
       .def("flat_diag", &DeviceIndex::flat_diag)

@@ -603,6 +603,51 @@ __device__ __forceinline__ void screen_fold(uint32_t *v, bool upper) {
   }
 }
 
+// The adjacency-order row whose sum lane l (< 32) holds after screen_dots_pass' five halving steps:
+// l's low five bits reversed.
+__device__ __forceinline__ int screen_pass_row(int lane) {
+  return ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4);
+}
+
+// One pass of screen_dots_int (below) on ids held in registers, for the scout wave, which has no LDS
+// lists: AC of the query codes and the records of the 32 rows whose ids lanes 0 .. 31 hold in `id`
+// (every one a valid row: the caller repeats one for the slots it does not need -- cache hits whose
+// sums it drops -- so the issue is branch-free).  Lane l < 32 returns the sum of row screen_pass_row(l).
+// after_issue() runs right after the pass's loads are issued.  (Kept beside screen_dots_int, not under
+// it: built on this function the one-wave screening kernels compiled to a different schedule.)
+template <int kChunks, typename Hook>
+__device__ __forceinline__ uint32_t screen_dots_pass(const SearchParams &p, const uint4 qc, uint32_t id, Hook after_issue) {
+  constexpr int kPieces = 2 * kChunks;
+  const int lane = lane_id();
+  const uint32_t rec = screen_u8_record_bytes(p.stride);
+  // a lane past the row reads the row's last piece again, against query codes that are 0: no exec
+  // mask around the loads, and every address is a wave-uniform base plus one per-lane offset
+  const uint32_t piece = kScreenU8Header + 16u * static_cast<uint32_t>(lane < kPieces ? lane : kPieces - 1);
+  uint4 y[32];
+#pragma unroll
+  for (int r = 0; r < 32; ++r) {
+    const uint8_t *rp = p.screen_u8 + static_cast<uint64_t>(read_lane(id, r)) * rec;
+    y[r] = *reinterpret_cast<const uint4 *>(rp + piece);
+  }
+  __builtin_amdgcn_sched_barrier(0);  // every load of the pass before the first dot product
+  after_issue();
+  uint32_t acc[32];
+#pragma unroll
+  for (int r = 0; r < 32; ++r) {  // loads retire in issue order: row r's sum runs while rows r + 1 .. arrive
+    uint32_t a = __builtin_amdgcn_udot4(qc.x, y[r].x, 0u, false);
+    a = __builtin_amdgcn_udot4(qc.y, y[r].y, a, false);
+    a = __builtin_amdgcn_udot4(qc.z, y[r].z, a, false);
+    acc[r] = __builtin_amdgcn_udot4(qc.w, y[r].w, a, false);
+    if ((r & 7) == 7) __builtin_amdgcn_sched_barrier(0);  // (the scheduler would start with the last rows)
+  }
+  screen_fold<1, 32>(acc, (lane & 1) != 0);
+  screen_fold<2, 16>(acc, (lane & 2) != 0);
+  screen_fold<4, 8>(acc, (lane & 4) != 0);
+  screen_fold<8, 4>(acc, (lane & 8) != 0);
+  screen_fold<16, 2>(acc, (lane & 16) != 0);
+  return acc[0] + static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, static_cast<int>(acc[0])));
+}
+
 // AC of the query codes and the records of rows ids[0 .. n) -> out[0 .. n).
 // after_issue() runs once, right after the first pass's loads are issued (see sq8_distances).
 template <int kChunks, typename Hook>

@@ -81,7 +81,8 @@ struct SearchParams {
   uint32_t help_flags;
   uint32_t memo_off;      // byte offset of a helper's memo in its wave region (0: the query vector)
   uint32_t two_waves;     // 1 = the wide-row f32 kernel at two waves per SIMD (one row per lane group):
-                          // twice the resident searchers, each with half the rows in flight
+                          // twice the resident searchers, each with half the rows in flight (0 in a scouted
+                          // launch, which runs that kernel for its registers: its second wave is the scout)
   uint32_t *help_stats;   // nullable: per searcher, (fresh distances it took from a memo, expansions
                           // with every fresh distance from the memo, rows it computed as a helper)
   // Candidate screen (search_has_screen; kModeScreen): once the pool is full, an expansion's fresh
@@ -94,7 +95,22 @@ struct SearchParams {
   const uint8_t *screen_u8;    // 8-bit: n records of screen_u8_record_bytes(stride) bytes (screen_bound.h):
                                // {e_row, lo, scale, 0} and `stride` codes
   uint32_t *screen_stats;      // per searcher: (candidates screened, candidates screened out)
+  // Scout (the two-waves screening kernels, screen == 3; search kernel "Scout"): every searcher wave has
+  // a second wave in its workgroup that computes the integer screen's bounds for the nodes the searcher
+  // will probably pop next into an LDS memo (kScoutBoardBytes after the wave regions).  Bits:
+  // kScoutOn; kScoutVerify = on a memo hit the searcher also computes its own bounds and counts the
+  // ones that differ; kScoutMiss = diagnostics: the scout answers only the request for the pop after
+  // the next, under a tag no lookup matches (every expansion falls back).
+  uint32_t scout;
+  uint32_t *scout_stats;       // per searcher: (expansions screened, memo hits, records the scout read,
+                               // verify mismatches)
 };
+constexpr uint32_t kScoutOn = 1, kScoutVerify = 2, kScoutMiss = 4;
+constexpr uint32_t kScoutSlots = 3;   // requests, and memo rows, per searcher
+constexpr uint32_t kScoutR = 32;      // adjacency positions per memo row: one pass of the integer screen
+// one searcher's board: kScoutSlots memo rows of kScoutR bounds, their tags, the requests, the state
+// word and the searcher's three counters
+constexpr size_t kScoutBoardBytes = kScoutSlots * (kScoutR * 4 + 8 + 4) + 20;
 
 // PyIndex::rerank inputs (python/include/index.hpp:450-488).  Per query the kernel rescores
 // search_ids[0 .. n_take) (row stride n_src; kEmpty entries are skipped) plus `zeros` entries of id 0

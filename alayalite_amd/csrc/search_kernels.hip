@@ -576,6 +576,164 @@ __device__ void help_siblings(const SearchParams &p, unsigned char *smem, const 
 }
 
 // --------------------------------------------------------------------------------------------
+// Scout (SearchParams::scout; the two-waves screening kernels under the integer screen).  A workgroup is
+// Ws searcher waves followed by Ws scout waves; scout wave Ws + i serves searcher i and owns nothing
+// but registers.  The searcher posts the nodes it will probably pop next -- the pool's first two
+// unchecked entries after each pop, and the merge's new next pop when that changes -- as requests on
+// its board.  The scout loads a requested node's adjacency row, drops the neighbours the searcher's
+// first-level visited table already holds (a hint: a stale answer costs bytes or a miss), runs one pass
+// of the integer screen over the others' records with its own copy of the query's codes, and writes one
+// bound per adjacency position into the request's memo row.  When the searcher pops a node whose row
+// is published it takes its fresh candidates' bounds from there and skips the screen pass.
+//
+// Why the bound is the same: screen_int_bound is a function of the query (its codes, sums, grid and
+// error, which screen_query_codes derives from L.q alone) and of one row's record, which no launch
+// writes.  It depends on neither tau, the pool nor the visited set, so the value computed early by
+// another wave has the bits the searcher would compute at the pop; everything after it -- keep, the
+// counters, the exact pass, the merge -- runs in the searcher as before.
+//
+// Protocol (all workgroup-scope relaxed atomics; the LDS performs one wave's operations in order, so
+// compiler barriers are the only fences).  The searcher keeps none of it in registers: its kernel has
+// none to spare at two waves per SIMD.
+//   * state: 0 between queries, the query's epoch (its index + 1) while L.q holds that query,
+//     kScoutDone once the searcher has no query left.  The searcher zeroes it before it overwrites L.q
+//     and sets the new epoch after, so a scout that reads the same epoch before and after reading L.q
+//     (or the requests) read them within that query.
+//   * req[0 .. 2] = the node being expanded (kEmpty once its memo row has been looked at), the next pop
+//     and the one after (kEmpty: none).  The scout answers the next pop first, and writes only into a
+//     row that answers none of the three.
+//   * tag[s] = epoch << 32 | node of the request row s answers, 0 while it is being written: the scout
+//     zeroes the tag, writes the bounds, then sets the tag; the searcher finds its row by the tag, reads
+//     its bounds and the tag again, and takes the bounds only if both reads show its (query, node).  A
+//     bound depends on nothing else, so a row answers its node for as long as the query lasts, and the
+//     epoch keeps one query's rows from the next.
+// No wave waits for another's data: a searcher never waits at all, and a scout leaves its poll loop
+// when it reads kScoutDone, which its searcher -- a wave of the same workgroup, so co-resident --
+// stores on its only way out of the query loop.
+// --------------------------------------------------------------------------------------------
+constexpr uint32_t kScoutDone = 0xffffffffu;
+constexpr uint32_t kScoutMissing = 0xffffffffu;  // a memo bound the scout did not compute (never a bound's bits: a NaN)
+constexpr uint64_t kScoutNoMatch = 1ull << 63;   // kScoutMiss: set in every tag the scout writes; no lookup has it
+struct ScoutBoard {
+  uint64_t tag[kScoutSlots];
+  uint32_t bound[kScoutSlots][kScoutR];
+  uint32_t req[kScoutSlots];
+  uint32_t state;
+  uint32_t stat[3];  // the searcher's counters: expansions that screened, memo hits, verify mismatches
+  uint32_t pad;
+};
+static_assert(sizeof(ScoutBoard) == kScoutBoardBytes && kScoutSlots == 3, "board size");
+
+__device__ __forceinline__ ScoutBoard *scout_board(const SearchParams &p, unsigned char *smem, int n_search, int i) {
+  return reinterpret_cast<ScoutBoard *>(smem + search_shared_lds_bytes(p.stride, p.sq8_order != 0) +
+                                        static_cast<size_t>(n_search) * p.wave_lds) + i;
+}
+
+template <typename T>
+__device__ __forceinline__ T lds_load(const T *a) {
+  return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+template <typename T, typename U>
+__device__ __forceinline__ void lds_store(T *a, U v) {
+  __hip_atomic_store(a, static_cast<T>(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// keeps the compiler from moving LDS accesses across it; the LDS itself keeps a wave's order
+__device__ __forceinline__ void lds_order() { asm volatile("" ::: "memory"); }
+
+__device__ __forceinline__ uint64_t scout_key(uint32_t epoch, uint32_t node) {
+  return (static_cast<uint64_t>(epoch & 0x7fffffffu) << 32) | node;
+}
+
+// The searcher's requests: lanes 0 .. 2 store (a, b, c) into req[first ..]; kEmpty = none.
+__device__ __forceinline__ void scout_post(ScoutBoard *b, int first, int n, uint32_t x0, uint32_t x1, uint32_t x2) {
+  const int lane = lane_id();
+  if (lane < n) lds_store(&b->req[first + lane], lane == 0 ? x0 : (lane == 1 ? x1 : x2));
+}
+
+// The scout wave of the searcher whose LDS region is Ls.
+template <int kChunks>
+__device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, uint32_t *stats) {
+  const int lane = lane_id();
+  const int mine = screen_pass_row(lane);           // the adjacency position lane (& 31) finishes
+  const int R = static_cast<int>(p.R);              // <= kScoutR (the plan)
+  const uint32_t rec = screen_u8_record_bytes(p.stride);
+  const bool miss = (p.scout & kScoutMiss) != 0u;
+  __builtin_amdgcn_s_setprio(0);                     // the scout fills issue slots the searchers leave free
+  ScreenQuery sq{};
+  uint32_t sq_epoch = 0u;
+  uint32_t records = 0u;
+  for (;;) {
+    const uint32_t e = read_lane(lds_load(&b->state), 0);
+    if (e == kScoutDone) break;
+    if (e == 0u) {
+      __builtin_amdgcn_s_sleep(8);
+      continue;
+    }
+    if (e != sq_epoch) {  // a new query: its codes, valid only if L.q held it all the while
+      lds_order();
+      sq = screen_query_codes<kChunks>(p, Ls.q);
+      lds_order();
+      sq_epoch = read_lane(lds_load(&b->state), 0) == e ? e : 0u;
+      continue;
+    }
+    uint32_t rq = kEmpty;
+    uint64_t tg = 0ull;
+    if (lane < static_cast<int>(kScoutSlots)) {
+      rq = lds_load(&b->req[lane]);
+      tg = lds_load(&b->tag[lane]);
+    }
+    lds_order();
+    if (read_lane(lds_load(&b->state), 0) != sq_epoch) continue;  // the requests may be another query's
+    const uint32_t u = read_lane(rq, 0), c1 = read_lane(rq, 1), c2 = read_lane(rq, 2);
+    // the rows as (query, node), whatever kScoutMiss marked them with
+    const uint64_t ku = scout_key(e, u), k1 = scout_key(e, c1), k2 = scout_key(e, c2);
+    tg &= ~kScoutNoMatch;
+    const bool have1 = ballot(tg == k1) != 0ull, have2 = ballot(tg == k2) != 0ull;
+    // the next pop before the one after (kScoutMiss: only ever the one after)
+    uint32_t node = kEmpty;
+    if (!miss && c1 != kEmpty && !have1) {
+      node = c1;
+    } else if (c2 != kEmpty && !have2) {
+      node = c2;
+    }
+    // a row that answers none of the three requests; none: the searcher has yet to look at u's
+    const uint64_t spare = ballot(lane < static_cast<int>(kScoutSlots) && tg != ku && tg != k1 && tg != k2);
+    if (node == kEmpty || spare == 0ull) {
+      __builtin_amdgcn_s_sleep(8);  // ~512 cycles: polls stay off the searcher's LDS
+      continue;
+    }
+    const int row = __ffsll(static_cast<unsigned long long>(spare)) - 1;
+    // lanes 0 .. 31 take one adjacency position each, the one whose sum the pass leaves them
+    const uint32_t v = lane < R ? p.l0[static_cast<uint64_t>(node) * p.R + lane] : kEmpty;
+    const uint64_t endm = ballot(lane < R && v == kEmpty);
+    const int cnt = endm ? __ffsll(static_cast<unsigned long long>(endm)) - 1 : R;
+    bool want = lane < cnt;
+    want = want && !sibling_visited<0>(p, Ls, 0, v, want);
+    const uint64_t wm = ballot(want);
+    if (lane == 0) lds_store(&b->tag[row], 0ull);
+    lds_order();
+    uint32_t lb_bits = kScoutMissing;
+    if (wm != 0ull) {
+      const uint32_t v0 = read_lane(v, __ffsll(static_cast<unsigned long long>(wm)) - 1);
+      const uint32_t id = want ? v : v0;  // an unwanted slot repeats the first wanted row
+      const uint32_t idm = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(mine << 2, static_cast<int>(id)));
+      const uint8_t *rp = p.screen_u8 + static_cast<uint64_t>(idm) * rec;
+      const float4 head = *reinterpret_cast<const float4 *>(rp);
+      const uint2 sums = *reinterpret_cast<const uint2 *>(rp + screen_u8_sums_offset(p.stride));
+      const uint32_t ac = screen_dots_pass<kChunks>(p, sq.codes, id, NoHook());
+      const float lb = screen_int_bound(p.stride, sq.err, sq.lo, sq.scale, sq.a1, sq.a2, head.x, head.y, head.z, sums.x,
+                                        sums.y, ac);
+      if ((wm >> mine) & 1ull) lb_bits = __float_as_uint(lb);
+      records += static_cast<uint32_t>(__popcll(wm));
+    }
+    if (lane < 32 && mine < R) lds_store(&b->bound[row][mine], lb_bits);
+    lds_order();
+    if (lane == 0) lds_store(&b->tag[row], scout_key(e, node) | (miss ? kScoutNoMatch : 0ull));
+  }
+  if (stats != nullptr && lane == 0) stats[2] = records;
+}
+
+// --------------------------------------------------------------------------------------------
 // The search kernel.
 // --------------------------------------------------------------------------------------------
 // kMode is a set of the kMode* bits of search_variants.h, which also lists the instantiations.
@@ -602,7 +760,32 @@ __global__ void __launch_bounds__(256)
   uint32_t n_screened = 0, n_screened_out = 0;  // wave-uniform, over the searcher's queries
   const int lane = lane_id();
   const int wave = static_cast<int>(threadIdx.x >> 6);
-  const int W = static_cast<int>(blockDim.x >> 6);
+  // Scout (p.scout, wave-uniform, the two-waves screening kernels only): the workgroup's upper half are
+  // scout waves, one per searcher wave.  The roles part here, before any per-query state exists; no
+  // workgroup barrier runs after it.
+  constexpr bool kScout = kScreen && (kMode & kModeTwoWaves) != 0;
+  const bool scouting = kScout && p.scout != 0u;
+  const int W = static_cast<int>(blockDim.x >> 6) >> (scouting ? 1 : 0);  // searcher waves
+  ScoutBoard *sboard = nullptr;
+  if constexpr (kScout) {
+    if (scouting) {
+      sboard = scout_board(p, smem, W, wave < W ? wave : wave - W);
+      if (wave < W && lane < static_cast<int>(kScoutSlots)) {
+        sboard->req[lane] = kEmpty;
+        sboard->tag[lane] = 0ull;
+        sboard->stat[lane] = 0u;
+        sboard->state = 0u;
+      }
+      __syncthreads();
+      if (wave >= W) {
+        const uint64_t sslot = static_cast<uint64_t>(blockIdx.x) * W + (wave - W);
+        scout_loop<kChunks>(p, carve_lds<kSpace>(p, smem, wave - W), sboard,
+                            p.scout_stats != nullptr ? p.scout_stats + 4 * sslot : nullptr);
+        return;
+      }
+      __builtin_amdgcn_s_setprio(2);  // the searcher's chain issues ahead of the scout that shares its SIMD
+    }
+  }
   const Lds L = carve_lds<kSpace>(p, smem, wave);
   fill_shared<kSpace>(p, L);
   HelpBoard *board = kHelp ? help_board(p, smem, W) : nullptr;
@@ -616,7 +799,7 @@ __global__ void __launch_bounds__(256)
     mine.memo_wave = -1;
   }
   const uint64_t bit_words = (p.n + 31) / 32;
-  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + wave;
+  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * W + wave;
   uint32_t *slot_bits = p.overflow_bits + slot * bit_words;
   uint32_t *slot_dirty = p.dirty_words + slot * p.dirty_cap;
   // spill tables only in the AVX-512-order SQ8 kernels (a compile-time null elsewhere: the f32
@@ -639,6 +822,13 @@ __global__ void __launch_bounds__(256)
     // a memo entry belongs to the query it was requested in: requests of an earlier query never
     // match again (the seq only grows, and the requests are dropped here)
     if constexpr (kHelp) mine_reset(board, wave, mine);
+    if constexpr (kScout) {
+      if (scouting) {  // between queries: L.q is about to change, and no request of the last query stays
+        if (lane == 0) lds_store(&sboard->state, 0u);
+        lds_order();
+        scout_post(sboard, 0, 3, kEmpty, kEmpty, kEmpty);
+      }
+    }
 
     uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_prev = kStamp ? __builtin_readcyclecounter() : 0;
@@ -657,6 +847,12 @@ __global__ void __launch_bounds__(256)
     ScreenQuery sq{};  // the integer screen's view of the query (p.screen == 3), in registers
     if constexpr (kScreen) {
       if (p.screen == 3) sq = screen_query_codes<kChunks>(p, L.q);
+    }
+    if constexpr (kScout) {
+      if (scouting) {  // L.q holds this query until the next one zeroes the state
+        lds_order();
+        if (lane == 0) lds_store(&sboard->state, qi + 1u);
+      }
     }
 
     // ---- best-first expansion (graph_search_job.hpp:228-252 / 310-330) -----------------------
@@ -679,8 +875,13 @@ __global__ void __launch_bounds__(256)
     uint64_t pre_lo = 0ull, pre_hi = 0ull;
     while (ps.cur < ps.size) {
       uint32_t c1 = kEmpty, c2 = kEmpty;
-      const uint32_t u = pool_pop<kHelp>(ps, L, &c1, &c2);
+      const uint32_t u = pool_pop<kHelp || kScout>(ps, L, &c1, &c2);
       ++n_expand;
+      // scout: this node (its memo row stays until it is read at the screen) and the next two pops as
+      // the pool stands now -- once the pool is full: nothing is screened before
+      if constexpr (kScout) {
+        if (scouting && ps.size == ps.ef) scout_post(sboard, 0, 3, u, c1, c2);
+      }
       // helpers present: the request for this node (if any; its memo is read in the distance phase)
       // and requests for the next two expansions as the pool stands now
       uint32_t look = 0u;  // (seq << 2) | slot
@@ -766,6 +967,28 @@ __global__ void __launch_bounds__(256)
       // distances a helper already computed for this node's row (exact: the same function of the same
       // query and row) go straight to cd; the rest are computed here, the known ones standing in the
       // list as kEmpty (distance functions skip them)
+      // scout: the bounds of this node's neighbours, if a memo row is published for it -- tag, bounds,
+      // tag again (see "Scout"); a fresh lane reads its own adjacency position and hands the bound to
+      // the lane that will hold the candidate.  One bound missing: today's pass for the whole list.
+      bool memo_ok = false;
+      if constexpr (kScout) {
+        if (scouting && ps.size == ps.ef && p.screen == 3) {
+          const uint64_t key = scout_key(qi + 1u, u);
+          uint64_t tg = 0ull;
+          if (lane < static_cast<int>(kScoutSlots)) tg = lds_load(&sboard->tag[lane]);
+          const uint64_t rows = ballot(tg == key);
+          if (rows != 0ull) {
+            const int row = __ffsll(static_cast<unsigned long long>(rows)) - 1;
+            lds_order();
+            const uint32_t mb = lds_load(&sboard->bound[row][lane & static_cast<int>(kScoutR - 1)]);
+            lds_order();
+            const uint64_t again = lds_load(&sboard->tag[row]);
+            memo_ok = ballot(again != key || (fresh && (mb == kScoutMissing || lane >= static_cast<int>(kScoutR)))) == 0ull;
+            if (memo_ok && fresh) L.cd[slot] = __uint_as_float(mb);
+          }
+          if (lane == 0) lds_store(&sboard->req[0], kEmpty);  // looked at: the scout may reuse u's row
+        }
+      }
       const uint32_t *dist_ids = L.cid;
       bool compute = true;
       if constexpr (kHelp) {
@@ -825,7 +1048,24 @@ __global__ void __launch_bounds__(256)
           const uint32_t c = in ? L.cid[lane] : 0u;
           float e_row = 0.f;
           float lb3 = 0.f;  // p.screen == 3: the bound itself
-          if (p.screen == 3) {  // wave-uniform: the 8-bit records under the integer dot product
+          if (p.screen == 3 && kScout && memo_ok) {  // wave-uniform: the scout's bounds (written to cd above)
+            lb3 = L.cd[lane];  // (past the list: a stale word, a bound nobody reads)
+            if (lane == 0) sboard->stat[0] += 1u, sboard->stat[1] += 1u;
+            if (p.scout & kScoutVerify) {  // diagnostics: the searcher's own bounds must have the same bits
+              const uint8_t *rp = p.screen_u8 + static_cast<uint64_t>(c) * screen_u8_record_bytes(p.stride);
+              const float4 head = *reinterpret_cast<const float4 *>(rp);
+              const uint2 sums = *reinterpret_cast<const uint2 *>(rp + screen_u8_sums_offset(p.stride));
+              wave_sync();  // (every lane has read its memo bound from cd)
+              screen_dots_int<kChunks>(p, sq.codes, L.cid, nf, reinterpret_cast<uint32_t *>(L.cd), NoHook());
+              const float own = screen_int_bound(p.stride, sq.err, sq.lo, sq.scale, sq.a1, sq.a2, head.x, head.y, head.z,
+                                                 sums.x, sums.y, __float_as_uint(L.cd[lane]));
+              const uint32_t bad = static_cast<uint32_t>(__popcll(ballot(in && __float_as_uint(own) != __float_as_uint(lb3))));
+              if (lane == 0 && bad != 0u) sboard->stat[2] += bad;
+            }
+          } else if (p.screen == 3) {  // wave-uniform: the 8-bit records under the integer dot product
+            if constexpr (kScout) {
+              if (scouting && lane == 0) sboard->stat[0] += 1u;
+            }
             // The lane's record header and code sums go out ahead of the pass's loads, in straight-line
             // code (a lane past the list reads row 0's): under `if (in)` the compiler joined this block
             // with the bound's and waited for both loads, two round trips, before the pass was issued.
@@ -893,6 +1133,9 @@ __global__ void __launch_bounds__(256)
           if constexpr (kHelp) {  // the new next pop, keeping the old one's request (likely the one after)
             if (mine.memo_wave >= 0) mine_request(board, wave, mine, kEmpty, nx, old_pred);
           }
+          if constexpr (kScout) {  // the same for the scout
+            if (scouting && ps.size == ps.ef) scout_post(sboard, 1, 2, nx, old_pred, kEmpty);
+          }
         }
       }
 #ifdef ALAYA_FINE_STAMPS
@@ -916,6 +1159,16 @@ __global__ void __launch_bounds__(256)
       p.help_stats[3 * slot] = board->own[wave].hits;
       p.help_stats[3 * slot + 1] = board->own[wave].skips;
       p.help_stats[3 * slot + 2] = board->own[wave].rows;
+    }
+  }
+  if constexpr (kScout) {
+    if (scouting) {  // the only way out of the query loop: the scout leaves its poll loop
+      if (lane == 0) lds_store(&sboard->state, kScoutDone);
+      if (p.scout_stats != nullptr && lane == 0) {  // (the scout writes word 2, the records it read)
+        p.scout_stats[4 * slot] = sboard->stat[0];
+        p.scout_stats[4 * slot + 1] = sboard->stat[1];
+        p.scout_stats[4 * slot + 3] = sboard->stat[2];
+      }
     }
   }
   if constexpr (kScreen) {  // every searcher of the launch writes its slot

@@ -313,6 +313,24 @@ int alaya_search_variant_at(uint32_t index, int *space, uint32_t *chunks, uint32
 /* The last graph search's launch shape: persistent workgroups and searchers (waves) per workgroup --
  * workgroups x waves is the number of queries the launch runs at once (introspection). */
 int alaya_index_last_launch(const alaya_index *ix, uint32_t *workgroups, uint32_t *waves_per_group);
+/* The rest of that launch's plan: LDS bytes per workgroup, the first-level visited table (log2 slots;
+ * compact: 1 = 16-bit slots), resident workgroups per CU, and the scout flags (below; 0 = no scouts). */
+int alaya_index_last_plan(const alaya_index *ix, uint32_t *lds_bytes, uint32_t *hash_log2, uint32_t *compact,
+                          uint32_t *groups_per_cu, uint32_t *scout);
+/* Scout of the screened graph search at d = 768 / 960 (L2, integer screen): in a batch that leaves the
+ * second wave per SIMD idle, every searcher wave gets a scout wave in its workgroup, which computes the
+ * screen's bounds for the neighbours of the nodes the searcher will probably pop next; the searcher
+ * takes them at the pop and skips its screen pass, or runs it as before when they are not there.
+ * alaya_index_last_launch then reports two waves per searcher.  Environment ALAYA_SEARCH_SCOUT, read per
+ * launch: 0 = off, 1 = on, 2 = on and every hit checked against the searcher's own bounds, unset = the
+ * width's default; ALAYA_SEARCH_SCOUT_MISS=1 (diagnostics) lets no answer match, and
+ * ALAYA_SEARCH_SCOUT_GRID=n (diagnostics) holds a scouted launch to n workgroups, so each searcher and
+ * its scout run several queries one after the other.  Results and counters
+ * never depend on either.  alaya_index_scout_stats: of the last graph search, summed over its searchers,
+ * the expansions that screened, those that took the scout's bounds, the records the scouts read, and
+ * the bounds the check found different (waits for that search; zeros when it had no scouts). */
+int alaya_index_scout_stats(alaya_index *ix, uint64_t *expansions, uint64_t *hits, uint64_t *records,
+                            uint64_t *mismatches);
 int alaya_index_info(const alaya_index *ix, uint64_t *n, uint32_t *dim, uint32_t *stride,
                      int *metric, uint64_t *device_bytes);
 
