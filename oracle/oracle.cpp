@@ -202,6 +202,17 @@ struct Pool {
   void vis_set(uint32_t v) { vis[v >> 6] |= 1ull << (v & 63); }
 };
 
+// The k results of a search over a pool of ef entries.  With k > ef the reference reads past the
+// pool (slot ef holds the last dropped neighbour, beyond it is out of bounds: query_utils.hpp:238,
+// graph_search_job.hpp:254-256); the engine defines it, and so does this restatement: the first ef
+// slots are the pool (value-initialised past its size), the rest are (id 0, distance 0.0).
+void pool_results(const Pool &pool, uint32_t k, uint32_t ef, uint32_t *ids, float *dists) {
+  for (uint32_t i = 0; i < k; ++i) {
+    ids[i] = i < ef ? pool.id(i) : 0u;
+    if (dists) dists[i] = i < ef ? pool.data[i].dist : 0.0f;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // QueryComputer (raw_space.hpp:255-305): FLT_MAX for invalid rows, else dist(query, row).
 // COS queries are normalised by the caller (the reference normalises the caller's buffer).
@@ -311,10 +322,7 @@ Task search_coro(const orc_index *ix, const float *query, uint32_t k, uint32_t e
       pool.insert(v, d);
     }
   }
-  for (uint32_t i = 0; i < k; ++i) {
-    ids[i] = pool.id(i);
-    if (dists) dists[i] = pool.data[i].dist;
-  }
+  pool_results(pool, k, ef, ids, dists);
   co_return;
 }
 
@@ -504,10 +512,7 @@ void orc_search(const orc_index *ix, const float *query, uint32_t k, uint32_t ef
       pool.insert(v, d);
     }
   }
-  for (uint32_t i = 0; i < k; ++i) {
-    ids[i] = pool.id(i);
-    if (dists) dists[i] = pool.data[i].dist;
-  }
+  pool_results(pool, k, ef, ids, dists);
 }
 
 double orc_batch_search_coro(const orc_index *ix, const float *queries, uint64_t nq, uint32_t k,
