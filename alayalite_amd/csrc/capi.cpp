@@ -157,6 +157,8 @@ struct alaya_index {
   uint32_t last_lds = 0, last_hash_log2 = 0, last_compact = 0, last_per_cu = 0, last_scout = 0;
   DevBuf scout_stats;
   uint64_t scout_stats_slots = 0;   // searchers of the last launch, 0 = it had no scouts
+  DevBuf scout_policy_stats;        // (the same slots)
+  uint32_t last_scout_policy = 0;   // SearchParams::scout_policy of the last launch
   int visited_mode_override = 0;  // 0 auto, 1 compact 16-bit slots, 2 wide 32-bit slots,
                                   // 3 compact with probes capped at 2 (exercises the probe spill)
   int num_cus = 0;
@@ -524,6 +526,23 @@ uint32_t scout_requested(uint32_t dim) {
   return f;
 }
 
+// ALAYA_SEARCH_SCOUT_POLICY (a mask of kScoutEarly = 1 and kScoutRecheck = 2; unset =
+// scout_policy_default) as SearchParams::scout_policy of a scouted launch.
+// Default per width: the bits that measured faster on MI355X by the project's rule -- the early
+// request against the same launch without it, the second look beside the early request against the
+// early request alone (on its own it returns a fifth of the scouts' records and no time) -- at d = 960
+// and d = 768 alike (profiles/r12/README.md, DESIGN.md section 3, "Round 12").
+uint32_t scout_policy_default(uint32_t dim) {
+  return (dim == 768 || dim == 960) ? (alaya_amd::kScoutEarly | alaya_amd::kScoutRecheck) : 0u;
+}
+
+uint32_t scout_policy_requested(uint32_t dim) {
+  const char *e = std::getenv("ALAYA_SEARCH_SCOUT_POLICY");
+  if (!(e && e[0])) return scout_policy_default(dim);
+  return static_cast<uint32_t>(std::strtoul(e, nullptr, 0)) &
+         (alaya_amd::kScoutEarly | alaya_amd::kScoutRecheck);
+}
+
 // Resolves the request and sizes the launch for the kernel it got, so a feature that has no kernel
 // for this shape is planned as absent: sets p.help / p.two_waves / p.screen, the visited table
 // (p.hash_log2, p.vis_*), p.wave_lds and p.memo_off.  A stamped call whose shape has no stamped
@@ -586,6 +605,7 @@ SearchPlan plan_search(alaya_index *ix, SearchParams &p, alaya_amd::SearchReques
   // costing a resident workgroup, and the batch runs in one round (a larger batch's second wave per
   // SIMD belongs to another searcher).  Otherwise the plan stands as it is: never half on.
   p.scout = 0u;
+  p.scout_policy = 0u;
   const uint32_t scout = scout_requested(ix->dim);
   if (scout != 0u && p.screen == 3u && !p.ip && !p.two_waves && !p.help && plan.W == 1 && ix->R <= kScoutR &&
       (plan.variant->mode & ~kModeScreen) == 0 && search_has_two_waves(ix->dim, p.sq8_order, ix->generic) &&
@@ -601,6 +621,7 @@ SearchPlan plan_search(alaya_index *ix, SearchParams &p, alaya_amd::SearchReques
       plan.variant = &v2;
       plan.lds = lds2;
       p.scout = scout;
+      p.scout_policy = scout_policy_requested(ix->dim);
       // diagnostics (ALAYA_SEARCH_SCOUT_GRID, include/alaya_hip.h): fewer workgroups than queries, so every
       // searcher -- and its scout -- runs several queries of the launch, one after the other
       if (const char *e = std::getenv("ALAYA_SEARCH_SCOUT_GRID"))
@@ -672,7 +693,10 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   if (p.scout) {
     ix->scout_stats.reserve(searchers * 16);
     p.scout_stats = ix->scout_stats.as<uint32_t>();
+    ix->scout_policy_stats.reserve(searchers * 12);
+    p.scout_policy_stats = ix->scout_policy_stats.as<uint32_t>();
   }
+  ix->last_scout_policy = p.scout_policy;
   ix->help_stats_slots = p.help ? searchers : 0;
   if (p.help) {
     ix->help_stats.reserve(searchers * 12);
@@ -2284,6 +2308,25 @@ int alaya_index_scout_stats(alaya_index *ix, uint64_t *expansions, uint64_t *hit
     if (hits) *hits = t[1];
     if (records) *records = t[2];
     if (mismatches) *mismatches = t[3];
+  });
+}
+
+int alaya_index_scout_policy_stats(alaya_index *ix, uint32_t *policy, uint64_t *early_posts, uint64_t *confirmed,
+                                   uint64_t *abandoned) {
+  return guarded_scratch(ix, [&] {
+    if (!ix) throw ArgError("null index");
+    uint64_t t[3] = {0, 0, 0};
+    if (ix->scout_stats_slots && (early_posts || confirmed || abandoned)) {  // (the mask alone: no wait)
+      set_device(ix);
+      scratch_drain(ix);
+      std::vector<uint32_t> h(3 * ix->scout_stats_slots);
+      hip_check(hipMemcpy(h.data(), ix->scout_policy_stats.ptr, h.size() * 4, hipMemcpyDeviceToHost), "D2H");
+      for (uint64_t i = 0; i < h.size(); ++i) t[i % 3] += h[i];
+    }
+    if (policy) *policy = ix->last_scout_policy;
+    if (early_posts) *early_posts = t[0];
+    if (confirmed) *confirmed = t[1];
+    if (abandoned) *abandoned = t[2];
   });
 }
 

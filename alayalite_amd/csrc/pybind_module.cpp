@@ -326,6 +326,16 @@ class PyIndexInterface {
     check(alaya_index_scout_stats(ix_, &e, &h, &r, &m));
     return py::make_tuple(e, h, r, m);
   }
+  py::tuple scout_policy_stats() {
+    uint64_t a = 0, c = 0, d = 0;
+    check(alaya_index_scout_policy_stats(ix_, nullptr, &a, &c, &d));
+    return py::make_tuple(a, c, d);
+  }
+  uint32_t scout_policy() {
+    uint32_t pol = 0;
+    check(alaya_index_scout_policy_stats(ix_, &pol, nullptr, nullptr, nullptr));
+    return pol;
+  }
   py::dict last_plan() {
     uint32_t g = 0, w = 0, lds = 0, hl = 0, c = 0, pc = 0, sc = 0;
     check(alaya_index_last_launch(ix_, &g, &w));
@@ -338,6 +348,7 @@ class PyIndexInterface {
     d["compact"] = c != 0;
     d["groups_per_cu"] = pc;
     d["scout"] = sc;
+    d["scout_policy"] = scout_policy();
     return d;
   }
   // SQ8 batch_search rerank: 1 = the reference's PyIndex::rerank (default), 2 = corrected (whole ef pool)
@@ -933,6 +944,16 @@ class DeviceIndex {
     check(alaya_index_scout_stats(ix_, &e, &h, &r, &m));
     return py::make_tuple(e, h, r, m);
   }
+  py::tuple scout_policy_stats() {
+    uint64_t a = 0, c = 0, d = 0;
+    check(alaya_index_scout_policy_stats(ix_, nullptr, &a, &c, &d));
+    return py::make_tuple(a, c, d);
+  }
+  uint32_t scout_policy() {
+    uint32_t pol = 0;
+    check(alaya_index_scout_policy_stats(ix_, &pol, nullptr, nullptr, nullptr));
+    return pol;
+  }
   py::dict last_plan() {
     uint32_t g = 0, w = 0, lds = 0, hl = 0, c = 0, pc = 0, sc = 0;
     check(alaya_index_last_launch(ix_, &g, &w));
@@ -945,6 +966,7 @@ class DeviceIndex {
     d["compact"] = c != 0;
     d["groups_per_cu"] = pc;
     d["scout"] = sc;
+    d["scout_policy"] = scout_policy();
     return d;
   }
   py::tuple profile_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k,
@@ -1043,6 +1065,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("help_stats", &PyIndexInterface::help_stats)
       .def("screen_stats", &PyIndexInterface::screen_stats)
       .def("scout_stats", &PyIndexInterface::scout_stats)
+      .def("scout_policy_stats", &PyIndexInterface::scout_policy_stats)
       .def("last_plan", &PyIndexInterface::last_plan)
       .def("set_rerank_mode", &PyIndexInterface::set_rerank_mode)
       .def("rerank_mode", &PyIndexInterface::rerank_mode)
@@ -1075,6 +1098,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("help_stats", &DeviceIndex::help_stats)
       .def("screen_stats", &DeviceIndex::screen_stats)
       .def("scout_stats", &DeviceIndex::scout_stats)
+      .def("scout_policy_stats", &DeviceIndex::scout_policy_stats)
       .def("last_plan", &DeviceIndex::last_plan)
       .def("flat_search", &DeviceIndex::flat_search, py::arg("queries"), py::arg("k"))
       .def("flat_search_device", &DeviceIndex::flat_search_device)

@@ -104,8 +104,18 @@ struct SearchParams {
   uint32_t scout;
   uint32_t *scout_stats;       // per searcher: (expansions screened, memo hits, records the scout read,
                                // verify mismatches)
+  // What the scout is asked and when it gives a node up (wave-uniform, 0 when scout == 0; hints both:
+  // no bound, result or counter depends on a bit).  kScoutEarly = the searcher names the likely
+  // retarget -- the screen's survivor with the smallest bound, if that bound is below the first
+  // unchecked entry's distance -- right after the screen, an exact pass and a merge before on_next can;
+  // kScoutRecheck = the scout looks at the requests again once a node's adjacency row has arrived and
+  // drops a node that is in neither.
+  uint32_t scout_policy;
+  uint32_t *scout_policy_stats;  // per searcher: (early requests, those on_next confirmed, nodes the
+                                 // scout dropped at the re-check)
 };
 constexpr uint32_t kScoutOn = 1, kScoutVerify = 2, kScoutMiss = 4;
+constexpr uint32_t kScoutEarly = 1, kScoutRecheck = 2;  // SearchParams::scout_policy
 constexpr uint32_t kScoutSlots = 3;   // requests, and memo rows, per searcher
 constexpr uint32_t kScoutR = 32;      // adjacency positions per memo row: one pass of the integer screen
 // one searcher's board: kScoutSlots memo rows of kScoutR bounds, their tags, the requests, the state

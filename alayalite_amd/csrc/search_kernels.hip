@@ -620,7 +620,7 @@ struct ScoutBoard {
   uint32_t req[kScoutSlots];
   uint32_t state;
   uint32_t stat[3];  // the searcher's counters: expansions that screened, memo hits, verify mismatches
-  uint32_t pad;
+  uint32_t pad;      // kScoutEarly's two (each stops at 0xffff): low half early requests, high half confirmed
 };
 static_assert(sizeof(ScoutBoard) == kScoutBoardBytes && kScoutSlots == 3, "board size");
 
@@ -652,16 +652,17 @@ __device__ __forceinline__ void scout_post(ScoutBoard *b, int first, int n, uint
 
 // The scout wave of the searcher whose LDS region is Ls.
 template <int kChunks>
-__device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, uint32_t *stats) {
+__device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, uint32_t *stats, uint32_t *policy_stats) {
   const int lane = lane_id();
   const int mine = screen_pass_row(lane);           // the adjacency position lane (& 31) finishes
   const int R = static_cast<int>(p.R);              // <= kScoutR (the plan)
   const uint32_t rec = screen_u8_record_bytes(p.stride);
   const bool miss = (p.scout & kScoutMiss) != 0u;
+  const bool recheck = (p.scout_policy & kScoutRecheck) != 0u;
   __builtin_amdgcn_s_setprio(0);                     // the scout fills issue slots the searchers leave free
   ScreenQuery sq{};
   uint32_t sq_epoch = 0u;
-  uint32_t records = 0u;
+  uint32_t records = 0u, abandoned = 0u;
   for (;;) {
     const uint32_t e = read_lane(lds_load(&b->state), 0);
     if (e == kScoutDone) break;
@@ -710,6 +711,20 @@ __device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, 
     bool want = lane < cnt;
     want = want && !sibling_visited<0>(p, Ls, 0, v, want);
     const uint64_t wm = ballot(want);
+    // kScoutRecheck: the adjacency row took a round trip, and the searcher may have merged, popped or
+    // retargeted meanwhile.  A node that is no longer the next pop or the one after costs its 128 B
+    // adjacency row and no record; the loop goes on with the requests as they stand now.
+    if (recheck) {
+      lds_order();
+      uint32_t rq2 = kEmpty;
+      if (lane < static_cast<int>(kScoutSlots)) rq2 = lds_load(&b->req[lane]);
+      lds_order();
+      const uint32_t e2 = read_lane(lds_load(&b->state), 0);
+      if (e2 != e || (read_lane(rq2, 1) != node && read_lane(rq2, 2) != node)) {
+        ++abandoned;
+        continue;
+      }
+    }
     if (lane == 0) lds_store(&b->tag[row], 0ull);
     lds_order();
     uint32_t lb_bits = kScoutMissing;
@@ -731,6 +746,7 @@ __device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, 
     if (lane == 0) lds_store(&b->tag[row], scout_key(e, node) | (miss ? kScoutNoMatch : 0ull));
   }
   if (stats != nullptr && lane == 0) stats[2] = records;
+  if (policy_stats != nullptr && lane == 0) policy_stats[2] = abandoned;
 }
 
 // --------------------------------------------------------------------------------------------
@@ -765,6 +781,7 @@ __global__ void __launch_bounds__(256)
   // workgroup barrier runs after it.
   constexpr bool kScout = kScreen && (kMode & kModeTwoWaves) != 0;
   const bool scouting = kScout && p.scout != 0u;
+  const bool early = scouting && p.screen == 3 && (p.scout_policy & kScoutEarly) != 0u;
   const int W = static_cast<int>(blockDim.x >> 6) >> (scouting ? 1 : 0);  // searcher waves
   ScoutBoard *sboard = nullptr;
   if constexpr (kScout) {
@@ -775,12 +792,14 @@ __global__ void __launch_bounds__(256)
         sboard->tag[lane] = 0ull;
         sboard->stat[lane] = 0u;
         sboard->state = 0u;
+        sboard->pad = 0u;
       }
       __syncthreads();
       if (wave >= W) {
         const uint64_t sslot = static_cast<uint64_t>(blockIdx.x) * W + (wave - W);
         scout_loop<kChunks>(p, carve_lds<kSpace>(p, smem, wave - W), sboard,
-                            p.scout_stats != nullptr ? p.scout_stats + 4 * sslot : nullptr);
+                            p.scout_stats != nullptr ? p.scout_stats + 4 * sslot : nullptr,
+                            p.scout_policy_stats != nullptr ? p.scout_policy_stats + 3 * sslot : nullptr);
         return;
       }
       __builtin_amdgcn_s_setprio(2);  // the searcher's chain issues ahead of the scout that shares its SIMD
@@ -1091,6 +1110,28 @@ __global__ void __launch_bounds__(256)
           nd = __popcll(km);
           n_screened += static_cast<uint32_t>(nf);
           n_screened_out += static_cast<uint32_t>(nf - nd);
+          // kScoutEarly: a survivor whose distance comes out below the first unchecked entry's is the
+          // next pop, and on_next names it only after the exact pass and most of the merge.  The
+          // survivor with the smallest bound (none = 0 = smallest) is the likely one: if its bound is
+          // below that entry's distance it is requested now, the entry itself as the pop after.  A
+          // hint like every request: a wrong one costs the scout a row, and on_next still posts what
+          // the merge finds.
+          if constexpr (kScout) {
+            if (early && nd > 0 && ps.cur < ps.size) {
+              const uint32_t kb = keep ? (lb3 > 0.f ? __float_as_uint(lb3) : 0u) : 0xffffffffu;
+              uint32_t mn = min(kb, lane_xor<1>(kb));
+              mn = min(mn, lane_xor<2>(mn));
+              mn = min(mn, lane_xor<4>(mn));
+              mn = min(mn, lane_xor<8>(mn));
+              mn = min(mn, lane_xor<16>(mn));
+              mn = min(read_lane(mn, 0), read_lane(mn, 32));
+              if (__uint_as_float(mn) < L.pd[ps.cur]) {
+                const uint32_t cand = read_lane(c, __ffsll(static_cast<unsigned long long>(ballot(kb == mn))) - 1);
+                scout_post(sboard, 1, 2, cand, pred, kEmpty);
+                if (lane == 0 && (sboard->pad & 0xffffu) != 0xffffu) sboard->pad += 1u;
+              }
+            }
+          }
           // (every lane read its id before screen_distances' closing wave_sync)
           if (keep) L.cid[__popcll(km & ((1ull << lane) - 1ull))] = c;
           wave_sync();
@@ -1134,7 +1175,13 @@ __global__ void __launch_bounds__(256)
             if (mine.memo_wave >= 0) mine_request(board, wave, mine, kEmpty, nx, old_pred);
           }
           if constexpr (kScout) {  // the same for the scout
-            if (scouting && ps.size == ps.ef) scout_post(sboard, 1, 2, nx, old_pred, kEmpty);
+            if (scouting && ps.size == ps.ef) {
+              // (an early request that named nx: req[1] holds nx only then, the pop's own post was pred)
+              if (early && lane == 0 && lds_load(&sboard->req[1]) == nx &&
+                  (sboard->pad >> 16) != 0xffffu)
+                sboard->pad += 0x10000u;
+              scout_post(sboard, 1, 2, nx, old_pred, kEmpty);
+            }
           }
         }
       }
@@ -1168,6 +1215,10 @@ __global__ void __launch_bounds__(256)
         p.scout_stats[4 * slot] = sboard->stat[0];
         p.scout_stats[4 * slot + 1] = sboard->stat[1];
         p.scout_stats[4 * slot + 3] = sboard->stat[2];
+      }
+      if (p.scout_policy_stats != nullptr && lane == 0) {  // (the scout writes word 2, the nodes it dropped)
+        p.scout_policy_stats[3 * slot] = sboard->pad & 0xffffu;
+        p.scout_policy_stats[3 * slot + 1] = sboard->pad >> 16;
       }
     }
   }

@@ -331,6 +331,17 @@ int alaya_index_last_plan(const alaya_index *ix, uint32_t *lds_bytes, uint32_t *
  * the bounds the check found different (waits for that search; zeros when it had no scouts). */
 int alaya_index_scout_stats(alaya_index *ix, uint64_t *expansions, uint64_t *hits, uint64_t *records,
                             uint64_t *mismatches);
+/* What a scouted launch asks of its scouts: environment ALAYA_SEARCH_SCOUT_POLICY, read per launch, a mask
+ * of 1 = the searcher requests the likely next pop right after the screen (the survivor with the
+ * smallest bound, if below the first unchecked entry's distance) and 2 = the scout looks at the
+ * requests again when a node's adjacency row has arrived and drops a node that is in neither; other
+ * bits are ignored, unset = the width's default.  Ignored without scouts.  Results and counters never
+ * depend on it.  alaya_index_scout_policy_stats: the mask the last graph search ran with (0 = no
+ * scouts; no wait if only the mask is asked for) and, summed over its searchers, the early requests,
+ * those the merge confirmed and the nodes dropped at the second look (waits for that search; zeros
+ * when it had no scouts). */
+int alaya_index_scout_policy_stats(alaya_index *ix, uint32_t *policy, uint64_t *early_posts, uint64_t *confirmed,
+                                   uint64_t *abandoned);
 int alaya_index_info(const alaya_index *ix, uint64_t *n, uint32_t *dim, uint32_t *stride,
                      int *metric, uint64_t *device_bytes);
 
