@@ -2292,18 +2292,25 @@ int alaya_index_last_plan(const alaya_index *ix, uint32_t *lds_bytes, uint32_t *
   });
 }
 
+// The sums, per word, of a per-searcher counter buffer of the last search (`words` 32-bit words for
+// each of `searchers`): waits for the index's stream, then copies the buffer to the host.
+static std::vector<uint64_t> searcher_stats(alaya_index *ix, const DevBuf &buf, uint64_t searchers, uint32_t words) {
+  std::vector<uint64_t> t(words, 0);
+  if (searchers) {
+    set_device(ix);
+    scratch_drain(ix);
+    std::vector<uint32_t> h(words * searchers);
+    hip_check(hipMemcpy(h.data(), buf.ptr, h.size() * 4, hipMemcpyDeviceToHost), "D2H");
+    for (uint64_t i = 0; i < h.size(); ++i) t[i % words] += h[i];
+  }
+  return t;
+}
+
 int alaya_index_scout_stats(alaya_index *ix, uint64_t *expansions, uint64_t *hits, uint64_t *records,
                             uint64_t *mismatches) {
   return guarded_scratch(ix, [&] {
     if (!ix) throw ArgError("null index");
-    uint64_t t[4] = {0, 0, 0, 0};
-    if (ix->scout_stats_slots) {
-      set_device(ix);
-      scratch_drain(ix);
-      std::vector<uint32_t> h(4 * ix->scout_stats_slots);
-      hip_check(hipMemcpy(h.data(), ix->scout_stats.ptr, h.size() * 4, hipMemcpyDeviceToHost), "D2H");
-      for (uint64_t i = 0; i < h.size(); ++i) t[i & 3] += h[i];
-    }
+    const std::vector<uint64_t> t = searcher_stats(ix, ix->scout_stats, ix->scout_stats_slots, 4);
     if (expansions) *expansions = t[0];
     if (hits) *hits = t[1];
     if (records) *records = t[2];
@@ -2315,14 +2322,8 @@ int alaya_index_scout_policy_stats(alaya_index *ix, uint32_t *policy, uint64_t *
                                    uint64_t *abandoned) {
   return guarded_scratch(ix, [&] {
     if (!ix) throw ArgError("null index");
-    uint64_t t[3] = {0, 0, 0};
-    if (ix->scout_stats_slots && (early_posts || confirmed || abandoned)) {  // (the mask alone: no wait)
-      set_device(ix);
-      scratch_drain(ix);
-      std::vector<uint32_t> h(3 * ix->scout_stats_slots);
-      hip_check(hipMemcpy(h.data(), ix->scout_policy_stats.ptr, h.size() * 4, hipMemcpyDeviceToHost), "D2H");
-      for (uint64_t i = 0; i < h.size(); ++i) t[i % 3] += h[i];
-    }
+    const bool sums = early_posts || confirmed || abandoned;  // (the mask alone: no wait)
+    const std::vector<uint64_t> t = searcher_stats(ix, ix->scout_policy_stats, sums ? ix->scout_stats_slots : 0, 3);
     if (policy) *policy = ix->last_scout_policy;
     if (early_posts) *early_posts = t[0];
     if (confirmed) *confirmed = t[1];
@@ -2341,21 +2342,10 @@ int alaya_index_set_helpers(alaya_index *ix, int mode) {
 int alaya_index_help_stats(alaya_index *ix, uint64_t *memo_dists, uint64_t *memo_expansions, uint64_t *helper_rows) {
   return guarded_scratch(ix, [&] {
     if (!ix) throw ArgError("null index");
-    uint64_t m = 0, x = 0, r = 0;
-    if (ix->help_stats_slots) {
-      set_device(ix);
-      scratch_drain(ix);
-      std::vector<uint32_t> h(3 * ix->help_stats_slots);
-      hip_check(hipMemcpy(h.data(), ix->help_stats.ptr, h.size() * 4, hipMemcpyDeviceToHost), "D2H");
-      for (uint64_t i = 0; i < ix->help_stats_slots; ++i) {
-        m += h[3 * i];
-        x += h[3 * i + 1];
-        r += h[3 * i + 2];
-      }
-    }
-    if (memo_dists) *memo_dists = m;
-    if (memo_expansions) *memo_expansions = x;
-    if (helper_rows) *helper_rows = r;
+    const std::vector<uint64_t> t = searcher_stats(ix, ix->help_stats, ix->help_stats_slots, 3);
+    if (memo_dists) *memo_dists = t[0];
+    if (memo_expansions) *memo_expansions = t[1];
+    if (helper_rows) *helper_rows = t[2];
   });
 }
 
@@ -2484,19 +2474,9 @@ int alaya_search_variant_at(uint32_t index, int *space, uint32_t *chunks, uint32
 int alaya_index_screen_stats(alaya_index *ix, uint64_t *screened, uint64_t *screened_out) {
   return guarded_scratch(ix, [&] {
     if (!ix) throw ArgError("null index");
-    uint64_t a = 0, b = 0;
-    if (ix->screen_stats_slots) {
-      set_device(ix);
-      scratch_drain(ix);
-      std::vector<uint32_t> h(2 * ix->screen_stats_slots);
-      hip_check(hipMemcpy(h.data(), ix->screen_stats.ptr, h.size() * 4, hipMemcpyDeviceToHost), "D2H");
-      for (uint64_t i = 0; i < ix->screen_stats_slots; ++i) {
-        a += h[2 * i];
-        b += h[2 * i + 1];
-      }
-    }
-    if (screened) *screened = a;
-    if (screened_out) *screened_out = b;
+    const std::vector<uint64_t> t = searcher_stats(ix, ix->screen_stats, ix->screen_stats_slots, 2);
+    if (screened) *screened = t[0];
+    if (screened_out) *screened_out = t[1];
   });
 }
 

@@ -87,7 +87,63 @@ void to_float(const void *src, DType t, size_t count, float *dst) {
 // (distance_l2.ipp:694-708): the device reproduces the order this host's reference build uses.
 int host_sq8_order() { return __builtin_cpu_supports("avx512f") ? 2 : 1; }
 
-class PyIndexInterface {
+// The launch controls and the device counters of the last search, as both index classes expose them.
+class LaunchControls {
+ public:
+  void set_hash_log2(uint32_t v) { check(alaya_index_set_hash_log2(ix_, v)); }
+  void set_visited_mode(int m) { check(alaya_index_set_visited_mode(ix_, m)); }
+  void set_helpers(int m) { check(alaya_index_set_helpers(ix_, m)); }
+  py::tuple last_launch() {
+    uint32_t g = 0, w = 0;
+    check(alaya_index_last_launch(ix_, &g, &w));
+    return py::make_tuple(g, w);
+  }
+  py::tuple help_stats() {
+    uint64_t m = 0, x = 0, r = 0;
+    check(alaya_index_help_stats(ix_, &m, &x, &r));
+    return py::make_tuple(m, x, r);
+  }
+  py::tuple screen_stats() {
+    uint64_t a = 0, b = 0;
+    check(alaya_index_screen_stats(ix_, &a, &b));
+    return py::make_tuple(a, b);
+  }
+  py::tuple scout_stats() {
+    uint64_t e = 0, h = 0, r = 0, m = 0;
+    check(alaya_index_scout_stats(ix_, &e, &h, &r, &m));
+    return py::make_tuple(e, h, r, m);
+  }
+  py::tuple scout_policy_stats() {
+    uint64_t a = 0, c = 0, d = 0;
+    check(alaya_index_scout_policy_stats(ix_, nullptr, &a, &c, &d));
+    return py::make_tuple(a, c, d);
+  }
+  uint32_t scout_policy() {
+    uint32_t pol = 0;
+    check(alaya_index_scout_policy_stats(ix_, &pol, nullptr, nullptr, nullptr));
+    return pol;
+  }
+  py::dict last_plan() {
+    uint32_t g = 0, w = 0, lds = 0, hl = 0, c = 0, pc = 0, sc = 0;
+    check(alaya_index_last_launch(ix_, &g, &w));
+    check(alaya_index_last_plan(ix_, &lds, &hl, &c, &pc, &sc));
+    py::dict d;
+    d["workgroups"] = g;
+    d["waves_per_group"] = w;
+    d["lds_bytes"] = lds;
+    d["hash_log2"] = hl;
+    d["compact"] = c != 0;
+    d["groups_per_cu"] = pc;
+    d["scout"] = sc;
+    d["scout_policy"] = scout_policy();
+    return d;
+  }
+
+ protected:
+  alaya_index *ix_ = nullptr;
+};
+
+class PyIndexInterface : public LaunchControls {
  public:
   explicit PyIndexInterface(const IndexParams &params) : params_(params) {
     dtype_ = dtype_code(params_.data_type_);
@@ -302,54 +358,6 @@ class PyIndexInterface {
     py::array_t<uint32_t> out({static_cast<py::ssize_t>(last_counters_.size() / 4), static_cast<py::ssize_t>(4)});
     std::memcpy(out.mutable_data(), last_counters_.data(), last_counters_.size() * 4);
     return out;
-  }
-  void set_hash_log2(uint32_t v) { check(alaya_index_set_hash_log2(ix_, v)); }
-  void set_visited_mode(int m) { check(alaya_index_set_visited_mode(ix_, m)); }
-  void set_helpers(int m) { check(alaya_index_set_helpers(ix_, m)); }
-  py::tuple last_launch() {
-    uint32_t g = 0, w = 0;
-    check(alaya_index_last_launch(ix_, &g, &w));
-    return py::make_tuple(g, w);
-  }
-  py::tuple help_stats() {
-    uint64_t m = 0, x = 0, r = 0;
-    check(alaya_index_help_stats(ix_, &m, &x, &r));
-    return py::make_tuple(m, x, r);
-  }
-  py::tuple screen_stats() {
-    uint64_t a = 0, b = 0;
-    check(alaya_index_screen_stats(ix_, &a, &b));
-    return py::make_tuple(a, b);
-  }
-  py::tuple scout_stats() {
-    uint64_t e = 0, h = 0, r = 0, m = 0;
-    check(alaya_index_scout_stats(ix_, &e, &h, &r, &m));
-    return py::make_tuple(e, h, r, m);
-  }
-  py::tuple scout_policy_stats() {
-    uint64_t a = 0, c = 0, d = 0;
-    check(alaya_index_scout_policy_stats(ix_, nullptr, &a, &c, &d));
-    return py::make_tuple(a, c, d);
-  }
-  uint32_t scout_policy() {
-    uint32_t pol = 0;
-    check(alaya_index_scout_policy_stats(ix_, &pol, nullptr, nullptr, nullptr));
-    return pol;
-  }
-  py::dict last_plan() {
-    uint32_t g = 0, w = 0, lds = 0, hl = 0, c = 0, pc = 0, sc = 0;
-    check(alaya_index_last_launch(ix_, &g, &w));
-    check(alaya_index_last_plan(ix_, &lds, &hl, &c, &pc, &sc));
-    py::dict d;
-    d["workgroups"] = g;
-    d["waves_per_group"] = w;
-    d["lds_bytes"] = lds;
-    d["hash_log2"] = hl;
-    d["compact"] = c != 0;
-    d["groups_per_cu"] = pc;
-    d["scout"] = sc;
-    d["scout_policy"] = scout_policy();
-    return d;
   }
   // SQ8 batch_search rerank: 1 = the reference's PyIndex::rerank (default), 2 = corrected (whole ef pool)
   void set_rerank_mode(int m) {
@@ -681,7 +689,6 @@ class PyIndexInterface {
   IndexParams params_;
   DType dtype_ = kF32;
   int id_bytes_ = 4;
-  alaya_index *ix_ = nullptr;
   alaya_graph *graph_ = nullptr;
   uint64_t n_ = 0;
   uint32_t dim_ = 0;
@@ -773,7 +780,7 @@ class Graph {
 };
 
 // Raw device index: rows + graph in HBM, batch search on host arrays or device pointers.
-class DeviceIndex {
+class DeviceIndex : public LaunchControls {
  public:
   explicit DeviceIndex(int device) { check(alaya_index_create(device, &ix_)); }
   ~DeviceIndex() {
@@ -921,54 +928,6 @@ class DeviceIndex {
                                 reinterpret_cast<uint32_t *>(flags), reinterpret_cast<uint32_t *>(mc),
                                 reinterpret_cast<void *>(stream)));
   }
-  void set_hash_log2(uint32_t v) { check(alaya_index_set_hash_log2(ix_, v)); }
-  void set_visited_mode(int m) { check(alaya_index_set_visited_mode(ix_, m)); }
-  void set_helpers(int m) { check(alaya_index_set_helpers(ix_, m)); }
-  py::tuple last_launch() {
-    uint32_t g = 0, w = 0;
-    check(alaya_index_last_launch(ix_, &g, &w));
-    return py::make_tuple(g, w);
-  }
-  py::tuple help_stats() {
-    uint64_t m = 0, x = 0, r = 0;
-    check(alaya_index_help_stats(ix_, &m, &x, &r));
-    return py::make_tuple(m, x, r);
-  }
-  py::tuple screen_stats() {
-    uint64_t a = 0, b = 0;
-    check(alaya_index_screen_stats(ix_, &a, &b));
-    return py::make_tuple(a, b);
-  }
-  py::tuple scout_stats() {
-    uint64_t e = 0, h = 0, r = 0, m = 0;
-    check(alaya_index_scout_stats(ix_, &e, &h, &r, &m));
-    return py::make_tuple(e, h, r, m);
-  }
-  py::tuple scout_policy_stats() {
-    uint64_t a = 0, c = 0, d = 0;
-    check(alaya_index_scout_policy_stats(ix_, nullptr, &a, &c, &d));
-    return py::make_tuple(a, c, d);
-  }
-  uint32_t scout_policy() {
-    uint32_t pol = 0;
-    check(alaya_index_scout_policy_stats(ix_, &pol, nullptr, nullptr, nullptr));
-    return pol;
-  }
-  py::dict last_plan() {
-    uint32_t g = 0, w = 0, lds = 0, hl = 0, c = 0, pc = 0, sc = 0;
-    check(alaya_index_last_launch(ix_, &g, &w));
-    check(alaya_index_last_plan(ix_, &lds, &hl, &c, &pc, &sc));
-    py::dict d;
-    d["workgroups"] = g;
-    d["waves_per_group"] = w;
-    d["lds_bytes"] = lds;
-    d["hash_log2"] = hl;
-    d["compact"] = c != 0;
-    d["groups_per_cu"] = pc;
-    d["scout"] = sc;
-    d["scout_policy"] = scout_policy();
-    return d;
-  }
   py::tuple profile_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k,
                            uint32_t ef, int space) {
     const uint64_t nq = q.shape(0);
@@ -986,7 +945,6 @@ class DeviceIndex {
   }
 
  private:
-  alaya_index *ix_ = nullptr;
 };
 
 }  // namespace alaya_py

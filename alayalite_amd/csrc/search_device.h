@@ -57,6 +57,19 @@ __device__ __forceinline__ uint32_t read_lane(uint32_t v, int l) {
   return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), l));
 }
 
+// A node's level-0 adjacency row, one neighbour per lane (R = p.R, as the caller holds it); a lane
+// past the row gets `past`: kEmpty, or the old value of a register that is kept.
+__device__ __forceinline__ uint32_t adjacency_row(const SearchParams &p, int R, uint32_t node, uint32_t past = kEmpty) {
+  const int lane = lane_id();
+  return lane < R ? p.l0[static_cast<uint64_t>(node) * p.R + lane] : past;
+}
+
+// The neighbours in a row: up to the first kEmpty.
+__device__ __forceinline__ int adjacency_count(int R, uint32_t v) {
+  const uint64_t endm = ballot(lane_id() < R && v == kEmpty);
+  return endm ? __ffsll(static_cast<unsigned long long>(endm)) - 1 : R;
+}
+
 __device__ __forceinline__ uint32_t hash_slot(uint32_t v, uint32_t log2h) {
   return (v * 0x9E3779B1u) >> (32 - log2h);
 }

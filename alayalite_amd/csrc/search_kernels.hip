@@ -444,6 +444,23 @@ __device__ __forceinline__ uint64_t *help_memo(const SearchParams &p, unsigned c
                                       p.memo_off);
 }
 
+// n_got of an expansion's nf fresh distances came from the memo.
+__device__ __forceinline__ void help_count(HelpBoard *b, int wave, uint32_t n_got, uint32_t nf, int lane) {
+  if (lane == 0 && n_got) {
+    b->own[wave].hits += n_got;
+    if (n_got == nf) b->own[wave].skips += 1u;
+  }
+}
+
+// A searcher's help_stats row (the board outlives every wave's searching).
+__device__ __forceinline__ void help_stats_out(const SearchParams &p, const HelpBoard *b, int wave, uint64_t slot, int lane) {
+  if (p.help_stats != nullptr && lane == 0) {
+    p.help_stats[3 * slot] = b->own[wave].hits;
+    p.help_stats[3 * slot + 1] = b->own[wave].skips;
+    p.help_stats[3 * slot + 2] = b->own[wave].rows;
+  }
+}
+
 // Whether sibling t has probably visited v already (a hint: read while the sibling writes, so it may
 // be stale either way): its LDS first level, and -- SQ8 on the spill table -- its spill-table bucket.
 template <int kSpace>
@@ -544,9 +561,8 @@ __device__ void help_siblings(const SearchParams &p, unsigned char *smem, const 
       old = read_lane(old, 0);
       if ((old >> 8) != (seq & 0xffffffu)) continue;  // replaced by a newer request meanwhile
       const uint32_t pos = old & 0xffu;
-      const uint32_t v = lane < static_cast<int>(R) ? p.l0[static_cast<uint64_t>(node) * R + lane] : kEmpty;
-      const uint64_t endm = ballot(lane < static_cast<int>(R) && v == kEmpty);
-      const uint32_t cnt = endm ? static_cast<uint32_t>(__ffsll(static_cast<unsigned long long>(endm)) - 1) : R;
+      const uint32_t v = adjacency_row(p, static_cast<int>(R), node);
+      const uint32_t cnt = static_cast<uint32_t>(adjacency_count(static_cast<int>(R), v));
       if (pos >= cnt) {
         if (lane == 0) exhausted[t * kHelpSlots + s] = seq;
         wave_sync();
@@ -620,7 +636,7 @@ struct ScoutBoard {
   uint32_t req[kScoutSlots];
   uint32_t state;
   uint32_t stat[3];  // the searcher's counters: expansions that screened, memo hits, verify mismatches
-  uint32_t pad;      // kScoutEarly's two (each stops at 0xffff): low half early requests, high half confirmed
+  uint32_t early;    // kScoutEarly's two (each stops at 0xffff): low half early requests, high half confirmed
 };
 static_assert(sizeof(ScoutBoard) == kScoutBoardBytes && kScoutSlots == 3, "board size");
 
@@ -650,9 +666,117 @@ __device__ __forceinline__ void scout_post(ScoutBoard *b, int first, int n, uint
   if (lane < n) lds_store(&b->req[first + lane], lane == 0 ? x0 : (lane == 1 ? x1 : x2));
 }
 
+// ---- the searcher's side of the protocol ----
+// Before the roles part (a workgroup barrier follows): the searcher's first lanes clear its board.
+__device__ __forceinline__ void scout_board_init(ScoutBoard *b) {
+  const int lane = lane_id();
+  if (lane < static_cast<int>(kScoutSlots)) {
+    b->req[lane] = kEmpty;
+    b->tag[lane] = 0ull;
+    b->stat[lane] = 0u;
+    b->state = 0u;
+    b->early = 0u;
+  }
+}
+
+// Between queries: L.q is about to change, and no request of the last query stays.
+__device__ __forceinline__ void scout_query_end(ScoutBoard *b) {
+  if (lane_id() == 0) lds_store(&b->state, 0u);
+  lds_order();
+  scout_post(b, 0, 3, kEmpty, kEmpty, kEmpty);
+}
+
+// L.q holds the query of this epoch until the next scout_query_end.
+__device__ __forceinline__ void scout_query_begin(ScoutBoard *b, uint32_t epoch) {
+  lds_order();
+  if (lane_id() == 0) lds_store(&b->state, epoch);
+}
+
+// The bounds of node u's neighbours, if a memo row is published for it -- tag, bounds, tag again; a
+// fresh lane reads its own adjacency position and hands the bound to the lane that will hold the
+// candidate (cd[slot]).  One bound missing: false, and the searcher's own pass for the whole list.
+__device__ __forceinline__ bool scout_lookup(ScoutBoard *b, uint32_t epoch, uint32_t u, bool fresh, uint32_t slot, float *cd) {
+  const int lane = lane_id();
+  bool memo_ok = false;
+  const uint64_t key = scout_key(epoch, u);
+  uint64_t tg = 0ull;
+  if (lane < static_cast<int>(kScoutSlots)) tg = lds_load(&b->tag[lane]);
+  const uint64_t rows = ballot(tg == key);
+  if (rows != 0ull) {
+    const int row = __ffsll(static_cast<unsigned long long>(rows)) - 1;
+    lds_order();
+    const uint32_t mb = lds_load(&b->bound[row][lane & static_cast<int>(kScoutR - 1)]);
+    lds_order();
+    const uint64_t again = lds_load(&b->tag[row]);
+    memo_ok = ballot(again != key || (fresh && (mb == kScoutMissing || lane >= static_cast<int>(kScoutR)))) == 0ull;
+    if (memo_ok && fresh) cd[slot] = __uint_as_float(mb);
+  }
+  if (lane == 0) lds_store(&b->req[0], kEmpty);  // looked at: the scout may reuse u's row
+  return memo_ok;
+}
+
+// An expansion that screened, from the memo (hit) or with the searcher's own pass.
+__device__ __forceinline__ void scout_count_screen(ScoutBoard *b, bool hit) {
+  if (lane_id() == 0) {
+    b->stat[0] += 1u;
+    if (hit) b->stat[1] += 1u;
+  }
+}
+
+// kScoutEarly: a survivor whose distance comes out below the first unchecked entry's is the next pop,
+// and the merge names it only after the exact pass and most of its own work.  The survivor with the
+// smallest bound (none = 0 = smallest) is the likely one: if its bound is below that entry's distance
+// it is requested now, the entry itself (pred) as the pop after.  A hint like every request: a wrong
+// one costs the scout a row, and scout_retarget still posts what the merge finds.
+__device__ __forceinline__ void scout_early_request(ScoutBoard *b, const Lds &L, const PoolState &ps, bool keep, float lb3,
+                                                    uint32_t c, uint32_t pred) {
+  const uint32_t kb = keep ? (lb3 > 0.f ? __float_as_uint(lb3) : 0u) : 0xffffffffu;
+  uint32_t mn = min(kb, lane_xor<1>(kb));
+  mn = min(mn, lane_xor<2>(mn));
+  mn = min(mn, lane_xor<4>(mn));
+  mn = min(mn, lane_xor<8>(mn));
+  mn = min(mn, lane_xor<16>(mn));
+  mn = min(read_lane(mn, 0), read_lane(mn, 32));
+  if (__uint_as_float(mn) < L.pd[ps.cur]) {
+    const uint32_t cand = read_lane(c, __ffsll(static_cast<unsigned long long>(ballot(kb == mn))) - 1);
+    scout_post(b, 1, 2, cand, pred, kEmpty);
+    if (lane_id() == 0 && (b->early & 0xffffu) != 0xffffu) b->early += 1u;
+  }
+}
+
+// kScoutVerify: bounds of the searcher's own that did not have the bits of the memo's.
+__device__ __forceinline__ void scout_count_mismatches(ScoutBoard *b, uint32_t bad, int lane) {
+  if (lane == 0 && bad != 0u) b->stat[2] += bad;
+}
+
+// The merge found the next pop nx: requested, with the old prediction as the pop after.
+__device__ __forceinline__ void scout_retarget(ScoutBoard *b, bool early, uint32_t nx, uint32_t old_pred) {
+  // (an early request that named nx: req[1] holds nx only then, the pop's own post was pred)
+  if (early && lane_id() == 0 && lds_load(&b->req[1]) == nx && (b->early >> 16) != 0xffffu) b->early += 0x10000u;
+  scout_post(b, 1, 2, nx, old_pred, kEmpty);
+}
+
+// The searcher's only way out of the query loop: the scout leaves its poll loop.  The scout itself
+// writes word 2 of both stats rows (the records it read, the nodes it dropped).
+__device__ __forceinline__ void scout_leave(const SearchParams &p, ScoutBoard *b, uint64_t slot) {
+  const int lane = lane_id();
+  if (lane == 0) lds_store(&b->state, kScoutDone);
+  if (p.scout_stats != nullptr && lane == 0) {
+    p.scout_stats[4 * slot] = b->stat[0];
+    p.scout_stats[4 * slot + 1] = b->stat[1];
+    p.scout_stats[4 * slot + 3] = b->stat[2];
+  }
+  if (p.scout_policy_stats != nullptr && lane == 0) {
+    p.scout_policy_stats[3 * slot] = b->early & 0xffffu;
+    p.scout_policy_stats[3 * slot + 1] = b->early >> 16;
+  }
+}
+
 // The scout wave of the searcher whose LDS region is Ls.
 template <int kChunks>
-__device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, uint32_t *stats, uint32_t *policy_stats) {
+__device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, uint64_t slot) {
+  uint32_t *stats = p.scout_stats != nullptr ? p.scout_stats + 4 * slot : nullptr;
+  uint32_t *policy_stats = p.scout_policy_stats != nullptr ? p.scout_policy_stats + 3 * slot : nullptr;
   const int lane = lane_id();
   const int mine = screen_pass_row(lane);           // the adjacency position lane (& 31) finishes
   const int R = static_cast<int>(p.R);              // <= kScoutR (the plan)
@@ -705,9 +829,8 @@ __device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, 
     }
     const int row = __ffsll(static_cast<unsigned long long>(spare)) - 1;
     // lanes 0 .. 31 take one adjacency position each, the one whose sum the pass leaves them
-    const uint32_t v = lane < R ? p.l0[static_cast<uint64_t>(node) * p.R + lane] : kEmpty;
-    const uint64_t endm = ballot(lane < R && v == kEmpty);
-    const int cnt = endm ? __ffsll(static_cast<unsigned long long>(endm)) - 1 : R;
+    const uint32_t v = adjacency_row(p, R, node);
+    const int cnt = adjacency_count(R, v);
     bool want = lane < cnt;
     want = want && !sibling_visited<0>(p, Ls, 0, v, want);
     const uint64_t wm = ballot(want);
@@ -749,6 +872,15 @@ __device__ void scout_loop(const SearchParams &p, const Lds &Ls, ScoutBoard *b, 
   if (policy_stats != nullptr && lane == 0) policy_stats[2] = abandoned;
 }
 
+// A searcher's screen_stats row: every searcher of the launch writes its slot.
+__device__ __forceinline__ void screen_stats_out(const SearchParams &p, uint64_t slot, uint32_t n_screened,
+                                                 uint32_t n_screened_out, int lane) {
+  if (p.screen_stats != nullptr && lane == 0) {
+    p.screen_stats[2 * slot] = n_screened;
+    p.screen_stats[2 * slot + 1] = n_screened_out;
+  }
+}
+
 // --------------------------------------------------------------------------------------------
 // The search kernel.
 // --------------------------------------------------------------------------------------------
@@ -787,19 +919,11 @@ __global__ void __launch_bounds__(256)
   if constexpr (kScout) {
     if (scouting) {
       sboard = scout_board(p, smem, W, wave < W ? wave : wave - W);
-      if (wave < W && lane < static_cast<int>(kScoutSlots)) {
-        sboard->req[lane] = kEmpty;
-        sboard->tag[lane] = 0ull;
-        sboard->stat[lane] = 0u;
-        sboard->state = 0u;
-        sboard->pad = 0u;
-      }
+      if (wave < W) scout_board_init(sboard);
       __syncthreads();
       if (wave >= W) {
-        const uint64_t sslot = static_cast<uint64_t>(blockIdx.x) * W + (wave - W);
         scout_loop<kChunks>(p, carve_lds<kSpace>(p, smem, wave - W), sboard,
-                            p.scout_stats != nullptr ? p.scout_stats + 4 * sslot : nullptr,
-                            p.scout_policy_stats != nullptr ? p.scout_policy_stats + 3 * sslot : nullptr);
+                            static_cast<uint64_t>(blockIdx.x) * W + (wave - W));
         return;
       }
       __builtin_amdgcn_s_setprio(2);  // the searcher's chain issues ahead of the scout that shares its SIMD
@@ -842,11 +966,7 @@ __global__ void __launch_bounds__(256)
     // match again (the seq only grows, and the requests are dropped here)
     if constexpr (kHelp) mine_reset(board, wave, mine);
     if constexpr (kScout) {
-      if (scouting) {  // between queries: L.q is about to change, and no request of the last query stays
-        if (lane == 0) lds_store(&sboard->state, 0u);
-        lds_order();
-        scout_post(sboard, 0, 3, kEmpty, kEmpty, kEmpty);
-      }
+      if (scouting) scout_query_end(sboard);
     }
 
     uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -868,10 +988,7 @@ __global__ void __launch_bounds__(256)
       if (p.screen == 3) sq = screen_query_codes<kChunks>(p, L.q);
     }
     if constexpr (kScout) {
-      if (scouting) {  // L.q holds this query until the next one zeroes the state
-        lds_order();
-        if (lane == 0) lds_store(&sboard->state, qi + 1u);
-      }
+      if (scouting) scout_query_begin(sboard, qi + 1u);
     }
 
     // ---- best-first expansion (graph_search_job.hpp:228-252 / 310-330) -----------------------
@@ -927,8 +1044,10 @@ __global__ void __launch_bounds__(256)
         if (kStamp) st[7]++;
 #endif
       } else {
-        v = lane < static_cast<int>(p.R) ? p.l0[static_cast<uint64_t>(u) * p.R + lane] : kEmpty;
+        v = adjacency_row(p, static_cast<int>(p.R), u);
       }
+      // (adjacency_count, written out: through the helper the SQ8 helper kernels of width 4 come out
+      // 8 % longer, DESIGN.md "Round 13")
       const uint64_t endm = ballot(lane < static_cast<int>(p.R) && v == kEmpty);
       const int cnt = endm ? __ffsll(static_cast<unsigned long long>(endm)) - 1 : static_cast<int>(p.R);
       bool act = lane < cnt;
@@ -973,7 +1092,7 @@ __global__ void __launch_bounds__(256)
       // issue the prefetch only after v is consumed: a use of v behind a younger load would
       // otherwise wait for that load too (vmcnt counts in issue order)
       pred = ps.cur < ps.size ? (L.pi[ps.cur] & kIdMask) : kEmpty;
-      if (pred != kEmpty && lane < static_cast<int>(p.R)) pred_v = p.l0[static_cast<uint64_t>(pred) * p.R + lane];
+      if (pred != kEmpty) pred_v = adjacency_row(p, static_cast<int>(p.R), pred, pred_v);
 #ifdef ALAYA_FINE_STAMPS
       stamp(5);
 #else
@@ -986,27 +1105,9 @@ __global__ void __launch_bounds__(256)
       // distances a helper already computed for this node's row (exact: the same function of the same
       // query and row) go straight to cd; the rest are computed here, the known ones standing in the
       // list as kEmpty (distance functions skip them)
-      // scout: the bounds of this node's neighbours, if a memo row is published for it -- tag, bounds,
-      // tag again (see "Scout"); a fresh lane reads its own adjacency position and hands the bound to
-      // the lane that will hold the candidate.  One bound missing: today's pass for the whole list.
       bool memo_ok = false;
       if constexpr (kScout) {
-        if (scouting && ps.size == ps.ef && p.screen == 3) {
-          const uint64_t key = scout_key(qi + 1u, u);
-          uint64_t tg = 0ull;
-          if (lane < static_cast<int>(kScoutSlots)) tg = lds_load(&sboard->tag[lane]);
-          const uint64_t rows = ballot(tg == key);
-          if (rows != 0ull) {
-            const int row = __ffsll(static_cast<unsigned long long>(rows)) - 1;
-            lds_order();
-            const uint32_t mb = lds_load(&sboard->bound[row][lane & static_cast<int>(kScoutR - 1)]);
-            lds_order();
-            const uint64_t again = lds_load(&sboard->tag[row]);
-            memo_ok = ballot(again != key || (fresh && (mb == kScoutMissing || lane >= static_cast<int>(kScoutR)))) == 0ull;
-            if (memo_ok && fresh) L.cd[slot] = __uint_as_float(mb);
-          }
-          if (lane == 0) lds_store(&sboard->req[0], kEmpty);  // looked at: the scout may reuse u's row
-        }
+        if (scouting && ps.size == ps.ef && p.screen == 3) memo_ok = scout_lookup(sboard, qi + 1u, u, fresh, slot, L.cd);
       }
       const uint32_t *dist_ids = L.cid;
       bool compute = true;
@@ -1027,10 +1128,7 @@ __global__ void __launch_bounds__(256)
           }
           dist_ids = ids2;
           const uint32_t n_got = __popcll(ballot(got));
-          if (lane == 0 && n_got) {
-            board->own[wave].hits += n_got;
-            if (n_got == static_cast<uint32_t>(nf)) board->own[wave].skips += 1u;
-          }
+          help_count(board, wave, n_got, static_cast<uint32_t>(nf), lane);
           compute = n_got < static_cast<uint32_t>(nf);
         }
       }
@@ -1069,7 +1167,7 @@ __global__ void __launch_bounds__(256)
           float lb3 = 0.f;  // p.screen == 3: the bound itself
           if (p.screen == 3 && kScout && memo_ok) {  // wave-uniform: the scout's bounds (written to cd above)
             lb3 = L.cd[lane];  // (past the list: a stale word, a bound nobody reads)
-            if (lane == 0) sboard->stat[0] += 1u, sboard->stat[1] += 1u;
+            scout_count_screen(sboard, true);
             if (p.scout & kScoutVerify) {  // diagnostics: the searcher's own bounds must have the same bits
               const uint8_t *rp = p.screen_u8 + static_cast<uint64_t>(c) * screen_u8_record_bytes(p.stride);
               const float4 head = *reinterpret_cast<const float4 *>(rp);
@@ -1079,11 +1177,11 @@ __global__ void __launch_bounds__(256)
               const float own = screen_int_bound(p.stride, sq.err, sq.lo, sq.scale, sq.a1, sq.a2, head.x, head.y, head.z,
                                                  sums.x, sums.y, __float_as_uint(L.cd[lane]));
               const uint32_t bad = static_cast<uint32_t>(__popcll(ballot(in && __float_as_uint(own) != __float_as_uint(lb3))));
-              if (lane == 0 && bad != 0u) sboard->stat[2] += bad;
+              scout_count_mismatches(sboard, bad, lane);
             }
           } else if (p.screen == 3) {  // wave-uniform: the 8-bit records under the integer dot product
             if constexpr (kScout) {
-              if (scouting && lane == 0) sboard->stat[0] += 1u;
+              if (scouting) scout_count_screen(sboard, false);
             }
             // The lane's record header and code sums go out ahead of the pass's loads, in straight-line
             // code (a lane past the list reads row 0's): under `if (in)` the compiler joined this block
@@ -1110,27 +1208,8 @@ __global__ void __launch_bounds__(256)
           nd = __popcll(km);
           n_screened += static_cast<uint32_t>(nf);
           n_screened_out += static_cast<uint32_t>(nf - nd);
-          // kScoutEarly: a survivor whose distance comes out below the first unchecked entry's is the
-          // next pop, and on_next names it only after the exact pass and most of the merge.  The
-          // survivor with the smallest bound (none = 0 = smallest) is the likely one: if its bound is
-          // below that entry's distance it is requested now, the entry itself as the pop after.  A
-          // hint like every request: a wrong one costs the scout a row, and on_next still posts what
-          // the merge finds.
           if constexpr (kScout) {
-            if (early && nd > 0 && ps.cur < ps.size) {
-              const uint32_t kb = keep ? (lb3 > 0.f ? __float_as_uint(lb3) : 0u) : 0xffffffffu;
-              uint32_t mn = min(kb, lane_xor<1>(kb));
-              mn = min(mn, lane_xor<2>(mn));
-              mn = min(mn, lane_xor<4>(mn));
-              mn = min(mn, lane_xor<8>(mn));
-              mn = min(mn, lane_xor<16>(mn));
-              mn = min(read_lane(mn, 0), read_lane(mn, 32));
-              if (__uint_as_float(mn) < L.pd[ps.cur]) {
-                const uint32_t cand = read_lane(c, __ffsll(static_cast<unsigned long long>(ballot(kb == mn))) - 1);
-                scout_post(sboard, 1, 2, cand, pred, kEmpty);
-                if (lane == 0 && (sboard->pad & 0xffffu) != 0xffffu) sboard->pad += 1u;
-              }
-            }
+            if (early && nd > 0 && ps.cur < ps.size) scout_early_request(sboard, L, ps, keep, lb3, c, pred);
           }
           // (every lane read its id before screen_distances' closing wave_sync)
           if (keep) L.cid[__popcll(km & ((1ull << lane) - 1ull))] = c;
@@ -1170,18 +1249,13 @@ __global__ void __launch_bounds__(256)
           const uint32_t old_pred = pred;
           (void)old_pred;
           pred = nx;
+          // (adjacency_row, written out: through the helper a kernel-argument load of <30, 16> moves)
           if (lane < static_cast<int>(p.R)) pred_v = p.l0[static_cast<uint64_t>(nx) * p.R + lane];
           if constexpr (kHelp) {  // the new next pop, keeping the old one's request (likely the one after)
             if (mine.memo_wave >= 0) mine_request(board, wave, mine, kEmpty, nx, old_pred);
           }
           if constexpr (kScout) {  // the same for the scout
-            if (scouting && ps.size == ps.ef) {
-              // (an early request that named nx: req[1] holds nx only then, the pop's own post was pred)
-              if (early && lane == 0 && lds_load(&sboard->req[1]) == nx &&
-                  (sboard->pad >> 16) != 0xffffu)
-                sboard->pad += 0x10000u;
-              scout_post(sboard, 1, 2, nx, old_pred, kEmpty);
-            }
+            if (scouting && ps.size == ps.ef) scout_retarget(sboard, early, nx, old_pred);
           }
         }
       }
@@ -1202,32 +1276,12 @@ __global__ void __launch_bounds__(256)
   }
   if constexpr (kHelp) {
     help_siblings<kIP, kChunks, kSpace>(p, smem, L, board, wave, W);
-    if (p.help_stats != nullptr && lane == 0) {  // (the board outlives every wave's searching)
-      p.help_stats[3 * slot] = board->own[wave].hits;
-      p.help_stats[3 * slot + 1] = board->own[wave].skips;
-      p.help_stats[3 * slot + 2] = board->own[wave].rows;
-    }
+    help_stats_out(p, board, wave, slot, lane);
   }
   if constexpr (kScout) {
-    if (scouting) {  // the only way out of the query loop: the scout leaves its poll loop
-      if (lane == 0) lds_store(&sboard->state, kScoutDone);
-      if (p.scout_stats != nullptr && lane == 0) {  // (the scout writes word 2, the records it read)
-        p.scout_stats[4 * slot] = sboard->stat[0];
-        p.scout_stats[4 * slot + 1] = sboard->stat[1];
-        p.scout_stats[4 * slot + 3] = sboard->stat[2];
-      }
-      if (p.scout_policy_stats != nullptr && lane == 0) {  // (the scout writes word 2, the nodes it dropped)
-        p.scout_policy_stats[3 * slot] = sboard->pad & 0xffffu;
-        p.scout_policy_stats[3 * slot + 1] = sboard->pad >> 16;
-      }
-    }
+    if (scouting) scout_leave(p, sboard, slot);
   }
-  if constexpr (kScreen) {  // every searcher of the launch writes its slot
-    if (p.screen_stats != nullptr && lane == 0) {
-      p.screen_stats[2 * slot] = n_screened;
-      p.screen_stats[2 * slot + 1] = n_screened_out;
-    }
-  }
+  if constexpr (kScreen) screen_stats_out(p, slot, n_screened, n_screened_out, lane);
 }
 
 // The screening copy of the base (launch_screen_rows): one wave per row.  err = an over-estimate of

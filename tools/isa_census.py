@@ -12,6 +12,10 @@ A restore outside the expansion loop runs a handful of times per query; one insi
 per expansion (~90 times per SIFT query at ef 70).
 
 usage: python tools/isa_census.py [--out profiles/r03/isa/search_isa_census.json] [--filter 'Li4E']
+
+--compare PATH compiles another tree's search_kernels.hip (say the parent commit's, checked out into
+a scratch directory) as well and reports, per kernel symbol of the file, whether the two trees'
+generated code is the same: the acceptance test of a change that only moves source around.
 """
 
 from __future__ import annotations
@@ -165,13 +169,57 @@ def census(name: str, body: list[str]) -> dict:
     }
 
 
+def normalise(body: list[str]) -> list[str]:
+    """A kernel body without what differs between two compiles of one source: comments, debug
+    directives and the per-compile __hip_cuid_ symbol."""
+    out = []
+    for ln in body:
+        s = ln.split(";", 1)[0].strip()
+        if not s or s.startswith((".file", ".loc", ".ident")) or "__hip_cuid_" in s:
+            continue
+        out.append(s)
+    return out
+
+
+def compare(asm: str, other: str, show: int = 6) -> bool:
+    """Prints identical / differs per kernel symbol; True if every kernel is identical."""
+    mine, theirs = split_functions(asm), split_functions(other)
+    same = True
+    for name in sorted(set(mine) | set(theirs)):
+        if name not in mine or name not in theirs:
+            print(f"differs    {name}: only in {'this tree' if name in mine else 'the other tree'}")
+            same = False
+            continue
+        a, b = normalise(mine[name]), normalise(theirs[name])
+        if a == b:
+            print(f"identical  {demangle(name)}")
+            continue
+        same = False
+        at = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+        print(f"differs    {demangle(name)}: {len(a)} / {len(b)} lines, first at line {at}")
+        for x, y in list(zip(a[at:], b[at:]))[:show]:
+            print(f"    this: {x:<60} other: {y}")
+        print(f"    this:  {resource_comments(asm, name)}")
+        print(f"    other: {resource_comments(other, name)}")
+        for tag, src, body in (("this", asm, mine[name]), ("other", other, theirs[name])):
+            if "hnsw_search_kernel" in name:
+                c = census(name, body)
+                print(f"    {tag}: restores / scratch ops in expansion loops: "
+                      f"{c['restores_in_expansion_loops']} / {c['scratch_ops_in_expansion_loops']}")
+    return same
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--filter", default="hnsw_search_kernel")
     ap.add_argument("--extra", default="", help="extra hipcc flags (e.g. -DALAYA_...)")
+    ap.add_argument("--compare", default=None, metavar="PATH",
+                    help="another tree's search_kernels.hip: report identical / differs per kernel and exit")
     args = ap.parse_args()
     asm = compile_asm(SRC, args.extra.split())
+    if args.compare:
+        raise SystemExit(0 if compare(asm, compile_asm(args.compare, args.extra.split())) else 1)
     rows = []
     for name, body in split_functions(asm).items():
         if "hnsw_search_kernel" not in name or args.filter not in name:
