@@ -130,6 +130,7 @@ struct alaya_index {
   float max_norm = 0.f;
   // scratch
   DevBuf work, overflow, dirty, stab, q_buf, id_buf, dist_buf, cnt_buf, dlist_buf, dout_buf;
+  DevBuf allow_buf, group_buf;  // the host filtered search's masks and per-query mask indices
   size_t overflow_clean = 0;  // leading bytes of `overflow` known to be zero (kernels leave it clean)
   size_t stab_clean = 0;      // the same for the spill tables
   uint32_t hash_log2_override = 0;
@@ -356,8 +357,10 @@ bool helpers_requested(const alaya_index *ix, const SearchParams &p, uint64_t nq
   return nq > max_search_waves_per_cu() * cus;
 }
 
+// filter_k != 0: the filtered search -- its own kernel's registers, and a result pool of filter_k entries
+// in every wave's region.
 uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchVariant &v, uint64_t nq, uint32_t ef,
-                      int W = 1) {
+                      int W = 1, uint32_t filter_k = 0) {
   const uint32_t lbits = std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2)));
   const int mode = ix->visited_mode_override;  // 0 auto, 1 compact, 2 wide, 3 compact + short probes
   auto set_mode = [&](uint32_t l, bool compact) {
@@ -395,13 +398,16 @@ uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchV
   }
   const size_t shared = alaya_amd::search_shared_lds_bytes(ix->stride, p.sq8_order != 0) +
                         (p.help ? alaya_amd::kHelpBoardBytes : 0);
-  const size_t wave_fixed = alaya_amd::search_wave_lds_bytes(ix->stride, ef, 0, false, p.sq8_order) - 4;
+  const size_t wave_fixed = alaya_amd::search_wave_lds_bytes(ix->stride, ef, 0, false, p.sq8_order) - 4 +
+                            (filter_k ? alaya_amd::filter_result_lds_bytes(filter_k) : 0);
   // the register-bound residency, probed with a 4 KB table.  The 1 KB probe applies only to the
   // forced compact modes (1, 3) with a spill table: every other mode with a spill table returned
   // set_mode(7) above.
   const bool stab = p.stab_log2 != 0;  // set by do_search (spill_table_log2)
   int vgpr_blocks = 0;
-  hip_check(alaya_amd::search_occupancy(v, p.ip, W, shared + W * (wave_fixed + (stab ? 1024 : 4096)), &vgpr_blocks),
+  const size_t probe_lds = shared + W * (wave_fixed + (stab ? 1024 : 4096));
+  hip_check(filter_k ? alaya_amd::filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
+                     : alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks),
             "occupancy");
   const uint64_t vgpr_waves = static_cast<uint64_t>(std::max(1, vgpr_blocks)) * W;
   const uint64_t max_waves = std::max<uint64_t>(W, max_search_waves_per_cu());
@@ -631,14 +637,9 @@ SearchPlan plan_search(alaya_index *ix, SearchParams &p, alaya_amd::SearchReques
   return plan;
 }
 
-void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef,
-               uint32_t *d_ids, float *d_dists, uint32_t *d_cnt, hipStream_t stream,
-               uint64_t *d_stamps = nullptr, bool sq8 = false, uint32_t fill_id = 0) {
-  if (!ix->base.ptr) throw ArgError("index has no base vectors");
-  if (!ix->has_graph) throw ArgError("index has no graph");
-  if (ef == 0) throw ArgError("ef must be >= 1");
-  if (k == 0 || nq == 0) return;
-  if (ix->graph_n > ix->n) throw ArgError("graph has more nodes than base vectors");
+// base_params plus the graph and one batch: what every graph search launch reads and writes.
+SearchParams graph_search_params(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef, uint32_t *d_ids,
+                                 float *d_dists, uint32_t *d_cnt) {
   SearchParams p = base_params(ix);
   p.l0 = ix->l0.as<uint32_t>();
   p.R = ix->R;
@@ -658,6 +659,18 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   p.out_ids = d_ids;
   p.out_dists = d_dists;
   p.out_counters = d_cnt;
+  return p;
+}
+
+void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef,
+               uint32_t *d_ids, float *d_dists, uint32_t *d_cnt, hipStream_t stream,
+               uint64_t *d_stamps = nullptr, bool sq8 = false, uint32_t fill_id = 0) {
+  if (!ix->base.ptr) throw ArgError("index has no base vectors");
+  if (!ix->has_graph) throw ArgError("index has no graph");
+  if (ef == 0) throw ArgError("ef must be >= 1");
+  if (k == 0 || nq == 0) return;
+  if (ix->graph_n > ix->n) throw ArgError("graph has more nodes than base vectors");
+  SearchParams p = graph_search_params(ix, d_q, nq, k, ef, d_ids, d_dists, d_cnt);
   p.stamps = d_stamps;
   p.fill_id = fill_id;
   if (sq8) {
@@ -711,6 +724,64 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   p.work_counter = ix->work.as<uint32_t>();
   hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
   hip_check(alaya_amd::launch_search(*plan.variant, p, plan.grid, wg_waves, plan.lds, stream), "search launch");
+  scratch_release(ix, stream);
+}
+
+// Filtered graph search (alaya_index_filtered_search*, filtered_search_kernel): planned as the plain
+// (mode 0) search of the shape -- one searcher per wave, no helpers, screen, scout or two-waves mode --
+// with a result pool of k entries at the end of every wave's LDS region and the occupancy of the
+// filtered kernel itself.  d_allow: n_masks x ceil(n / 32) words; d_mask_of_query: nq indices or null.
+void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef, const uint32_t *d_allow,
+                        const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt,
+                        hipStream_t stream) {
+  using namespace alaya_amd;
+  if (!ix->base.ptr) throw ArgError("index has no base vectors");
+  if (!ix->has_graph) throw ArgError("index has no graph");
+  if (ix->has_sq8) throw ArgError("filtered search of an SQ8 index is not supported (f32 rows only)");
+  if (ef == 0) throw ArgError("ef must be >= 1");
+  if (k == 0 || k > 224) throw ArgError("filtered search: k must be in 1..224");
+  if (nq == 0) return;
+  if (ix->graph_n > ix->n) throw ArgError("graph has more nodes than base vectors");
+  SearchParams p = graph_search_params(ix, d_q, nq, k, ef, d_ids, d_dists, d_cnt);
+  p.fill_id = 0xffffffffu;  // empty result slots: (all-ones id, FLT_MAX), exact_search's convention
+  const SearchVariant &plain = resolve_search_variant({ix->dim, p.ip, 0, ix->generic, 0});
+  int W = search_waves(p);
+  while (W > 1 && static_cast<uint64_t>(W) > nq) W /= 2;
+  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k);
+  const size_t traversal_lds = search_wave_lds_bytes(ix->stride, ef, p.hash_log2, p.vis_rbits != kVisWide, 0);
+  p.wave_lds = static_cast<uint32_t>(traversal_lds + filter_result_lds_bytes(k));
+  FilterParams f{};
+  f.allow = d_allow;
+  f.mask_of_query = d_mask_of_query;
+  f.mask_words = static_cast<uint32_t>((ix->n + 31) / 32);
+  f.k = k;
+  f.result_off = static_cast<uint32_t>(traversal_lds);
+  const size_t lds = static_cast<size_t>(W) * p.wave_lds;
+  if (lds > kLdsPerCu) throw ArgError("filtered search: k / ef / dim too large for the LDS budget");
+  int per_cu = 0;
+  hip_check(filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu), "occupancy");
+  per_cu = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(per_cu, max_search_waves_per_cu() / W)));
+  const uint64_t cus = static_cast<uint64_t>(stream_cus(ix, stream));
+  int grid = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>((nq + W - 1) / W, static_cast<uint64_t>(per_cu) * cus)));
+  // diagnostics (ALAYA_FILTER_GRID, include/alaya_hip.h): fewer workgroups than queries, so every wave runs
+  // several queries of the launch, one after the other, on one result pool
+  if (const char *e = std::getenv("ALAYA_FILTER_GRID")) grid = std::max(1, std::min(grid, std::atoi(e)));
+  scratch_acquire(ix, stream);
+  const uint64_t searchers = static_cast<uint64_t>(grid) * W;
+  prepare_spill(ix, p, searchers, stream);
+  ix->last_grid = static_cast<uint32_t>(grid);
+  ix->last_waves = static_cast<uint32_t>(W);
+  ix->last_lds = static_cast<uint32_t>(lds);
+  ix->last_hash_log2 = p.hash_log2;
+  ix->last_compact = p.vis_rbits != kVisWide ? 1u : 0u;
+  ix->last_per_cu = static_cast<uint32_t>(per_cu);
+  ix->last_scout = 0;
+  ix->last_scout_policy = 0;
+  ix->scout_stats_slots = ix->help_stats_slots = ix->screen_stats_slots = 0;
+  ix->work.reserve(4);
+  p.work_counter = ix->work.as<uint32_t>();
+  hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
+  hip_check(launch_filtered_search(p, f, grid, W, lds, stream), "filtered search launch");
   scratch_release(ix, stream);
 }
 
@@ -1865,6 +1936,60 @@ int alaya_index_batch_search(alaya_index *ix, const float *queries, uint64_t nq,
     if (counters)
       hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
     hip_check(hipStreamSynchronize(ix->stream), "search");
+  });
+}
+
+int alaya_index_filtered_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                       const uint32_t *d_allow_words, uint32_t n_masks, const uint32_t *d_mask_of_query,
+                                       uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (nq && (!d_queries || !d_ids || !d_allow_words))) throw ArgError("invalid arguments");
+    if (nq && (n_masks == 0 || (n_masks > 1 && !d_mask_of_query)))
+      throw ArgError("filtered search: mask_of_query may be null only with one mask");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    do_filtered_search(ix, d_queries, nq, k, ef, d_allow_words, d_mask_of_query, d_ids, d_dists, d_counters,
+                       static_cast<hipStream_t>(stream));
+  });
+}
+
+int alaya_index_filtered_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                uint32_t *ids, float *dists, uint32_t *counters) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (nq && (!queries || !ids || !allow_words))) throw ArgError("invalid arguments");
+    if (nq && (n_masks == 0 || (n_masks > 1 && !mask_of_query)))
+      throw ArgError("filtered search: mask_of_query may be null only with one mask");
+    if (mask_of_query)
+      for (uint64_t i = 0; i < nq; ++i)
+        if (mask_of_query[i] >= n_masks) throw ArgError("filtered search: mask_of_query holds an index past n_masks");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    if (k == 0 || k > 224) throw ArgError("filtered search: k must be in 1..224");
+    if (nq == 0) return;
+    const size_t mask_bytes = static_cast<size_t>(n_masks) * ((ix->n + 31) / 32) * 4;
+    ix->q_buf.reserve(nq * ix->dim * 4);
+    ix->id_buf.reserve(nq * k * 4);
+    ix->dist_buf.reserve(nq * k * 4);
+    ix->cnt_buf.reserve(nq * 16);
+    ix->allow_buf.reserve(mask_bytes);
+    ix->group_buf.reserve(nq * 4);
+    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
+              "upload queries");
+    hip_check(hipMemcpyAsync(ix->allow_buf.ptr, allow_words, mask_bytes, hipMemcpyHostToDevice, ix->stream),
+              "upload masks");
+    if (mask_of_query)
+      hip_check(hipMemcpyAsync(ix->group_buf.ptr, mask_of_query, nq * 4, hipMemcpyHostToDevice, ix->stream),
+                "upload mask indices");
+    do_filtered_search(ix, ix->q_buf.as<float>(), nq, k, ef, ix->allow_buf.as<uint32_t>(),
+                       mask_of_query ? ix->group_buf.as<uint32_t>() : nullptr, ix->id_buf.as<uint32_t>(),
+                       ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream);
+    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    if (dists)
+      hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    if (counters)
+      hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    hip_check(hipStreamSynchronize(ix->stream), "filtered search");
   });
 }
 

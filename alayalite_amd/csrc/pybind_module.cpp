@@ -264,6 +264,49 @@ class PyIndexInterface : public LaunchControls {
     return py::make_tuple(ids, dists);
   }
 
+  // --- extra (not in the reference binding): the topk nearest rows among those a mask allows
+  // (alaya_index_filtered_search).  allow_words: uint32 [n_masks, ceil(n / 32)] (utils.pack_allow);
+  // mask_of_query: each query's mask, or None with one mask.  Empty slots as exact_search's.
+  py::object filtered_search(py::array queries, uint32_t topk, uint32_t ef,
+                             py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
+                             py::object mask_of_query) {
+    if (!graph_) throw std::runtime_error("Index is not init yet");
+    if (params_.quantization_type_ != QuantizationType::NONE)
+      throw std::runtime_error("filtered_search on quantized indexes is not supported by the MI355X engine");
+    py::array q = prepare_queries(queries);
+    const uint64_t nq = q.shape(0);
+    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n_ + 31) / 32 || allow_words.shape(0) < 1)
+      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
+    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
+    const uint32_t *gp = nullptr;
+    if (!mask_of_query.is_none()) {
+      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
+      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
+        throw py::value_error("mask_of_query must hold one index per query");
+      gp = groups.data();
+    }
+    std::vector<uint32_t> ids32(nq * topk);
+    py::array_t<float> dists({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    last_counters_.assign(nq * 4, 0);
+    const uint32_t *ap = allow_words.data();
+    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_filtered_search(ix_, static_cast<const float *>(q.data()), nq, topk, ef, ap, n_masks, gp,
+                                        ids32.data(), dists.mutable_data(), last_counters_.data()));
+    }
+    py::array ids(params_.id_type_, std::vector<py::ssize_t>{static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    if (id_bytes_ == 4) {
+      std::memcpy(ids.mutable_data(), ids32.data(), ids32.size() * 4);
+    } else {
+      auto *o = static_cast<uint64_t *>(ids.mutable_data());
+      for (size_t i = 0; i < ids32.size(); ++i) o[i] = ids32[i] == 0xffffffffu ? UINT64_MAX : ids32[i];
+    }
+    return py::make_tuple(ids, dists);
+  }
+
+  uint64_t get_data_num() const { return n_; }
+
   py::array get_data_by_id(uint32_t id) {
     if (n_ == 0) throw std::runtime_error("space is nullptr");
     if (id >= n_) throw std::runtime_error("id out of range");
@@ -844,6 +887,48 @@ class DeviceIndex : public LaunchControls {
                                           reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
                                           reinterpret_cast<uint32_t *>(counters), reinterpret_cast<void *>(stream)));
   }
+  // the k nearest rows among those allow_words (uint32 [n_masks, ceil(n / 32)], utils.pack_allow) allows;
+  // mask_of_query: each query's mask, or None with one mask
+  py::tuple filtered_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
+                            py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
+                            py::object mask_of_query) {
+    const uint64_t nq = q.shape(0);
+    uint64_t n = 0;
+    check(alaya_index_info(ix_, &n, nullptr, nullptr, nullptr, nullptr));
+    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n + 31) / 32 || allow_words.shape(0) < 1)
+      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
+    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
+    const uint32_t *gp = nullptr;
+    if (!mask_of_query.is_none()) {
+      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
+      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
+        throw py::value_error("mask_of_query must hold one index per query");
+      gp = groups.data();
+    }
+    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
+    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
+    py::array_t<uint32_t> c({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(4)});
+    const float *qp = q.data();
+    const uint32_t *ap = allow_words.data();
+    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
+    uint32_t *ip = ids.mutable_data();
+    float *dp = d.mutable_data();
+    uint32_t *cp = c.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_filtered_search(ix_, qp, nq, k, ef, ap, n_masks, gp, ip, dp, cp));
+    }
+    return py::make_tuple(ids, d, c);
+  }
+  void filtered_search_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t allow_words, uint32_t n_masks,
+                              uintptr_t mask_of_query, uintptr_t ids, uintptr_t dists, uintptr_t counters,
+                              uintptr_t stream) {
+    check(alaya_index_filtered_search_device(ix_, reinterpret_cast<const float *>(q), nq, k, ef,
+                                             reinterpret_cast<const uint32_t *>(allow_words), n_masks,
+                                             reinterpret_cast<const uint32_t *>(mask_of_query),
+                                             reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
+                                             reinterpret_cast<uint32_t *>(counters), reinterpret_cast<void *>(stream)));
+  }
   void shard_search_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t ids, uintptr_t dists,
                            uintptr_t counters, uintptr_t stream) {
     check(alaya_index_shard_search_device(ix_, reinterpret_cast<const float *>(q), nq, k, ef,
@@ -1014,7 +1099,10 @@ PYBIND11_MODULE(_alayalitepy, m) {
            py::arg("quant_path") = std::string())
       .def("load", &PyIndexInterface::load, py::arg("index_path"), py::arg("data_path"),
            py::arg("quant_path") = std::string())
+      .def("filtered_search", &PyIndexInterface::filtered_search, py::arg("queries"), py::arg("topk"), py::arg("ef"),
+           py::arg("allow_words"), py::arg("mask_of_query") = py::none())
       .def("get_data_dim", &PyIndexInterface::get_data_dim)
+      .def("get_data_num", &PyIndexInterface::get_data_num)
       .def("last_counters", &PyIndexInterface::last_counters)
       .def("set_hash_log2", &PyIndexInterface::set_hash_log2)
       .def("set_visited_mode", &PyIndexInterface::set_visited_mode)
@@ -1047,6 +1135,9 @@ PYBIND11_MODULE(_alayalitepy, m) {
            py::arg("seed") = 100, py::arg("batch_div") = 0, py::arg("max_batch") = 0, py::arg("refine") = 2)
       .def("search", &DeviceIndex::search, py::arg("queries"), py::arg("k"), py::arg("ef"))
       .def("search_device", &DeviceIndex::search_device)
+      .def("filtered_search", &DeviceIndex::filtered_search, py::arg("queries"), py::arg("k"), py::arg("ef"),
+           py::arg("allow_words"), py::arg("mask_of_query") = py::none())
+      .def("filtered_search_device", &DeviceIndex::filtered_search_device)
       .def("shard_search_device", &DeviceIndex::shard_search_device)
       .def("distances", &DeviceIndex::distances)
       .def("set_hash_log2", &DeviceIndex::set_hash_log2)

@@ -122,6 +122,18 @@ constexpr uint32_t kScoutR = 32;      // adjacency positions per memo row: one p
 // word and the searcher's three counters
 constexpr size_t kScoutBoardBytes = kScoutSlots * (kScoutR * 4 + 8 + 4) + 20;
 
+// The filtered search's own arguments (filtered_search_kernel's second argument: SearchParams keeps
+// its layout).  All pointers are device pointers.
+struct FilterParams {
+  const uint32_t *allow;          // n_masks x mask_words words; bit i of word i / 32 = row i (the validity
+                                  // bitmap's layout)
+  const uint32_t *mask_of_query;  // nq indices below n_masks; nullptr = every query uses mask 0
+  uint32_t mask_words;            // ceil(n / 32)
+  uint32_t k;                     // the result pool's capacity (= SearchParams::k)
+  uint32_t result_off;            // byte offset of the result pool in a wave's LDS region (past the
+                                  // visited table: SearchParams::wave_lds - filter_result_lds_bytes(k))
+};
+
 // PyIndex::rerank inputs (python/include/index.hpp:450-488).  Per query the kernel rescores
 // search_ids[0 .. n_take) (row stride n_src; kEmpty entries are skipped) plus `zeros` entries of id 0
 // -- the reference's res_pool slots [k, ef) that batch_search leaves zero (index.hpp:301) -- and
@@ -181,6 +193,13 @@ hipError_t launch_screen_rows_u8(const float *base, uint64_t first, uint64_t cou
 // p.screen / the LDS layout were planned for
 hipError_t launch_search(const SearchVariant &v, const SearchParams &p, int grid, int waves, size_t lds,
                          hipStream_t stream);
+// Filtered search (filtered_search_kernel; f32 rows): bytes of a wave's result pool (k + 1 distances and
+// ids), the kernel of the shape's resident workgroups per CU, and its launch.  p is planned as the
+// plain (mode 0) search of the shape, with the result pool's bytes at the end of p.wave_lds.
+size_t filter_result_lds_bytes(uint32_t k);
+hipError_t filtered_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);
+hipError_t launch_filtered_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
+                                  hipStream_t stream);
 // out[q * n + i] = dist(queries[q], base[ids[i]]) for q < nq (bit-exact device distance)
 hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint32_t n,
                                 uint32_t nq, float *out, hipStream_t stream);

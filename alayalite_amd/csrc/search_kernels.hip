@@ -109,10 +109,16 @@ __device__ __forceinline__ void fill_shared(const SearchParams &p, const Lds &L)
 
 // Per-query setup shared by the search kernels: the query staged in LDS (SQ8: encoded with the
 // quantizer), visited table and pool cleared, then Graph::initialize_search (graph.hpp:148-158).
-template <bool kIP, int kChunks, int kSpace, int kRows = 0>
+// on_entry(has, id, d) sees what initialize_search hands to pool.insert, lane order = insertion order
+// (the filtered search's result pool).
+struct NoEntry {
+  __device__ void operator()(bool, uint32_t, float) const {}
+};
+
+template <bool kIP, int kChunks, int kSpace, int kRows = 0, typename Entry = NoEntry>
 __device__ __forceinline__ void query_begin(const SearchParams &p, const Lds &L, uint32_t qi, uint32_t *slot_bits,
                                             uint32_t *slot_dirty, uint16_t *slot_stab, Visited &vs, PoolState &ps,
-                                            uint32_t &n_dist_up, uint32_t &n_hops_up) {
+                                            uint32_t &n_dist_up, uint32_t &n_hops_up, Entry on_entry = Entry()) {
   const int lane = lane_id();
   const uint32_t hsize = 1u << p.hash_log2;
   // ---- per-query init ------------------------------------------------------------------
@@ -219,6 +225,7 @@ __device__ __forceinline__ void query_begin(const SearchParams &p, const Lds &L,
     ps.cur = 0;
     visit<kTab>(vs, u, lane == 0);
     wave_sync();
+    on_entry(lane == 0, u, cur);
   } else {
     // NSG-style entry points: insert each ep, then mark it visited (graph.hpp:153-156)
     for (uint32_t b = 0; b < p.n_eps; b += 64) {
@@ -234,6 +241,7 @@ __device__ __forceinline__ void query_begin(const SearchParams &p, const Lds &L,
       const float d = has ? L.cd[lane] : 0.f;
       wave_sync();
       pool_merge(ps, L, has, v, d);
+      on_entry(has, v, d);
       // duplicates among eps are all inserted (no visited check in the reference loop)
       for (uint32_t j = 0; j < cnt; ++j) {
         const uint32_t vj = read_lane(v, j);
@@ -1517,6 +1525,130 @@ __global__ void __launch_bounds__(256) stream_read_kernel(const float4 *p, uint6
   for (; i < n16; i += stride) acc += p[i].x;
   if (acc == -1.2345f) *sink = acc;  // never true for the probe's zeroed buffer
 }
+
+// --------------------------------------------------------------------------------------------
+// Filtered search: the traversal of hnsw_search_kernel's plain searcher (no helpers, screen, scout or two-waves
+// mode; f32 rows), plus a second LinearPool of capacity k per wave, the result pool, that is offered
+// every (id, distance) the traversal hands to pool.insert -- in that order -- whose row is valid and
+// allowed by the query's mask.  The traversal pool, the visited set, every pop and the four counters
+// are those of the unfiltered search at the same ef; the output is the result pool, then empty slots
+// (kEmpty, FLT_MAX).  The result pool sits at f.result_off of the wave's LDS region, past the visited
+// table, so carve_lds and every offset the other kernels use stay as they are.
+// --------------------------------------------------------------------------------------------
+// The wave's result pool as an Lds whose pool is the result pool (pool_merge's view; sd is shared
+// scratch, free between two merges).
+__device__ __forceinline__ Lds result_lds(const Lds &L, const FilterParams &f) {
+  Lds Lr = L;
+  unsigned char *ptr = reinterpret_cast<unsigned char *>(L.q) + f.result_off;
+  Lr.pd = reinterpret_cast<float *>(ptr);
+  Lr.pi = reinterpret_cast<uint32_t *>(ptr + ((f.k + 1) * 4 + 15) / 16 * 16);
+  return Lr;
+}
+
+// result.insert(id, d) for the lanes with ok, in lane order.  Most offers find the pool full and every
+// distance at or past its worst one: one LDS read and one ballot, no merge.
+__device__ __forceinline__ void result_offer(PoolState &rs, const Lds &Lr, bool ok, uint32_t id, float d) {
+  const bool full = rs.size == rs.ef;
+  const float worst = full ? Lr.pd[rs.size - 1] : 0.f;
+  if (ballot(ok && !(full && d >= worst)) == 0ull) return;
+  pool_merge(rs, Lr, ok, id, d);
+}
+
+template <bool kIP, int kChunks>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(search_min_waves<kChunks, 0, 0>() ? search_min_waves<kChunks, 0, 0>() : 1, 8)))
+    filtered_search_kernel(SearchParams p, FilterParams f) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int kSpace = 0;
+  const int lane = lane_id();
+  const int wave = static_cast<int>(threadIdx.x >> 6);
+  const int W = static_cast<int>(blockDim.x >> 6);
+  const Lds L = carve_lds<kSpace>(p, smem, wave);
+  const Lds Lr = result_lds(L, f);
+  const uint64_t bit_words = (p.n + 31) / 32;
+  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * W + wave;
+  uint32_t *slot_bits = p.overflow_bits + slot * bit_words;
+  uint32_t *slot_dirty = p.dirty_words + slot * p.dirty_cap;
+  constexpr bool kRegMerge = kChunks > 0 && kChunks <= 8;  // as the plain kernel's traversal merge
+
+  for (;;) {
+    uint32_t qi = 0;
+    if (lane == 0) qi = atomicAdd(p.work_counter, 1u);
+    qi = read_lane(qi, 0);
+    if (qi >= p.nq) break;
+    // the query's mask; a row is allowed if its bit is set and (indexes with a bitmap) it is valid
+    const uint32_t *mask = f.allow + static_cast<uint64_t>(f.mask_of_query != nullptr ? f.mask_of_query[qi] : 0u) * f.mask_words;
+    for (uint32_t e = lane; e <= f.k; e += 64) {
+      Lr.pd[e] = 0.f;
+      Lr.pi[e] = 0u;
+    }
+    PoolState rs{0u, 0u, f.k};
+    Visited vs;
+    PoolState ps;
+    uint32_t n_dist = 0, n_expand = 0, n_dist_up = 0, n_hops_up = 0;
+    // (query_begin's first wave_sync orders the reset above before any offer)
+    query_begin<kIP, kChunks, kSpace>(p, L, qi, slot_bits, slot_dirty, nullptr, vs, ps, n_dist_up, n_hops_up,
+                                      [&](bool has, uint32_t id, float d) {
+                                        bool ok = false;
+                                        if (has) {
+                                          ok = ((mask[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                          if (p.valid != nullptr) ok = ok && ((p.valid[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                        }
+                                        result_offer(rs, Lr, ok, id, d);
+                                      });
+
+    // ---- best-first expansion: the plain searcher's loop ------------------------------------
+    uint32_t pred = kEmpty, pred_v = kEmpty;  // adjacency prefetch of the predicted next pop
+    while (ps.cur < ps.size) {
+      const uint32_t u = pool_pop(ps, L);
+      ++n_expand;
+      uint32_t v = u == pred ? pred_v : adjacency_row(p, static_cast<int>(p.R), u);
+      const int cnt = adjacency_count(static_cast<int>(p.R), v);
+      bool act = lane < cnt;
+      if (p.dedup_edges) {  // graphs with repeated ids in a row: keep the first occurrence only
+        for (int j = 0; j < cnt; ++j) {
+          const uint32_t vj = read_lane(v, j);
+          if (j < lane && vj == v) act = false;
+        }
+      }
+      if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin(vs);
+      const bool fresh = visit(vs, v, act);
+      const uint64_t fm = ballot(fresh);
+      const int nf = __popcll(fm);
+      pred = ps.cur < ps.size ? (L.pi[ps.cur] & kIdMask) : kEmpty;
+      if (pred != kEmpty) pred_v = adjacency_row(p, static_cast<int>(p.R), pred, pred_v);
+      if (nf == 0) continue;
+      // compact fresh ids in adjacency order
+      if (fresh) L.cid[__popcll(fm & ((1ull << lane) - 1ull))] = v;
+      wave_sync();
+      // The candidates are known: each one's allow word (and validity word) goes out here, ahead of
+      // the row gather, by the lane that will hold the candidate at the merges; the words are used
+      // only after the distances, so their latency is the rows'.
+      const bool has = lane < nf;
+      const uint32_t cid = has ? L.cid[lane] : 0u;
+      uint32_t aw = 0u, vw = 0xffffffffu;
+      if (has) {
+        aw = mask[cid >> 5];
+        if (p.valid != nullptr) vw = p.valid[cid >> 5];
+      }
+      space_distances<kIP, kChunks, kSpace>(p, L, L.cid, nf, L.cd);
+      n_dist += nf;
+      const float cd = has ? L.cd[lane] : 0.f;
+      wave_sync();
+      pool_merge<kRegMerge>(ps, L, has, cid, cd, [&](uint32_t nx) {
+        if (nx != pred) {
+          pred = nx;
+          pred_v = adjacency_row(p, static_cast<int>(p.R), nx, pred_v);
+        }
+      });
+      result_offer(rs, Lr, has && (((aw & vw) >> (cid & 31)) & 1u) != 0u, cid, cd);
+    }
+
+    query_end(p, Lr, rs, qi, n_dist, n_expand, n_dist_up, n_hops_up);
+    visit_end(vs);
+    wave_sync();
+  }
+}
 }  // namespace
 
 hipError_t launch_stream_read(const void *buf, uint64_t bytes, int grid, int shape, float *sink,
@@ -1613,6 +1745,39 @@ hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint
 
 hipError_t search_occupancy(const SearchVariant &v, bool ip, int waves, size_t lds, int *blocks_per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, search_kernel_symbol(v, ip), 64 * waves, lds);
+}
+
+// The filtered kernels: {L2, IP} x the plain f32 kernels' widths; the generic element order rides on
+// the runtime-d kernel (chunks 0), as in the plain kernel.
+template <int... kChunks>
+static const void *filtered_symbol_of(int chunks, bool ip) {
+  const void *sym = nullptr;
+  ((chunks == kChunks ? (sym = ip ? reinterpret_cast<const void *>(&filtered_search_kernel<true, kChunks>)
+                                  : reinterpret_cast<const void *>(&filtered_search_kernel<false, kChunks>),
+                         0)
+                      : 0),
+   ...);
+  return sym;
+}
+
+static const void *filtered_kernel_symbol(uint32_t dim, bool generic, bool ip) {
+  const void *sym = filtered_symbol_of<4, 8, 16, 24, 30, 32>(search_chunks(dim, generic), ip);
+  return sym != nullptr ? sym : filtered_symbol_of<0>(0, ip);
+}
+
+size_t filter_result_lds_bytes(uint32_t k) { return 2 * ((static_cast<size_t>(k + 1) * 4 + 15) / 16 * 16); }
+
+hipError_t launch_filtered_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
+                                  hipStream_t stream) {
+  SearchParams arg = p;
+  FilterParams farg = f;
+  void *args[] = {&arg, &farg};
+  return hipLaunchKernel(filtered_kernel_symbol(p.dim, p.generic, p.ip), dim3(grid), dim3(64 * waves), args, lds, stream);
+}
+
+hipError_t filtered_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, filtered_kernel_symbol(dim, generic, ip), 64 * waves,
+                                                      lds);
 }
 
 }  // namespace alaya_amd

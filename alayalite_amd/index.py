@@ -10,6 +10,7 @@ import numpy as np
 from ._native import PyIndexInterface as _PyIndexInterface
 from .common import VectorLike, VectorLikeBatch, _assert
 from .schema import IndexParams, load_schema
+from .utils import pack_allow
 
 
 class Index:
@@ -107,6 +108,35 @@ class Index:
         valid rows hold (the id type's maximum, FLT_MAX).  1 <= topk <= 224, float32 data."""
         self._check_queries(queries, 2, "queries")
         return self.__index.exact_search(queries, topk)
+
+    def get_data_num(self) -> int:
+        """Rows the index holds, removed ones included: the length of a ``filtered_search`` mask."""
+        _assert(self.__index is not None, "Index is not init yet")
+        return self.__index.get_data_num()
+
+    def filtered_search(self, queries: VectorLikeBatch, topk: int, ef_search: int = 100, allow=None, groups=None):
+        """The ``topk`` nearest rows among those a mask allows.  The graph traversal is ``batch_search``'s
+        at ``ef_search``; every distance it computes for a valid, allowed row is offered to a result
+        pool of ``topk`` entries, so the answer draws on all of them and not only on the ``ef_search``
+        rows the traversal keeps.  ``allow``: bool array of shape (n,), n = ``get_data_num()``, or
+        (G, n) with ``groups`` of shape (nq,), the mask (an int below G) of each query.  Returns
+        (ids, distances); slots the allowed rows did not fill hold (the id type's maximum, FLT_MAX).
+        1 <= topk <= 224; float32 rows without quantization."""
+        self._check_queries(queries, 2, "queries")
+        _assert(allow is not None, "allow is required")
+        allow = np.asarray(allow)
+        _assert(allow.ndim in (1, 2), "allow must have shape (n,) or (G, n)")
+        words = pack_allow(allow, self.get_data_num())
+        if groups is None:
+            _assert(words.shape[0] == 1, "groups is required with more than one mask")
+        else:
+            groups = np.asarray(groups)
+            _assert(groups.shape == (queries.shape[0],), "groups must have shape (nq,)")
+            _assert(np.issubdtype(groups.dtype, np.integer), "groups must be integers")
+            _assert(groups.size == 0 or (groups.min() >= 0 and groups.max() < words.shape[0]),
+                    "groups must be below the number of masks")
+            groups = np.ascontiguousarray(groups, np.uint32)
+        return self.__index.filtered_search(queries, topk, ef_search, words, groups)
 
     def save(self, url) -> dict:
         os.makedirs(url, exist_ok=True)

@@ -341,6 +341,12 @@ class ShardedIndex:
         shard_search(self.index, self.lo, self.sq8 is not None, q_dev, k, ef, ids_dev, dists_dev, counters_dev,
                      stream, rq_dev)
 
+    def filtered_search(self, *args, **kwargs):
+        """Not built: a mask covers the whole base's rows, a shard holds a range of them, and the
+        cross-shard merge has no filtered form yet."""
+        raise NotImplementedError("filtered_search is not supported on a sharded index; use Index.filtered_search "
+                                  "on an unsharded one")
+
     def search(self, q_dev, k: int, ef: int, stream, group=None):
         import torch
 

@@ -6,7 +6,7 @@ import hashlib
 
 import numpy as np
 
-__all__ = ["load_fvecs", "load_ivecs", "calc_recall", "calc_gt", "calc_gt_device", "md5"]
+__all__ = ["load_fvecs", "load_ivecs", "calc_recall", "calc_gt", "calc_gt_device", "md5", "pack_allow"]
 
 
 def _load_vecs(file_path, dtype):
@@ -68,6 +68,24 @@ def calc_gt_device(data, query, topk, device=0, metric="l2"):
     ix.set_base(data, _GT_METRICS[metric])
     ids, dists, _ = ix.flat_search(query, topk)
     return ids.astype(np.int32), dists
+
+
+def pack_allow(allow, n):
+    """Bool masks over n rows as the words ``filtered_search`` reads: uint32 [G, ceil(n / 32)], bit
+    i % 32 of word i // 32 of a mask = row i (little bit order), padding bits zero.  ``allow`` has
+    shape (n,) -- one mask, G = 1 -- or (G, n); any dtype, nonzero = allowed."""
+    a = np.asarray(allow)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[0] < 1:
+        raise ValueError(f"allow must have shape (n,) or (G, n) with G >= 1, got {np.asarray(allow).shape}")
+    if n < 0 or a.shape[1] != n:
+        raise ValueError(f"allow must cover the index's {n} rows, got {a.shape[1]}")
+    words = (n + 31) // 32
+    bits = np.zeros((a.shape[0], words * 32), np.uint8)
+    bits[:, :n] = a != 0
+    packed = np.packbits(bits, axis=1, bitorder="little")
+    return np.ascontiguousarray(packed).view("<u4").astype(np.uint32, copy=False).reshape(a.shape[0], words)
 
 
 def md5(arr, chunk_size=1024 * 1024):

@@ -124,6 +124,26 @@ int alaya_index_batch_search_device(alaya_index *ix, const float *d_queries, uin
 int alaya_index_shard_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k,
                                     uint32_t ef, uint32_t *d_ids, float *d_dists, uint32_t *d_counters,
                                     void *stream);
+/* Filtered graph search: the k nearest rows among those a per-query mask allows (f32 rows; an index
+ * with SQ8 codes is refused).  The traversal is alaya_index_batch_search's at the same ef -- the same
+ * overlay descent, pool of capacity ef, visited set and pops, so the four counters are the same --
+ * and beside it a second pool of capacity k, the result pool, is offered every (id, distance) the
+ * traversal hands to its own pool, in that order, whose row is valid and allowed.  ids / dists hold
+ * the result pool in order, then empty slots (0xffffffff, FLT_MAX).  A candidate the traversal pool
+ * rejects can still enter the result pool, and k may exceed ef; 1 <= k <= 224, ef >= 1.
+ * allow_words: n_masks x ceil(n / 32) uint32 words, bit i % 32 of word i / 32 of a mask = row i (the
+ * validity bitmap's layout as 32-bit words); n = the index's row count, removed rows included; bits
+ * past n are ignored.  mask_of_query: nq indices below n_masks, the mask of each query; may be NULL
+ * when n_masks == 1.  Environment ALAYA_FILTER_GRID=n (diagnostics, read per launch) holds the launch
+ * to n workgroups, so every wave runs several queries one after the other; results never depend on it. */
+int alaya_index_filtered_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                uint32_t *ids, float *dists, uint32_t *counters);
+/* Same on device buffers, asynchronous on `stream`; the indices of d_mask_of_query are not checked. */
+int alaya_index_filtered_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                       const uint32_t *d_allow_words, uint32_t n_masks,
+                                       const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
+                                       uint32_t *d_counters, void *stream);
 /* ---- device graph construction (Index.fit on the MI355X) ------------------------------------
  * Replaces HNSWBuilder::build_graph (include/index/graph/hnsw/hnsw_builder.hpp:98-194) over hnswlib
  * add_point (include/index/graph/hnsw/hnswlib.hpp:652-751), from the index's own rows
