@@ -406,8 +406,9 @@ uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchV
   const bool stab = p.stab_log2 != 0;  // set by do_search (spill_table_log2)
   int vgpr_blocks = 0;
   const size_t probe_lds = shared + W * (wave_fixed + (stab ? 1024 : 4096));
-  hip_check(filter_k ? alaya_amd::filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
-                     : alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks),
+  hip_check(!filter_k ? alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks)
+            : p.sq8_order ? alaya_amd::filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, probe_lds, &vgpr_blocks)
+                          : alaya_amd::filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks),
             "occupancy");
   const uint64_t vgpr_waves = static_cast<uint64_t>(std::max(1, vgpr_blocks)) * W;
   const uint64_t max_waves = std::max<uint64_t>(W, max_search_waves_per_cu());
@@ -731,24 +732,40 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
 // (mode 0) search of the shape -- one searcher per wave, no helpers, screen, scout or two-waves mode --
 // with a result pool of k entries at the end of every wave's LDS region and the occupancy of the
 // filtered kernel itself.  d_allow: n_masks x ceil(n / 32) words; d_mask_of_query: nq indices or null.
+//
+// sq8: the search stage of the filtered SQ8 search (alaya_index_filtered_search_sq8*, filtered_sq8_search_kernel) --
+// the same plan for the mode-0 SQ8 request of the shape (four waves per workgroup beside the shared scale / min,
+// the spill-table second level where spill_table_log2 gives one); k is then the candidate pool's capacity m
+// and d_ids / d_dists receive the nq x m candidates by code distance, for the rerank.
 void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef, const uint32_t *d_allow,
                         const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt,
-                        hipStream_t stream) {
+                        hipStream_t stream, bool sq8 = false) {
   using namespace alaya_amd;
   if (!ix->base.ptr) throw ArgError("index has no base vectors");
   if (!ix->has_graph) throw ArgError("index has no graph");
-  if (ix->has_sq8) throw ArgError("filtered search of an SQ8 index is not supported (f32 rows only)");
+  if (sq8 && !ix->has_sq8) throw ArgError("index has no SQ8 codes");
+  if (!sq8 && ix->has_sq8)
+    throw ArgError("filtered search of an SQ8 index: use alaya_index_filtered_search_sq8 (this call searches f32 rows only)");
   if (ef == 0) throw ArgError("ef must be >= 1");
   if (k == 0 || k > 224) throw ArgError("filtered search: k must be in 1..224");
   if (nq == 0) return;
   if (ix->graph_n > ix->n) throw ArgError("graph has more nodes than base vectors");
   SearchParams p = graph_search_params(ix, d_q, nq, k, ef, d_ids, d_dists, d_cnt);
   p.fill_id = 0xffffffffu;  // empty result slots: (all-ones id, FLT_MAX), exact_search's convention
-  const SearchVariant &plain = resolve_search_variant({ix->dim, p.ip, 0, ix->generic, 0});
+  if (sq8) {
+    p.sq8_order = ix->sq8_order;
+    p.codes = ix->codes.as<uint8_t>();
+    p.code_stride = ix->code_stride;
+    p.sq_min = ix->sq_min.as<float>();
+    p.sq_max = ix->sq_max.as<float>();
+    // the visited second level: spill table or bitset, as do_search plans it
+    p.stab_log2 = spill_table_log2(p.sq8_order, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2))), ef);
+  }
+  const SearchVariant &plain = resolve_search_variant({ix->dim, p.ip, p.sq8_order, ix->generic, 0});
   int W = search_waves(p);
   while (W > 1 && static_cast<uint64_t>(W) > nq) W /= 2;
   p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k);
-  const size_t traversal_lds = search_wave_lds_bytes(ix->stride, ef, p.hash_log2, p.vis_rbits != kVisWide, 0);
+  const size_t traversal_lds = search_wave_lds_bytes(ix->stride, ef, p.hash_log2, p.vis_rbits != kVisWide, p.sq8_order);
   p.wave_lds = static_cast<uint32_t>(traversal_lds + filter_result_lds_bytes(k));
   FilterParams f{};
   f.allow = d_allow;
@@ -756,10 +773,12 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   f.mask_words = static_cast<uint32_t>((ix->n + 31) / 32);
   f.k = k;
   f.result_off = static_cast<uint32_t>(traversal_lds);
-  const size_t lds = static_cast<size_t>(W) * p.wave_lds;
+  const size_t lds = search_shared_lds_bytes(ix->stride, sq8) + static_cast<size_t>(W) * p.wave_lds;
   if (lds > kLdsPerCu) throw ArgError("filtered search: k / ef / dim too large for the LDS budget");
   int per_cu = 0;
-  hip_check(filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu), "occupancy");
+  hip_check(sq8 ? filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, lds, &per_cu)
+                : filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu),
+            "occupancy");
   per_cu = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(per_cu, max_search_waves_per_cu() / W)));
   const uint64_t cus = static_cast<uint64_t>(stream_cus(ix, stream));
   int grid = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>((nq + W - 1) / W, static_cast<uint64_t>(per_cu) * cus)));
@@ -781,7 +800,8 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   ix->work.reserve(4);
   p.work_counter = ix->work.as<uint32_t>();
   hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
-  hip_check(launch_filtered_search(p, f, grid, W, lds, stream), "filtered search launch");
+  hip_check(sq8 ? launch_filtered_sq8_search(p, f, grid, W, lds, stream) : launch_filtered_search(p, f, grid, W, lds, stream),
+            "filtered search launch");
   scratch_release(ix, stream);
 }
 
@@ -2210,6 +2230,107 @@ int alaya_index_shard_search_sq8_device(alaya_index *ix, const float *d_queries,
     set_device(ix);
     sq8_search_dev(ix, d_queries, d_rerank_queries, nq, k, ef, 1, d_ids, d_dists, d_counters,
                    static_cast<hipStream_t>(stream), holds_row0 ? 1 : 0);
+  });
+}
+
+// Filtered SQ8 search on device buffers: the search stage leaves every query's candidate pool (m ids by code
+// distance, kEmpty past the pool) in ix->sq_ids; the rerank rescores those rows on the f32 base against d_rq and
+// writes the first k under (exact distance, id), empty slots (kEmpty, FLT_MAX).  No id-0 entries, no zero fill.
+static void filtered_sq8_dev(alaya_index *ix, const float *d_q, const float *d_rq, uint64_t nq, uint32_t k, uint32_t ef,
+                             uint32_t pool, const uint32_t *d_allow, const uint32_t *d_mask_of_query, uint32_t *d_ids,
+                             float *d_dists, uint32_t *d_cnt, hipStream_t s) {
+  if (!ix->has_sq8) throw ArgError("index has no SQ8 codes");
+  if (ef == 0) throw ArgError("ef must be >= 1");
+  if (k == 0 || k > 224) throw ArgError("filtered search: k must be in 1..224");
+  const uint32_t m = pool ? pool : std::min<uint32_t>(224, std::max(k, ef));  // default: the whole traversal pool
+  if (m > 224) throw ArgError("filtered search: pool must be in 1..224");
+  if (m < k) throw ArgError("filtered search: pool must be at least k");
+  if (nq == 0) return;
+  ix->sq_ids.reserve(nq * m * 4);
+  ix->sq_d.reserve(nq * m * 4);
+  do_filtered_search(ix, d_q, nq, m, ef, d_allow, d_mask_of_query, ix->sq_ids.as<uint32_t>(), ix->sq_d.as<float>(), d_cnt, s,
+                     true);
+  // diagnostics (ALAYA_FILTER_RERANK=0, include/alaya_hip.h): the search stage alone, to time it; ids / dists
+  // are then not written
+  if (const char *e = std::getenv("ALAYA_FILTER_RERANK"))
+    if (std::atoi(e) == 0) return;
+  SearchParams p = base_params(ix);
+  p.queries = d_rq ? d_rq : d_q;
+  p.nq = nq;
+  p.q_stride = ix->dim;
+  alaya_amd::RerankParams r{};
+  r.search_ids = ix->sq_ids.as<uint32_t>();
+  r.k = k;
+  r.n_src = m;
+  r.n_take = m;
+  r.zeros = 0u;
+  r.fill_id = 0xffffffffu;
+  r.out_ids = d_ids;
+  r.out_dists = d_dists;
+  hip_check(alaya_amd::launch_rerank(p, r, s), "rerank launch");
+  scratch_release(ix, s);  // the rerank read the candidates from the index's sq_ids buffer
+}
+
+int alaya_index_filtered_search_sq8_device(alaya_index *ix, const float *d_queries, const float *d_rerank_queries,
+                                           uint64_t nq, uint32_t k, uint32_t ef, uint32_t pool,
+                                           const uint32_t *d_allow_words, uint32_t n_masks,
+                                           const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
+                                           uint32_t *d_counters, void *stream) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (nq && (!d_queries || !d_ids || !d_allow_words))) throw ArgError("invalid arguments");
+    if (nq && (n_masks == 0 || (n_masks > 1 && !d_mask_of_query)))
+      throw ArgError("filtered search: mask_of_query may be null only with one mask");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    filtered_sq8_dev(ix, d_queries, d_rerank_queries, nq, k, ef, pool, d_allow_words, d_mask_of_query, d_ids, d_dists,
+                     d_counters, static_cast<hipStream_t>(stream));
+  });
+}
+
+int alaya_index_filtered_search_sq8(alaya_index *ix, const float *queries, const float *rerank_queries, uint64_t nq,
+                                    uint32_t k, uint32_t ef, uint32_t pool, const uint32_t *allow_words, uint32_t n_masks,
+                                    const uint32_t *mask_of_query, uint32_t *ids, float *dists, uint32_t *counters) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (nq && (!queries || !ids || !allow_words))) throw ArgError("invalid arguments");
+    if (nq && (n_masks == 0 || (n_masks > 1 && !mask_of_query)))
+      throw ArgError("filtered search: mask_of_query may be null only with one mask");
+    if (mask_of_query)
+      for (uint64_t i = 0; i < nq; ++i)
+        if (mask_of_query[i] >= n_masks) throw ArgError("filtered search: mask_of_query holds an index past n_masks");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    if (k == 0 || k > 224) throw ArgError("filtered search: k must be in 1..224");
+    if (nq == 0) return;
+    const size_t mask_bytes = static_cast<size_t>(n_masks) * ((ix->n + 31) / 32) * 4;
+    ix->q_buf.reserve(nq * ix->dim * 4);
+    ix->id_buf.reserve(nq * k * 4);
+    ix->dist_buf.reserve(nq * k * 4);
+    ix->cnt_buf.reserve(nq * 16);
+    ix->allow_buf.reserve(mask_bytes);
+    ix->group_buf.reserve(nq * 4);
+    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
+              "upload queries");
+    const float *d_rq = nullptr;
+    if (rerank_queries && rerank_queries != queries) {
+      ix->rr_q_buf.reserve(nq * ix->dim * 4);
+      hip_check(hipMemcpyAsync(ix->rr_q_buf.ptr, rerank_queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
+                "upload rerank queries");
+      d_rq = ix->rr_q_buf.as<float>();
+    }
+    hip_check(hipMemcpyAsync(ix->allow_buf.ptr, allow_words, mask_bytes, hipMemcpyHostToDevice, ix->stream),
+              "upload masks");
+    if (mask_of_query)
+      hip_check(hipMemcpyAsync(ix->group_buf.ptr, mask_of_query, nq * 4, hipMemcpyHostToDevice, ix->stream),
+                "upload mask indices");
+    filtered_sq8_dev(ix, ix->q_buf.as<float>(), d_rq, nq, k, ef, pool, ix->allow_buf.as<uint32_t>(),
+                     mask_of_query ? ix->group_buf.as<uint32_t>() : nullptr, ix->id_buf.as<uint32_t>(),
+                     ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream);
+    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    if (dists)
+      hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    if (counters)
+      hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    hip_check(hipStreamSynchronize(ix->stream), "filtered sq8 search");
   });
 }
 

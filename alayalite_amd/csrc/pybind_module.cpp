@@ -267,12 +267,16 @@ class PyIndexInterface : public LaunchControls {
   // --- extra (not in the reference binding): the topk nearest rows among those a mask allows
   // (alaya_index_filtered_search).  allow_words: uint32 [n_masks, ceil(n / 32)] (utils.pack_allow);
   // mask_of_query: each query's mask, or None with one mask.  Empty slots as exact_search's.
+  // SQ8 indexes run alaya_index_filtered_search_sq8 with batch_search's two query forms; pool: its
+  // candidate pool (0 = the default), which an unquantized index does not have.
   py::object filtered_search(py::array queries, uint32_t topk, uint32_t ef,
                              py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
-                             py::object mask_of_query) {
+                             py::object mask_of_query, uint32_t pool) {
     if (!graph_) throw std::runtime_error("Index is not init yet");
-    if (params_.quantization_type_ != QuantizationType::NONE)
-      throw std::runtime_error("filtered_search on quantized indexes is not supported by the MI355X engine");
+    const bool sq8 = params_.quantization_type_ == QuantizationType::SQ8;
+    if (!sq8 && params_.quantization_type_ != QuantizationType::NONE)
+      throw std::runtime_error("filtered_search: the MI355X engine has float32 and SQ8 indexes only");
+    if (!sq8 && pool != 0) throw py::value_error("pool applies to SQ8 indexes only");
     py::array q = prepare_queries(queries);
     const uint64_t nq = q.shape(0);
     if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n_ + 31) / 32 || allow_words.shape(0) < 1)
@@ -290,7 +294,14 @@ class PyIndexInterface : public LaunchControls {
     last_counters_.assign(nq * 4, 0);
     const uint32_t *ap = allow_words.data();
     const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
-    {
+    if (sq8) {
+      // the traversal encodes the query as given, the rerank's f32 distance takes the normalised one (run())
+      const float *rq = static_cast<const float *>(q.data());
+      const float *sq = raw_queries_.empty() ? rq : raw_queries_.data();
+      py::gil_scoped_release nogil;
+      check(alaya_index_filtered_search_sq8(ix_, sq, rq, nq, topk, ef, pool, ap, n_masks, gp, ids32.data(),
+                                            dists.mutable_data(), last_counters_.data()));
+    } else {
       py::gil_scoped_release nogil;
       check(alaya_index_filtered_search(ix_, static_cast<const float *>(q.data()), nq, topk, ef, ap, n_masks, gp,
                                         ids32.data(), dists.mutable_data(), last_counters_.data()));
@@ -929,6 +940,56 @@ class DeviceIndex : public LaunchControls {
                                              reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
                                              reinterpret_cast<uint32_t *>(counters), reinterpret_cast<void *>(stream)));
   }
+  // the same over the index's SQ8 codes, reranked on the f32 rows (alaya_index_filtered_search_sq8); pool: the
+  // candidate pool's capacity, 0 = min(224, max(k, ef)); rerank_queries: None = queries
+  py::tuple filtered_search_sq8(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
+                                py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
+                                py::object mask_of_query, uint32_t pool, py::object rerank_queries) {
+    const uint64_t nq = q.shape(0);
+    uint64_t n = 0;
+    check(alaya_index_info(ix_, &n, nullptr, nullptr, nullptr, nullptr));
+    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n + 31) / 32 || allow_words.shape(0) < 1)
+      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
+    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
+    const uint32_t *gp = nullptr;
+    if (!mask_of_query.is_none()) {
+      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
+      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
+        throw py::value_error("mask_of_query must hold one index per query");
+      gp = groups.data();
+    }
+    py::array_t<float, py::array::c_style | py::array::forcecast> rq;
+    const float *rqp = nullptr;
+    if (!rerank_queries.is_none()) {
+      rq = py::array_t<float, py::array::c_style | py::array::forcecast>(rerank_queries);
+      if (rq.ndim() != 2 || rq.shape(0) != q.shape(0) || rq.shape(1) != q.shape(1))
+        throw py::value_error("rerank_queries must have the queries' shape");
+      rqp = rq.data();
+    }
+    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
+    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
+    py::array_t<uint32_t> c({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(4)});
+    const float *qp = q.data();
+    const uint32_t *ap = allow_words.data();
+    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
+    uint32_t *ip = ids.mutable_data();
+    float *dp = d.mutable_data();
+    uint32_t *cp = c.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_filtered_search_sq8(ix_, qp, rqp, nq, k, ef, pool, ap, n_masks, gp, ip, dp, cp));
+    }
+    return py::make_tuple(ids, d, c);
+  }
+  void filtered_search_sq8_device(uintptr_t q, uintptr_t rq, uint64_t nq, uint32_t k, uint32_t ef, uint32_t pool,
+                                  uintptr_t allow_words, uint32_t n_masks, uintptr_t mask_of_query, uintptr_t ids,
+                                  uintptr_t dists, uintptr_t counters, uintptr_t stream) {
+    check(alaya_index_filtered_search_sq8_device(ix_, reinterpret_cast<const float *>(q), reinterpret_cast<const float *>(rq),
+                                                 nq, k, ef, pool, reinterpret_cast<const uint32_t *>(allow_words), n_masks,
+                                                 reinterpret_cast<const uint32_t *>(mask_of_query),
+                                                 reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
+                                                 reinterpret_cast<uint32_t *>(counters), reinterpret_cast<void *>(stream)));
+  }
   void shard_search_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t ids, uintptr_t dists,
                            uintptr_t counters, uintptr_t stream) {
     check(alaya_index_shard_search_device(ix_, reinterpret_cast<const float *>(q), nq, k, ef,
@@ -1100,7 +1161,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("load", &PyIndexInterface::load, py::arg("index_path"), py::arg("data_path"),
            py::arg("quant_path") = std::string())
       .def("filtered_search", &PyIndexInterface::filtered_search, py::arg("queries"), py::arg("topk"), py::arg("ef"),
-           py::arg("allow_words"), py::arg("mask_of_query") = py::none())
+           py::arg("allow_words"), py::arg("mask_of_query") = py::none(), py::arg("pool") = 0)
       .def("get_data_dim", &PyIndexInterface::get_data_dim)
       .def("get_data_num", &PyIndexInterface::get_data_num)
       .def("last_counters", &PyIndexInterface::last_counters)
@@ -1138,6 +1199,10 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("filtered_search", &DeviceIndex::filtered_search, py::arg("queries"), py::arg("k"), py::arg("ef"),
            py::arg("allow_words"), py::arg("mask_of_query") = py::none())
       .def("filtered_search_device", &DeviceIndex::filtered_search_device)
+      .def("filtered_search_sq8", &DeviceIndex::filtered_search_sq8, py::arg("queries"), py::arg("k"), py::arg("ef"),
+           py::arg("allow_words"), py::arg("mask_of_query") = py::none(), py::arg("pool") = 0,
+           py::arg("rerank_queries") = py::none())
+      .def("filtered_search_sq8_device", &DeviceIndex::filtered_search_sq8_device)
       .def("shard_search_device", &DeviceIndex::shard_search_device)
       .def("distances", &DeviceIndex::distances)
       .def("set_hash_log2", &DeviceIndex::set_hash_log2)

@@ -200,6 +200,13 @@ size_t filter_result_lds_bytes(uint32_t k);
 hipError_t filtered_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);
 hipError_t launch_filtered_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
                                   hipStream_t stream);
+// Filtered search of SQ8 codes (filtered_sq8_search_kernel): f.k = p.k = m, the candidate pool's capacity
+// (filter_result_lds_bytes(m) at the end of p.wave_lds); p is planned as the plain (mode 0) SQ8 search of
+// the shape and p.out_ids receives nq x m candidate ids, kEmpty in empty slots, for launch_rerank.
+hipError_t filtered_sq8_search_occupancy(uint32_t dim, int sq8_order, bool ip, int waves, size_t lds,
+                                         int *blocks_per_cu);
+hipError_t launch_filtered_sq8_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
+                                      hipStream_t stream);
 // out[q * n + i] = dist(queries[q], base[ids[i]]) for q < nq (bit-exact device distance)
 hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint32_t n,
                                 uint32_t nq, float *out, hipStream_t stream);

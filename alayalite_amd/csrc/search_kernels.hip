@@ -1780,4 +1780,172 @@ hipError_t filtered_search_occupancy(uint32_t dim, bool generic, bool ip, int wa
                                                       lds);
 }
 
+// --------------------------------------------------------------------------------------------
+// Filtered search of SQ8 codes: the traversal of hnsw_search_kernel's plain (mode 0) SQ8 searcher -- the
+// query encoded to codes, code-to-code distances without a validity test, the spill levels and their
+// prefetch -- plus the candidate pool: a second LinearPool of capacity f.k = m per wave that is offered
+// every (id, code distance) the traversal hands to pool.insert, in that order, whose row is valid and
+// allowed by the query's mask.  The traversal pool, the visited set, every pop and the four counters
+// are those of the unfiltered SQ8 search at the same ef.  The output is the candidate pool's ids, then
+// kEmpty: launch_rerank rescores them on the f32 rows.  Four waves per workgroup share the quantizer's
+// scale / min; they meet once, in fill_shared, before any wave draws a query.  The candidate pool sits
+// at f.result_off of the wave's LDS region, past the visited table (carve_lds is unchanged).
+// --------------------------------------------------------------------------------------------
+namespace {
+// candidates.insert(id, d) for the lanes with `allowed`, in lane order: result_offer with the validity bitmap
+// read last, and only when some allowed lane's distance can enter the pool -- rarely once the pool is full --
+// so no validity word is live across the distance pass of a kernel that is at its register budget.
+// (Dropping the lanes that `full && d >= worst` rejects before the merge changes nothing: the merge rejects
+// them by the same test.)
+__device__ __forceinline__ void candidate_offer(const SearchParams &p, PoolState &rs, const Lds &Lr, bool allowed, uint32_t id,
+                                                float d) {
+  const bool full = rs.size == rs.ef;
+  const float worst = full ? Lr.pd[rs.size - 1] : 0.f;
+  bool ok = allowed && !(full && d >= worst);
+  if (ballot(ok) == 0ull) return;
+  if (p.valid != nullptr && ok) ok = ((p.valid[id >> 5] >> (id & 31)) & 1u) != 0u;
+  pool_merge(rs, Lr, ok, id, d);
+}
+
+template <bool kIP, int kChunks, int kSpace>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(search_min_waves<kChunks, kSpace, 0>() ? search_min_waves<kChunks, kSpace, 0>() : 1, 8)))
+    filtered_sq8_search_kernel(SearchParams p, FilterParams f) {
+  static_assert(space_sq8<kSpace>(), "SQ8 codes");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr bool kTab = space_tab<kSpace>();
+  const int lane = lane_id();
+  const int wave = static_cast<int>(threadIdx.x >> 6);
+  const int W = static_cast<int>(blockDim.x >> 6);
+  const Lds L = carve_lds<kSpace>(p, smem, wave);
+  fill_shared<kSpace>(p, L);  // the workgroup's only barrier: every wave passes it, with or without a query
+  const Lds Lr = result_lds(L, f);
+  const uint64_t bit_words = (p.n + 31) / 32;
+  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * W + wave;
+  uint32_t *slot_bits = p.overflow_bits + slot * bit_words;
+  uint32_t *slot_dirty = p.dirty_words + slot * p.dirty_cap;
+  uint16_t *slot_stab = (kTab && p.spill_table) ? p.spill_table + (slot << p.stab_log2) : nullptr;
+
+  for (;;) {
+    uint32_t qi = 0;
+    if (lane == 0) qi = atomicAdd(p.work_counter, 1u);
+    qi = read_lane(qi, 0);
+    if (qi >= p.nq) break;
+    // the query's mask; a row is allowed if its bit is set and (indexes with a bitmap) it is valid
+    const uint32_t *mask = f.allow + static_cast<uint64_t>(f.mask_of_query != nullptr ? f.mask_of_query[qi] : 0u) * f.mask_words;
+    for (uint32_t e = lane; e <= f.k; e += 64) {
+      Lr.pd[e] = 0.f;
+      Lr.pi[e] = 0u;
+    }
+    PoolState rs{0u, 0u, f.k};
+    Visited vs;
+    PoolState ps;
+    uint32_t n_dist = 0, n_expand = 0, n_dist_up = 0, n_hops_up = 0;
+    // (query_begin's first wave_sync orders the reset above before any offer)
+    query_begin<kIP, kChunks, kSpace>(p, L, qi, slot_bits, slot_dirty, slot_stab, vs, ps, n_dist_up, n_hops_up,
+                                      [&](bool has, uint32_t id, float d) {
+                                        const bool allowed = has && ((mask[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                        candidate_offer(p, rs, Lr, allowed, id, d);
+                                      });
+
+    // ---- best-first expansion: the plain SQ8 searcher's loop ----------------------------------
+    uint32_t pred = kEmpty, pred_v = kEmpty;  // adjacency prefetch of the predicted next pop
+    uint32_t pre_u = kEmpty;                  // second-level state read one expansion ahead (spill_prefetch)
+    uint64_t pre_lo = 0ull, pre_hi = 0ull;
+    while (ps.cur < ps.size) {
+      const uint32_t u = pool_pop(ps, L);
+      ++n_expand;
+      uint32_t v = u == pred ? pred_v : adjacency_row(p, static_cast<int>(p.R), u);
+      const int cnt = adjacency_count(static_cast<int>(p.R), v);
+      bool act = lane < cnt;
+      if (p.dedup_edges) {  // graphs with repeated ids in a row: keep the first occurrence only
+        for (int j = 0; j < cnt; ++j) {
+          const uint32_t vj = read_lane(v, j);
+          if (j < lane && vj == v) act = false;
+        }
+      }
+      if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin<kTab>(vs);
+      const bool fresh = visit<kTab>(vs, v, act, u == pre_u, pre_lo, pre_hi);
+      // the pred_v load below issues after this visit's spill-table stores and bitset atomics: the
+      // second-level prefetch's wait for pred_v is its wait for them (as in hnsw_search_kernel)
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" ::: "memory");
+      pre_u = kEmpty;  // consumed: the prefetched state describes the table only up to this visit's stores
+      pre_lo = pre_hi = 0ull;
+      const uint64_t fm = ballot(fresh);
+      const int nf = __popcll(fm);
+      pred = ps.cur < ps.size ? (L.pi[ps.cur] & kIdMask) : kEmpty;
+      if (pred != kEmpty) pred_v = adjacency_row(p, static_cast<int>(p.R), pred, pred_v);
+      if (nf == 0) continue;
+      // compact fresh ids in adjacency order
+      if (fresh) L.cid[__popcll(fm & ((1ull << lane) - 1ull))] = v;
+      wave_sync();
+      // each candidate's allow word goes out ahead of the code rows, by the lane that will hold the
+      // candidate at the merges; it is used only after the distances, so its latency is the rows'
+      const bool has = lane < nf;
+      uint32_t aw = 0u;
+      if (has) aw = mask[L.cid[lane] >> 5];
+      space_distances<kIP, kChunks, kSpace>(p, L, L.cid, nf, L.cd, [&]() {
+        // the predicted next expansion's second-level state, behind this expansion's first row pass
+        if (vs.spilled && pred != kEmpty && !(p.spill_flags & 1u)) {
+          spill_prefetch(vs, pred_v, lane < static_cast<int>(p.R), pre_lo, pre_hi);
+          pre_u = pred;
+        }
+      });
+      n_dist += nf;
+      const uint32_t cid = has ? L.cid[lane] : 0u;
+      const float cd = has ? L.cd[lane] : 0.f;
+      wave_sync();
+      pool_merge(ps, L, has, cid, cd, [&](uint32_t nx) {
+        if (nx != pred) {
+          pred = nx;
+          pred_v = adjacency_row(p, static_cast<int>(p.R), nx, pred_v);
+        }
+      });
+      candidate_offer(p, rs, Lr, has && ((aw >> (cid & 31)) & 1u) != 0u, cid, cd);
+    }
+
+    query_end(p, Lr, rs, qi, n_dist, n_expand, n_dist_up, n_hops_up);
+    visit_end(vs);
+    wave_sync();
+  }
+}
+}  // namespace
+
+// The filtered SQ8 kernels: {L2, IP} x the code order x the plain SQ8 kernels' widths (the mode-0 SQ8
+// rows of search_variants.h); any other width runs the runtime-d kernel (chunks 0).
+template <int kSpace, int... kChunks>
+static const void *filtered_sq8_symbol_of(int chunks, bool ip) {
+  const void *sym = nullptr;
+  ((chunks == kChunks ? (sym = ip ? reinterpret_cast<const void *>(&filtered_sq8_search_kernel<true, kChunks, kSpace>)
+                                  : reinterpret_cast<const void *>(&filtered_sq8_search_kernel<false, kChunks, kSpace>),
+                         0)
+                      : 0),
+   ...);
+  return sym;
+}
+
+static const void *filtered_sq8_kernel_symbol(uint32_t dim, int sq8_order, bool ip) {
+  const int chunks = search_chunks(dim, false);
+  const void *sym = sq8_order == 2 ? filtered_sq8_symbol_of<2, 4, 24, 30>(chunks, ip)
+                                   : filtered_sq8_symbol_of<1, 4, 24, 30>(chunks, ip);
+  if (sym != nullptr) return sym;
+  return sq8_order == 2 ? filtered_sq8_symbol_of<2, 0>(0, ip) : filtered_sq8_symbol_of<1, 0>(0, ip);
+}
+
+hipError_t launch_filtered_sq8_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
+                                      hipStream_t stream) {
+  SearchParams arg = p;
+  FilterParams farg = f;
+  void *args[] = {&arg, &farg};
+  return hipLaunchKernel(filtered_sq8_kernel_symbol(p.dim, p.sq8_order, p.ip), dim3(grid), dim3(64 * waves), args, lds,
+                         stream);
+}
+
+hipError_t filtered_sq8_search_occupancy(uint32_t dim, int sq8_order, bool ip, int waves, size_t lds,
+                                         int *blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, filtered_sq8_kernel_symbol(dim, sq8_order, ip),
+                                                      64 * waves, lds);
+}
+
 }  // namespace alaya_amd

@@ -114,16 +114,28 @@ class Index:
         _assert(self.__index is not None, "Index is not init yet")
         return self.__index.get_data_num()
 
-    def filtered_search(self, queries: VectorLikeBatch, topk: int, ef_search: int = 100, allow=None, groups=None):
+    def filtered_search(self, queries: VectorLikeBatch, topk: int, ef_search: int = 100, allow=None, groups=None,
+                        rerank_pool=None):
         """The ``topk`` nearest rows among those a mask allows.  The graph traversal is ``batch_search``'s
         at ``ef_search``; every distance it computes for a valid, allowed row is offered to a result
         pool of ``topk`` entries, so the answer draws on all of them and not only on the ``ef_search``
         rows the traversal keeps.  ``allow``: bool array of shape (n,), n = ``get_data_num()``, or
         (G, n) with ``groups`` of shape (nq,), the mask (an int below G) of each query.  Returns
         (ids, distances); slots the allowed rows did not fill hold (the id type's maximum, FLT_MAX).
-        1 <= topk <= 224; float32 rows without quantization."""
+        1 <= topk <= 224.
+
+        An SQ8 index traverses its codes, as its ``batch_search`` does, keeps the ``rerank_pool``
+        allowed rows nearest by code distance (``topk <= rerank_pool <= 224``; None =
+        ``min(224, max(topk, ef_search))``) and returns the ``topk`` of them nearest by exact float32
+        distance, ties by id; the distances returned are the exact ones.  On an unquantized index
+        ``rerank_pool`` must stay None."""
         self._check_queries(queries, 2, "queries")
         _assert(allow is not None, "allow is required")
+        pool = 0
+        if rerank_pool is not None:
+            _assert((self.__params.quantization_type or "none").lower() == "sq8", "rerank_pool applies to SQ8 indexes only")
+            pool = int(rerank_pool)
+            _assert(topk <= pool <= 224, "rerank_pool must be in topk..224")
         allow = np.asarray(allow)
         _assert(allow.ndim in (1, 2), "allow must have shape (n,) or (G, n)")
         words = pack_allow(allow, self.get_data_num())
@@ -136,7 +148,7 @@ class Index:
             _assert(groups.size == 0 or (groups.min() >= 0 and groups.max() < words.shape[0]),
                     "groups must be below the number of masks")
             groups = np.ascontiguousarray(groups, np.uint32)
-        return self.__index.filtered_search(queries, topk, ef_search, words, groups)
+        return self.__index.filtered_search(queries, topk, ef_search, words, groups, pool)
 
     def save(self, url) -> dict:
         os.makedirs(url, exist_ok=True)

@@ -144,6 +144,20 @@ def merge_reference(ids_per_shard, dists_per_shard, offsets, k):
     return out_i, out_d
 
 
+def shard_allow_words(allow, lo: int, hi: int):
+    """The words a shard holding rows [lo, hi) reads for a global ``filtered_search`` mask:
+    ``pack_allow`` of the mask's columns lo..hi, uint32 [G, ceil((hi - lo) / 32)] -- bit i % 32 of word
+    i // 32 = global row lo + i.  ``allow``: (n_total,) or (G, n_total)."""
+    from .utils import pack_allow
+
+    a = np.asarray(allow)
+    if a.ndim not in (1, 2):
+        raise ValueError(f"allow must have shape (n,) or (G, n), got {a.shape}")
+    if not 0 <= lo <= hi <= a.shape[-1]:
+        raise ValueError(f"rows [{lo}, {hi}) are not a range of the mask's {a.shape[-1]} rows")
+    return pack_allow(a[..., lo:hi], hi - lo)
+
+
 def shard_search(index, lo: int, sq8: bool, q_dev, k: int, ef: int, ids_dev, dists_dev, counters_dev, stream,
                  rq_dev=None):
     """One shard's search of a device query batch into device buffers (asynchronous on `stream`, a
@@ -341,11 +355,51 @@ class ShardedIndex:
         shard_search(self.index, self.lo, self.sq8 is not None, q_dev, k, ef, ids_dev, dists_dev, counters_dev,
                      stream, rq_dev)
 
-    def filtered_search(self, *args, **kwargs):
-        """Not built: a mask covers the whole base's rows, a shard holds a range of them, and the
-        cross-shard merge has no filtered form yet."""
-        raise NotImplementedError("filtered_search is not supported on a sharded index; use Index.filtered_search "
-                                  "on an unsharded one")
+    def filtered_search(self, q_dev, k: int, ef: int, allow, stream, groups=None, group=None, rerank_pool=None,
+                        rq_dev=None):
+        """The k nearest rows of the whole base among those a mask allows, merged over the shards.
+        ``allow`` is the global mask, identical on every rank: bool of shape (n_total,), or (G, n_total)
+        with ``groups`` of shape (nq,), each query's mask.  This shard packs its own columns
+        (``shard_allow_words``) and runs its filtered search -- f32 shards ``filtered_search_device``, SQ8
+        shards ``filtered_search_sq8_device`` on the shard's own SQ8 space with a candidate pool of
+        ``rerank_pool`` (None = the default; f32 shards take None only) -- then local ids become global
+        and ``exchange_and_merge`` keeps the first k by (distance, global id); empty slots sort last.
+        ``group``: the process group of the exchange; ``rq_dev``: SQ8 rerank queries, None = q_dev."""
+        import torch
+
+        nq = q_dev.shape[0]
+        if self.sq8 is None and rerank_pool is not None:
+            raise ValueError("rerank_pool applies to SQ8 shards only")
+        words = torch.from_numpy(shard_allow_words(allow, self.lo, self.hi).view(np.int32)).to(q_dev.device)
+        if groups is None:
+            if words.shape[0] != 1:
+                raise ValueError("groups is required with more than one mask")
+            gptr = 0
+        else:
+            g = np.ascontiguousarray(np.asarray(groups))
+            if g.shape != (nq,) or not np.issubdtype(g.dtype, np.integer):
+                raise ValueError("groups must be integers of shape (nq,)")
+            if g.size and (g.min() < 0 or g.max() >= words.shape[0]):
+                raise ValueError("groups must be below the number of masks")
+            g_dev = torch.from_numpy(g.astype(np.int32)).to(q_dev.device)
+            gptr = g_dev.data_ptr()
+        ids = torch.empty((nq, k), dtype=torch.int32, device=q_dev.device)
+        d = torch.empty((nq, k), dtype=torch.float32, device=q_dev.device)
+        c = torch.empty((nq, 4), dtype=torch.int32, device=q_dev.device)
+        # the masks were uploaded on torch's current stream and the search runs on `stream`: the uploads end
+        # before the launch, and the search before the masks are freed (ShardPipeline integration would keep
+        # them in its slots instead)
+        torch.cuda.synchronize(q_dev.device)
+        if self.sq8 is not None:
+            self.index.filtered_search_sq8_device(q_dev.data_ptr(), 0 if rq_dev is None else rq_dev.data_ptr(), nq, k, ef,
+                                                  0 if rerank_pool is None else int(rerank_pool), words.data_ptr(),
+                                                  words.shape[0], gptr, ids.data_ptr(), d.data_ptr(), c.data_ptr(), stream)
+        else:
+            self.index.filtered_search_device(q_dev.data_ptr(), nq, k, ef, words.data_ptr(), words.shape[0], gptr,
+                                              ids.data_ptr(), d.data_ptr(), c.data_ptr(), stream)
+        torch.cuda.synchronize(q_dev.device)
+        self.last_local = (ids, d, c)  # this shard's own answer (tests, diagnostics)
+        return exchange_and_merge(ids, d, self.lo, k, group)
 
     def search(self, q_dev, k: int, ef: int, stream, group=None):
         import torch

@@ -125,7 +125,7 @@ int alaya_index_shard_search_device(alaya_index *ix, const float *d_queries, uin
                                     uint32_t ef, uint32_t *d_ids, float *d_dists, uint32_t *d_counters,
                                     void *stream);
 /* Filtered graph search: the k nearest rows among those a per-query mask allows (f32 rows; an index
- * with SQ8 codes is refused).  The traversal is alaya_index_batch_search's at the same ef -- the same
+ * with SQ8 codes is refused here and served by alaya_index_filtered_search_sq8 below).  The traversal is alaya_index_batch_search's at the same ef -- the same
  * overlay descent, pool of capacity ef, visited set and pops, so the four counters are the same --
  * and beside it a second pool of capacity k, the result pool, is offered every (id, distance) the
  * traversal hands to its own pool, in that order, whose row is valid and allowed.  ids / dists hold
@@ -144,6 +144,36 @@ int alaya_index_filtered_search_device(alaya_index *ix, const float *d_queries, 
                                        const uint32_t *d_allow_words, uint32_t n_masks,
                                        const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
                                        uint32_t *d_counters, void *stream);
+/* Filtered graph search of an index with SQ8 codes (alaya_index_set_sq8): the k nearest rows, by exact
+ * f32 distance, among the candidates a filtered SQ8 traversal collects.
+ *   1. Traversal: alaya_index_batch_search_sq8's at the same ef -- the query encoded to codes, code-to-code
+ *      distances (no validity test in the distance: removed rows are traversed like any other), the same
+ *      overlay descent, pool of capacity ef, visited set and pops; the four counters are those of
+ *      alaya_index_batch_search_sq8(..., rerank = 0).
+ *   2. Candidate pool: a second pool of capacity m = `pool`, k <= m <= 224, is offered every (id, code
+ *      distance) the traversal hands to its own pool, in that order, whose row is valid and allowed.
+ *      pool = 0 means min(224, max(k, ef)): the whole traversal pool, under the cap.
+ *   3. Rerank: the candidates are rescored with the f32 distance of rerank_queries (NULL = queries) to their
+ *      f32 rows; ids / dists hold the first k under (exact distance, id), equal pairs in pool order, then
+ *      empty slots (0xffffffff, FLT_MAX).  No id-0 entries and no zero fill (this is not
+ *      alaya_index_batch_search_sq8's reference rerank); a candidate the traversal met twice stays twice.
+ * A larger m costs candidate-pool merges in the search stage and m row reads in the rerank, and buys
+ * candidates whose code distance misorders them against the k-th exact one.  allow_words, n_masks,
+ * mask_of_query and ALAYA_FILTER_GRID as for alaya_index_filtered_search.  For the COS metric the callers of
+ * the Index layer pass the un-normalised queries to the traversal and the normalised ones to the rerank, as
+ * for alaya_index_batch_search_sq8.  An index without SQ8 codes, k or pool outside 1..224, pool < k, ef = 0
+ * and a shape whose LDS does not fit are argument errors.  Environment ALAYA_FILTER_RERANK=0 (diagnostics, read
+ * per launch) runs the search stage alone, to time it: ids and dists are then left unwritten. */
+int alaya_index_filtered_search_sq8(alaya_index *ix, const float *queries, const float *rerank_queries, uint64_t nq,
+                                    uint32_t k, uint32_t ef, uint32_t pool, const uint32_t *allow_words,
+                                    uint32_t n_masks, const uint32_t *mask_of_query, uint32_t *ids, float *dists,
+                                    uint32_t *counters);
+/* Same on device buffers, asynchronous on `stream`; the indices of d_mask_of_query are not checked. */
+int alaya_index_filtered_search_sq8_device(alaya_index *ix, const float *d_queries, const float *d_rerank_queries,
+                                           uint64_t nq, uint32_t k, uint32_t ef, uint32_t pool,
+                                           const uint32_t *d_allow_words, uint32_t n_masks,
+                                           const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
+                                           uint32_t *d_counters, void *stream);
 /* ---- device graph construction (Index.fit on the MI355X) ------------------------------------
  * Replaces HNSWBuilder::build_graph (include/index/graph/hnsw/hnsw_builder.hpp:98-194) over hnswlib
  * add_point (include/index/graph/hnsw/hnswlib.hpp:652-751), from the index's own rows

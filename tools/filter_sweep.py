@@ -12,6 +12,16 @@ usage: python tools/filter_sweep.py [--leg sweep|filtered|plain] [--n 1000000] [
   plain     the plain search (k = 10) alone: its time.  With ALAYA_AB_ROOT=<a saved build of the package>
             this runs another build's kernel -- the parent commit's, which has no filtered search -- on
             the same rows, graph (the device build is deterministic) and queries.
+  sq8       the config-5 shape (768-d IP text-like unit-sphere rows, SQ8 codes + f32 rerank, device-built
+            graph; --n 1000000 --dim 768 are this leg's defaults): ef is the smallest of --ef-ladder at
+            which batch search (SQ8 + reference rerank) reaches recall@10 0.95 (--ef N skips the ladder),
+            then per share and per candidate pool m in k, 4k, 224: queries/s of
+            DeviceIndex.filtered_search_sq8_device, the search stage's ms (ALAYA_FILTER_RERANK=0), the
+            rerank's ms (the difference), recall@10 over the allowed rows against the exact IP top-10 on
+            base[allow], and the recall of post-filtering batch_search's ef ids.
+  sq8-ab    the all-ones filtered SQ8 launch, search stage only, against search_sq8(rerank = 0) of the
+            same process with ALAYA_HELPERS=0 (the plain mode-0 kernel the filtered one is built from):
+            --rounds alternated rounds of --reps launches each; medians and spreads.
 Every leg prints one JSON line per measurement; --out appends them to a file."""
 import argparse
 import json
@@ -34,17 +44,141 @@ def recall(ids, gt):
     return hits / float(sum(int((gt[i] >= 0).sum()) for i in range(len(gt))) or 1)
 
 
+def sq8_legs(args):
+    import torch
+    from alayalite_amd import _native
+    from alayalite_amd.utils import calc_gt_device, pack_allow
+    from workloads.datasets import text_like
+
+    ext = _native._ext
+    st = torch.cuda.current_stream()
+    n, nq = args.n, args.nq
+    base, queries = text_like(n, nq, dim=args.dim)
+    print(f"rows {base.shape}", file=sys.stderr, flush=True)
+    dev = ext.DeviceIndex(0)
+    dev.set_base(base, 1)
+    dev.build_graph(32, 100, 100, 0, 0, 2)
+    print("graph built", file=sys.stderr, flush=True)
+    mn, mx = ext.sq8_train(base)
+    dev.set_sq8(ext.sq8_encode(base, mn, mx, 16), mn, mx, ext.host_sq8_order())
+    print("codes set", file=sys.stderr, flush=True)
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    ids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+    dd = torch.empty((nq, K), dtype=torch.float32, device="cuda")
+    cnt = torch.empty((nq, 4), dtype=torch.int32, device="cuda")
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim, k=K, metric="ip", sq8_order=int(ext.host_sq8_order()))
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    def timed(run, reps=args.reps):
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def batch(ef, rerank, out=ids, k=K):
+        dev.search_sq8_device(qd.data_ptr(), 0, nq, k, ef, rerank, out.data_ptr(), dd.data_ptr() if k == K else 0,
+                              cnt.data_ptr(), st.cuda_stream)
+
+    def stage_only(on):
+        if on:
+            os.environ["ALAYA_FILTER_RERANK"] = "0"
+        else:
+            os.environ.pop("ALAYA_FILTER_RERANK", None)
+
+    ones = torch.from_numpy(pack_allow(np.ones(n, bool), n).view(np.int32)).cuda()
+
+    def filtered(ef, m, words):
+        dev.filtered_search_sq8_device(qd.data_ptr(), 0, nq, K, ef, m, words.data_ptr(), 1, 0, ids.data_ptr(), dd.data_ptr(),
+                                       cnt.data_ptr(), st.cuda_stream)
+
+    if args.leg == "sq8-ab":
+        ef = args.ef or 340
+        os.environ["ALAYA_HELPERS"] = "0"
+        plain_ms, filt_ms = [], []
+        for _ in range(args.rounds):  # alternated in one process: same rows, graph, queries and clocks
+            plain_ms.append(timed(lambda: batch(ef, 0)))
+            plan_plain = dev.last_plan()
+            stage_only(True)
+            filt_ms.append(timed(lambda: filtered(ef, K, ones)))
+            stage_only(False)
+            plan_filt = dev.last_plan()
+        med_p, med_f = float(np.median(plain_ms)), float(np.median(filt_ms))
+        emit(dict(leg="sq8-ab", ef=ef, pool=K, plain_ms=sorted(plain_ms), filtered_ms=sorted(filt_ms), plain_median=med_p,
+                  filtered_median=med_f, ratio=med_f / med_p, plain_spread=(max(plain_ms) - min(plain_ms)) / med_p,
+                  plain_plan={k: int(v) for k, v in plan_plain.items()}, filtered_plan={k: int(v) for k, v in plan_filt.items()}))
+        return
+
+    gt_all, _ = calc_gt_device(base, queries, K, metric="ip")
+    ef = args.ef
+    if not ef:  # the shape's recall-0.95 point of batch_search (SQ8 search + reference rerank)
+        for ef in [int(s) for s in args.ef_ladder.split(",")]:
+            batch(ef, 1)
+            torch.cuda.synchronize()
+            r = recall(ids.cpu().numpy().view(np.uint32), gt_all)
+            emit(dict(leg="sq8-ladder", ef=ef, recall_at_10=r))
+            if r >= 0.95:
+                break
+    wide = torch.empty((nq, ef), dtype=torch.int32, device="cuda")  # batch search's whole pool by code distance
+    batch(ef, 0, wide, ef)
+    torch.cuda.synchronize()
+    pool_ids = wide.cpu().numpy().view(np.uint32)
+    ms_plain = timed(lambda: batch(ef, 1))
+    emit(dict(leg="sq8-batch", ef=ef, ms=ms_plain, qps=nq / ms_plain * 1e3, plan={k: int(v) for k, v in dev.last_plan().items()}))
+    for share in [float(s) for s in args.shares.split(",")]:
+        allow = np.ones(n, bool) if share >= 1.0 else np.random.default_rng(100 + round(1000 * share)).random(n) < share
+        words = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+        rows = np.flatnonzero(allow)
+        gt_local, _ = calc_gt_device(base[rows], queries, K, metric="ip")
+        gt = np.where(gt_local >= 0, rows[np.clip(gt_local, 0, len(rows) - 1)], -1)
+        post = np.full((nq, K), 0xFFFFFFFF, np.uint32)
+        kept = []
+        for i in range(nq):
+            keep = pool_ids[i][allow[pool_ids[i]]][:K]
+            post[i, :len(keep)] = keep
+            kept.append(len(keep))
+        for m in (K, 4 * K, 224):
+            ms = timed(lambda: filtered(ef, m, words))
+            got = ids.cpu().numpy().view(np.uint32)
+            n_dist = float(cnt.cpu().numpy()[:, 0].mean())
+            groups, waves = dev.last_launch()
+            stage_only(True)
+            ms_search = timed(lambda: filtered(ef, m, words))
+            stage_only(False)
+            emit(dict(leg="sq8", share=share, allowed=int(allow.sum()), ef=ef, pool=m, ms=ms, qps=nq / ms * 1e3,
+                      search_ms=ms_search, rerank_ms=ms - ms_search, recall_at_10=recall(got, gt),
+                      results_per_query=float((got != 0xFFFFFFFF).sum(1).mean()), post_filter_recall_at_10=recall(post, gt),
+                      post_filter_results_per_query=float(np.mean(kept)), workgroups=groups, waves=waves, n_dist=n_dist))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("sweep", "filtered", "plain"), default="sweep")
+    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab"), default="sweep")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--nq", type=int, default=1000)
-    ap.add_argument("--dim", type=int, default=960)
-    ap.add_argument("--ef", type=int, default=387)
+    ap.add_argument("--dim", type=int, default=0, help="0 = 960 (768 for the sq8 legs)")
+    ap.add_argument("--ef", type=int, default=0, help="0 = 387 (the sq8 legs: found on --ef-ladder)")
+    ap.add_argument("--ef-ladder", default="40,60,80,100,120,160,200,260,340,440")
     ap.add_argument("--shares", default="1,0.5,0.1,0.01")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.leg in ("sq8", "sq8-ab"):
+        args.dim = args.dim or 768
+        return sq8_legs(args)
+    args.dim = args.dim or 960
+    args.ef = args.ef or 387
     import torch
     from alayalite_amd import _native
     from workloads.datasets import gist_like
