@@ -19,6 +19,7 @@
 #include "graph_update.h"
 #include "hnsw_build.h"
 #include "flat_bound.h"
+#include "flat_filtered_kernels.h"
 #include "flat_kernels.h"
 #include <cstdlib>
 #include "screen_bound.h"
@@ -131,6 +132,11 @@ struct alaya_index {
   // scratch
   DevBuf work, overflow, dirty, stab, q_buf, id_buf, dist_buf, cnt_buf, dlist_buf, dout_buf;
   DevBuf allow_buf, group_buf;  // the host filtered search's masks and per-query mask indices
+  // exact filtered scan (alaya_index_flat_search_filtered*): the current mask's id list (n words), the
+  // compaction's block sums and count, the partial lists of one scan launch (capped, see
+  // alaya_amd::flat_filtered_plan) and the queries ordered by mask
+  DevBuf ff_ids, ff_sums, ff_count, ff_part_d, ff_part_i, ff_qlist;
+  uint64_t ff_last[4] = {0, 0, 0, 0};  // alaya_index_flat_filtered_last
   size_t overflow_clean = 0;  // leading bytes of `overflow` known to be zero (kernels leave it clean)
   size_t stab_clean = 0;      // the same for the spill tables
   uint32_t hash_log2_override = 0;
@@ -2465,6 +2471,184 @@ int alaya_index_flat_last_contraction(const alaya_index *ix, int *contraction) {
   return guarded([&] {
     if (!ix || !contraction) throw ArgError("invalid arguments");
     *contraction = ix->flat_contraction;
+  });
+}
+
+// ---- exact filtered k-NN: compaction, row-reusing f32 scan, merge (flat_filtered_kernels.hip) ------
+static uint64_t flat_filter_forced_rows() {
+  const char *e = std::getenv("ALAYA_FLAT_FILTER_CHUNK_ROWS");
+  const long long v = e ? std::atoll(e) : 0;
+  return v > 0 ? static_cast<uint64_t>(v) : 0;
+}
+
+// Every pointer but h_groups is a device pointer.  h_groups: the queries' mask indices on the host (checked
+// by the caller), or null: with more than one mask they are read back from d_groups and checked here.
+// Masks are served one after another on `stream`; the host waits for each mask's allowed-row count.
+static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, const uint32_t *d_allow,
+                             uint32_t n_masks, const uint32_t *h_groups, const uint32_t *d_groups, uint32_t *d_ids,
+                             float *d_dists, hipStream_t stream) {
+  using namespace alaya_amd;
+  if (!ix->base.ptr) throw ArgError("index has no base vectors");
+  if (ix->generic) throw ArgError("flat filtered search: float32 rows only");
+  if (k == 0 || k > kFilteredMaxK) throw ArgError("flat filtered search: k must be in 1..224");
+  if (nq == 0) return;
+  if (nq > 0xffffffffull) throw ArgError("flat filtered search: too many queries");
+  std::vector<uint32_t> groups_read;
+  if (n_masks > 1 && !h_groups) {
+    groups_read.resize(nq);
+    hip_check(hipMemcpyAsync(groups_read.data(), d_groups, nq * 4, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "flat filtered search");
+    for (uint32_t g : groups_read)
+      if (g >= n_masks) throw ArgError("flat filtered search: mask_of_query holds an index past n_masks");
+    h_groups = groups_read.data();
+  }
+  // the queries of each mask as an index list, so outputs land in the caller's order
+  std::vector<uint64_t> first(static_cast<size_t>(n_masks) + 1, 0);
+  std::vector<uint32_t> order;
+  if (n_masks > 1) {
+    for (uint64_t i = 0; i < nq; ++i) ++first[h_groups[i] + 1];
+    for (uint32_t g = 0; g < n_masks; ++g) first[g + 1] += first[g];
+    order.resize(nq);
+    std::vector<uint64_t> at(first.begin(), first.end() - 1);
+    for (uint64_t i = 0; i < nq; ++i) order[at[h_groups[i]]++] = static_cast<uint32_t>(i);
+  } else {
+    first[1] = nq;
+  }
+  const uint64_t mask_words = (ix->n + 31) / 32;
+  const uint64_t forced = flat_filter_forced_rows();
+  const uint32_t cus = static_cast<uint32_t>(stream_cus(ix, stream));
+  scratch_acquire(ix, stream);
+  ix->ff_ids.reserve(std::max<uint64_t>(ix->n, 1) * 4);
+  ix->ff_sums.reserve((flat_filtered_blocks(ix->n) + 1) * 4);
+  ix->ff_count.reserve(4);
+  if (n_masks > 1) {
+    ix->ff_qlist.reserve(nq * 4);
+    hip_check(hipMemcpyAsync(ix->ff_qlist.ptr, order.data(), nq * 4, hipMemcpyHostToDevice, stream), "upload query lists");
+    hip_check(hipStreamSynchronize(stream), "flat filtered search");  // `order` is pageable host memory
+  }
+  uint64_t stats[4] = {0, 0, 0, 0};
+  for (uint32_t g = 0; g < n_masks; ++g) {
+    const uint64_t nq_g = first[g + 1] - first[g];
+    if (nq_g == 0) continue;
+    hip_check(launch_flat_filtered_compact(d_allow + static_cast<uint64_t>(g) * mask_words,
+                                           ix->has_valid ? ix->valid.as<uint32_t>() : nullptr, ix->n,
+                                           ix->ff_sums.as<uint32_t>(), ix->ff_ids.as<uint32_t>(),
+                                           ix->ff_count.as<uint32_t>(), stream),
+              "flat filtered compaction");
+    uint32_t m = 0;
+    hip_check(hipMemcpyAsync(&m, ix->ff_count.ptr, 4, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "flat filtered compaction");
+    if (m > ix->n) throw DeviceError("flat filtered compaction: count past the rows");
+    const FlatFilteredPlan plan = flat_filtered_plan(m, nq_g, k, ix->stride, cus, forced);
+    if (plan.tile == 0) throw ArgError("flat filtered search: k / dim too large for the LDS budget");
+    stats[0] += m;
+    FlatFilteredParams p{};
+    p.base = ix->base.as<float>();
+    p.dim = ix->dim;
+    p.stride = ix->stride;
+    p.ip = ix->metric == ALAYA_METRIC_L2 ? 0 : 1;
+    p.queries = d_q;
+    p.q_stride = ix->dim;
+    p.q_list = n_masks > 1 ? ix->ff_qlist.as<uint32_t>() : nullptr;
+    p.ids = ix->ff_ids.as<uint32_t>();
+    p.n_ids = m;
+    p.chunk_rows = plan.chunk_rows;
+    p.chunks = plan.chunks;
+    p.tile = static_cast<uint32_t>(plan.tile);
+    p.k = k;
+    p.out_ids = d_ids;
+    p.out_dists = d_dists;
+    if (m) {
+      // (a buffer that grows is freed first, which waits for the launches that still read it)
+      ix->ff_part_d.reserve(plan.partial_bytes / 2);
+      ix->ff_part_i.reserve(plan.partial_bytes / 2);
+      p.part_d = ix->ff_part_d.as<float>();
+      p.part_i = ix->ff_part_i.as<uint32_t>();
+    }
+    for (uint64_t sb = 0; sb < nq_g; sb += plan.sub_queries) {
+      p.q_first = first[g] + sb;
+      p.nq = std::min<uint64_t>(plan.sub_queries, nq_g - sb);
+      if (m) {
+        hip_check(launch_flat_filtered_scan(p, stream), "flat filtered scan");
+        stats[1] = plan.chunks;
+        stats[2] = plan.tile;
+        ++stats[3];
+      }
+      hip_check(launch_flat_filtered_merge(p, stream), "flat filtered merge");  // m = 0: empty slots
+    }
+  }
+  scratch_release(ix, stream);
+  std::memcpy(ix->ff_last, stats, sizeof(stats));
+}
+
+int alaya_index_flat_search_filtered_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k,
+                                            const uint32_t *d_allow_words, uint32_t n_masks,
+                                            const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
+                                            void *stream) {
+  return guarded([&] {
+    if (!ix || (nq && (!d_queries || !d_ids || !d_allow_words))) throw ArgError("invalid arguments");
+    if (nq && (n_masks == 0 || (n_masks > 1 && !d_mask_of_query)))
+      throw ArgError("flat filtered search: mask_of_query may be null only with one mask");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    do_flat_filtered(ix, d_queries, nq, k, d_allow_words, n_masks, nullptr, d_mask_of_query, d_ids, d_dists,
+                     static_cast<hipStream_t>(stream));
+  });
+}
+
+int alaya_index_flat_search_filtered(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k,
+                                     const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                     uint32_t *ids, float *dists) {
+  return guarded([&] {
+    if (!ix || (nq && (!queries || !ids || !allow_words))) throw ArgError("invalid arguments");
+    if (nq && (n_masks == 0 || (n_masks > 1 && !mask_of_query)))
+      throw ArgError("flat filtered search: mask_of_query may be null only with one mask");
+    if (mask_of_query)
+      for (uint64_t i = 0; i < nq; ++i)
+        if (mask_of_query[i] >= n_masks) throw ArgError("flat filtered search: mask_of_query holds an index past n_masks");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    if (k == 0 || k > 224) throw ArgError("flat filtered search: k must be in 1..224");
+    if (nq == 0) return;
+    const size_t mask_bytes = static_cast<size_t>(n_masks) * ((ix->n + 31) / 32) * 4;
+    scratch_acquire(ix, ix->stream);  // the upload buffers below are the index's, shared with other launches
+    ix->q_buf.reserve(nq * ix->dim * 4);
+    ix->id_buf.reserve(nq * k * 4);
+    ix->dist_buf.reserve(nq * k * 4);
+    ix->allow_buf.reserve(mask_bytes);
+    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
+              "upload queries");
+    hip_check(hipMemcpyAsync(ix->allow_buf.ptr, allow_words, mask_bytes, hipMemcpyHostToDevice, ix->stream),
+              "upload masks");
+    do_flat_filtered(ix, ix->q_buf.as<float>(), nq, k, ix->allow_buf.as<uint32_t>(), n_masks,
+                     n_masks > 1 ? mask_of_query : nullptr, nullptr, ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(),
+                     ix->stream);
+    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    if (dists)
+      hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    hip_check(hipStreamSynchronize(ix->stream), "flat filtered search");
+  });
+}
+
+int alaya_index_flat_filtered_last(const alaya_index *ix, uint64_t *out) {
+  return guarded([&] {
+    if (!ix || !out) throw ArgError("invalid arguments");
+    std::memcpy(out, ix->ff_last, sizeof(ix->ff_last));
+  });
+}
+
+int alaya_flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k, uint32_t stride, uint32_t cus,
+                             uint64_t *out) {
+  return guarded([&] {
+    if (!out) throw ArgError("invalid arguments");
+    if (k == 0 || k > alaya_amd::kFilteredMaxK) throw ArgError("flat filtered plan: k must be in 1..224");
+    const alaya_amd::FlatFilteredPlan r = alaya_amd::flat_filtered_plan(n_allowed, nq, k, stride, cus, flat_filter_forced_rows());
+    if (r.tile == 0) throw ArgError("flat filtered plan: k / dim too large for the LDS budget");
+    out[0] = r.chunk_rows;
+    out[1] = r.chunks;
+    out[2] = r.tile;
+    out[3] = r.sub_queries;
+    out[4] = r.partial_bytes;
   });
 }
 

@@ -316,6 +316,45 @@ class PyIndexInterface : public LaunchControls {
     return py::make_tuple(ids, dists);
   }
 
+  // --- extra (not in the reference binding): exact_search over the rows a mask allows
+  // (alaya_index_flat_search_filtered: a scan of the allowed valid rows, for small allowed shares).
+  // allow_words / mask_of_query as for filtered_search; the query forms and the empty slots are
+  // exact_search's.  An SQ8 index is scanned on its f32 rows.
+  py::object exact_search_filtered(py::array queries, uint32_t topk,
+                                   py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
+                                   py::object mask_of_query) {
+    if (!graph_) throw std::runtime_error("Index is not init yet");
+    py::array q = prepare_queries(queries);
+    const uint64_t nq = q.shape(0);
+    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n_ + 31) / 32 || allow_words.shape(0) < 1)
+      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
+    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
+    const uint32_t *gp = nullptr;
+    if (!mask_of_query.is_none()) {
+      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
+      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
+        throw py::value_error("mask_of_query must hold one index per query");
+      gp = groups.data();
+    }
+    std::vector<uint32_t> ids32(nq * topk);
+    py::array_t<float> dists({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    const uint32_t *ap = allow_words.data();
+    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_flat_search_filtered(ix_, static_cast<const float *>(q.data()), nq, topk, ap, n_masks, gp,
+                                             ids32.data(), dists.mutable_data()));
+    }
+    py::array ids(params_.id_type_, std::vector<py::ssize_t>{static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    if (id_bytes_ == 4) {
+      std::memcpy(ids.mutable_data(), ids32.data(), ids32.size() * 4);
+    } else {
+      auto *o = static_cast<uint64_t *>(ids.mutable_data());
+      for (size_t i = 0; i < ids32.size(); ++i) o[i] = ids32[i] == 0xffffffffu ? UINT64_MAX : ids32[i];
+    }
+    return py::make_tuple(ids, dists);
+  }
+
   uint64_t get_data_num() const { return n_; }
 
   py::array get_data_by_id(uint32_t id) {
@@ -1062,6 +1101,51 @@ class DeviceIndex : public LaunchControls {
                                          reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
                                          reinterpret_cast<uint32_t *>(flags), reinterpret_cast<void *>(stream)));
   }
+  // the exact k nearest among the valid rows allow_words (uint32 [n_masks, ceil(n / 32)], utils.pack_allow)
+  // allows: a scan of those rows (alaya_index_flat_search_filtered); mask_of_query as for filtered_search
+  py::tuple flat_search_filtered(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k,
+                                 py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
+                                 py::object mask_of_query) {
+    const uint64_t nq = q.shape(0);
+    uint64_t n = 0;
+    check(alaya_index_info(ix_, &n, nullptr, nullptr, nullptr, nullptr));
+    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n + 31) / 32 || allow_words.shape(0) < 1)
+      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
+    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
+    const uint32_t *gp = nullptr;
+    if (!mask_of_query.is_none()) {
+      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
+      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
+        throw py::value_error("mask_of_query must hold one index per query");
+      gp = groups.data();
+    }
+    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
+    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
+    const float *qp = q.data();
+    const uint32_t *ap = allow_words.data();
+    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
+    uint32_t *ip = ids.mutable_data();
+    float *dp = d.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_flat_search_filtered(ix_, qp, nq, k, ap, n_masks, gp, ip, dp));
+    }
+    return py::make_tuple(ids, d);
+  }
+  void flat_search_filtered_device(uintptr_t q, uint64_t nq, uint32_t k, uintptr_t allow_words, uint32_t n_masks,
+                                   uintptr_t mask_of_query, uintptr_t ids, uintptr_t dists, uintptr_t stream) {
+    check(alaya_index_flat_search_filtered_device(ix_, reinterpret_cast<const float *>(q), nq, k,
+                                                  reinterpret_cast<const uint32_t *>(allow_words), n_masks,
+                                                  reinterpret_cast<const uint32_t *>(mask_of_query),
+                                                  reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
+                                                  reinterpret_cast<void *>(stream)));
+  }
+  // (allowed valid rows over the masks, row chunks of the last scan, its query tile, scan launches)
+  py::tuple flat_filtered_last() const {
+    uint64_t o[4] = {0, 0, 0, 0};
+    check(alaya_index_flat_filtered_last(ix_, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3]);
+  }
   int flat_contraction() const {
     int c = -1;
     check(alaya_index_flat_last_contraction(ix_, &c));
@@ -1156,6 +1240,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("batch_search_with_distance", &PyIndexInterface::batch_search_with_distance,
            py::arg("queries"), py::arg("topk"), py::arg("ef"), py::arg("num_threads"))
       .def("exact_search", &PyIndexInterface::exact_search, py::arg("queries"), py::arg("topk"))
+      .def("exact_search_filtered", &PyIndexInterface::exact_search_filtered, py::arg("queries"), py::arg("topk"),
+           py::arg("allow_words"), py::arg("mask_of_query") = py::none())
       .def("save", &PyIndexInterface::save, py::arg("index_path"), py::arg("data_path"),
            py::arg("quant_path") = std::string())
       .def("load", &PyIndexInterface::load, py::arg("index_path"), py::arg("data_path"),
@@ -1216,6 +1302,10 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("last_plan", &DeviceIndex::last_plan)
       .def("flat_search", &DeviceIndex::flat_search, py::arg("queries"), py::arg("k"))
       .def("flat_search_device", &DeviceIndex::flat_search_device)
+      .def("flat_search_filtered", &DeviceIndex::flat_search_filtered, py::arg("queries"), py::arg("k"),
+           py::arg("allow_words"), py::arg("mask_of_query") = py::none())
+      .def("flat_search_filtered_device", &DeviceIndex::flat_search_filtered_device)
+      .def("flat_filtered_last", &DeviceIndex::flat_filtered_last)
       .def("flat_diag", &DeviceIndex::flat_diag)
       .def("flat_contraction", &DeviceIndex::flat_contraction)
       .def("search_sq8_device", &DeviceIndex::search_sq8_device)
@@ -1273,6 +1363,13 @@ PYBIND11_MODULE(_alayalitepy, m) {
                                  bound.mutable_data(), sums.mutable_data()));
     return py::make_tuple(d_in, e_sum, bound, sums);
   });
+  // the exact filtered scan's launch plan on the host (alaya_flat_filtered_plan): (rows per chunk, chunks,
+  // query tile, queries per scan launch, partial-list bytes)
+  m.def("flat_filtered_plan", [](uint64_t n_allowed, uint64_t nq, uint32_t k, uint32_t stride, uint32_t cus) {
+    uint64_t o[5] = {0, 0, 0, 0, 0};
+    check(alaya_flat_filtered_plan(n_allowed, nq, k, stride, cus, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3], o[4]);
+  }, py::arg("n_allowed"), py::arg("nq"), py::arg("k"), py::arg("stride"), py::arg("cus"));
   // the flat search's inner-product bound on the host (flat_bound.h): slack per query, and the test
   m.def("flat_ip_slack", [](int contraction, uint32_t k_acc,
                             py::array_t<float, py::array::c_style | py::array::forcecast> q_norm2,

@@ -101,13 +101,38 @@ class Index:
         """The underlying PyIndexInterface (device counters, graph arrays, tuning)."""
         return self.__index
 
-    def exact_search(self, queries: VectorLikeBatch, topk: int):
+    def exact_search(self, queries: VectorLikeBatch, topk: int, allow=None, groups=None):
         """The exact top-k of each query over the rows the index holds (valid rows only, the index's
         metric in f32, ties by id): the flat MFMA search on the device rows -- the ground truth for
         the recall of ``batch_search`` at some ``ef_search``.  Returns (ids, distances); slots past the
-        valid rows hold (the id type's maximum, FLT_MAX).  1 <= topk <= 224, float32 data."""
+        valid rows hold (the id type's maximum, FLT_MAX).  1 <= topk <= 224, float32 data.
+
+        With ``allow`` (``filtered_search``'s masks: a bool array of shape (n,), n = ``get_data_num()``,
+        or (G, n) with ``groups`` of shape (nq,), the mask of each query) the answer is the exact
+        top-k among the valid rows the query's mask allows, same order, same distance bits, same
+        empty slots; an SQ8 index is scanned on its float32 rows.  This skips the graph and scans
+        the allowed rows, each one reused across a tile of queries, so its cost grows with
+        allowed rows x queries: it is meant for small allowed shares, where the graph
+        ``filtered_search`` loses recall.  Above the measured crossover (a few per cent of the rows,
+        DESIGN.md section 3, Round 16) the graph ``filtered_search`` or the unmasked
+        ``exact_search`` is faster."""
         self._check_queries(queries, 2, "queries")
-        return self.__index.exact_search(queries, topk)
+        if allow is None:
+            _assert(groups is None, "groups needs allow")
+            return self.__index.exact_search(queries, topk)
+        allow = np.asarray(allow)
+        _assert(allow.ndim in (1, 2), "allow must have shape (n,) or (G, n)")
+        words = pack_allow(allow, self.get_data_num())
+        if groups is None:
+            _assert(words.shape[0] == 1, "groups is required with more than one mask")
+        else:
+            groups = np.asarray(groups)
+            _assert(groups.shape == (queries.shape[0],), "groups must have shape (nq,)")
+            _assert(np.issubdtype(groups.dtype, np.integer), "groups must be integers")
+            _assert(groups.size == 0 or (groups.min() >= 0 and groups.max() < words.shape[0]),
+                    "groups must be below the number of masks")
+            groups = np.ascontiguousarray(groups, np.uint32)
+        return self.__index.exact_search_filtered(queries, topk, words, groups)
 
     def get_data_num(self) -> int:
         """Rows the index holds, removed ones included: the length of a ``filtered_search`` mask."""

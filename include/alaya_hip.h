@@ -289,6 +289,49 @@ int alaya_index_flat_search_device(alaya_index *ix, const float *d_queries, uint
  * 0 = f32 MFMA; -1 before any flat search.  Environment ALAYA_FLAT_CONTRACTION = f16 | bf16x3 | f32
  * selects one. */
 int alaya_index_flat_last_contraction(const alaya_index *ix, int *contraction);
+/* ---- exact filtered k-NN: a scan over the allowed rows, for small allowed shares -----------------
+ * Stands in for find_exact_gt (include/utils/evaluate.hpp:29-62) over a subset: query i's answer is the
+ * rows that are valid and that its mask allows, ordered by (distance, id), the first k of them; the
+ * remaining slots hold (0xffffffff, FLT_MAX), alaya_index_flat_search's convention.  The distance is
+ * the index's metric in f32 in the reference's order from the start (l2_sqr_avx2; ip_sqr_avx2 for IP
+ * and COS, -(q.b), the caller having normalised rows and queries for COS) -- the bits of
+ * alaya_index_flat_search's and alaya_index_distances' results -- so nothing is flagged or recomputed.
+ * No graph is needed; an index with SQ8 codes is scanned on its f32 rows; ALAYA_DIST_GENERIC bases are
+ * refused.  Rows or queries with non-finite distances are not covered.
+ * allow_words, n_masks, mask_of_query: as for alaya_index_filtered_search (n_masks x ceil(n / 32) words,
+ * bit i % 32 of word i / 32 of a mask = row i, bits past n ignored whatever they hold; mask_of_query may
+ * be NULL with one mask), and so are the argument checks: 1 <= k <= 224, n_masks >= 1.
+ * Masks are served one after another: (mask AND validity) is compacted into an ascending id list, the
+ * mask's queries are scanned against ranges of that list with each gathered row reused across a tile
+ * of queries, and the per-range lists are merged.  The work grows with allowed rows x queries: above a
+ * share of a few per cent the graph search or the unmasked flat search is faster.  Environment
+ * ALAYA_FLAT_FILTER_CHUNK_ROWS=r (diagnostics, read per call) forces the id-list entries per range;
+ * results never depend on it. */
+int alaya_index_flat_search_filtered(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k,
+                                     const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                     uint32_t *ids, float *dists);
+/* Same (find_exact_gt, evaluate.hpp:29-62, over a subset) on device buffers, the mask words on the device,
+ * launched on `stream`.  The call waits on `stream` for each mask's allowed-row count (the scan's grid
+ * depends on it) and, with more than one mask, reads d_mask_of_query back and checks it; when it
+ * returns, the last mask's launches may still be running.  d_dists may be NULL. */
+int alaya_index_flat_search_filtered_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k,
+                                            const uint32_t *d_allow_words, uint32_t n_masks,
+                                            const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
+                                            void *stream);
+/* Introspection of the last call above (find_exact_gt over a subset has no counterpart): out[0] = allowed
+ * valid rows summed over the masks that had queries, out[1] = row chunks of the last scan, out[2] = its
+ * query tile, out[3] = scan launches. */
+int alaya_index_flat_filtered_last(const alaya_index *ix, uint64_t *out);
+/* The scan's launch plan as pure host arithmetic (no device; find_exact_gt over a subset has no
+ * counterpart): for n_allowed rows, nq queries of one mask, k, rows of `stride` floats and `cus` compute
+ * units, out[0] = rows per chunk (a multiple of the 32 rows a wave takes per pass; ALAYA_FLAT_FILTER_CHUNK_ROWS
+ * rounded up to one, unless a single query tile's lists would then pass the cap), out[1] = chunks
+ * (out[0] out[1] >= n_allowed, and no more than fill the CUs twice over at this tile), out[2] = queries per
+ * workgroup (4, 8 or 16), out[3] = queries per scan launch (a multiple of out[2]; the launches cover nq),
+ * out[4] = bytes of partial lists of one launch, at most 256 MiB for any nq.  ALAYA_ERR_ARG if k is
+ * outside 1..224 or the rows are too wide for the LDS. */
+int alaya_flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k, uint32_t stride, uint32_t cus,
+                             uint64_t *out);
 /* Tuning / introspection: LDS visited-table size (log2 slots, 6..16; 0 = automatic) and layout
  * (0 = automatic, 1 = compact 16-bit slots, 2 = 32-bit id slots, 3 = compact with probe distance
  * capped at 2, a test hook for the spill-on-long-probe path).  Results never depend on either:

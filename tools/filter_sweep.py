@@ -22,6 +22,14 @@ usage: python tools/filter_sweep.py [--leg sweep|filtered|plain] [--n 1000000] [
   sq8-ab    the all-ones filtered SQ8 launch, search stage only, against search_sq8(rerank = 0) of the
             same process with ALAYA_HELPERS=0 (the plain mode-0 kernel the filtered one is built from):
             --rounds alternated rounds of --reps launches each; medians and spreads.
+  exact     the exact filtered scan (DeviceIndex.flat_search_filtered_device: compaction, scan and merge
+            together, one mask per batch) alternated with the graph filtered search in one process,
+            --rounds rounds of --reps launches each after 3 warm-ups, per share of 0.001 .. 1: medians
+            and spreads, whether the ids and distance bits equal calc_gt_device(base[rows]) mapped through
+            rows, the graph search's recall, the scan's plan and achieved f32 rate; first the unmasked
+            flat search's time, last the two crossover shares.  --space sq8 runs config 5's shape
+            (768-d IP, SQ8 codes) against filtered_search_sq8_device at m = k, ef 200; --dim 128 the
+            narrow L2 shape.
 Every leg prints one JSON line per measurement; --out appends them to a file."""
 import argparse
 import json
@@ -161,19 +169,136 @@ def sq8_legs(args):
                       post_filter_results_per_query=float(np.mean(kept)), workgroups=groups, waves=waves, n_dist=n_dist))
 
 
+def exact_leg(args):
+    """The exact filtered scan against the graph filtered search, alternated in one process."""
+    import torch
+    from alayalite_amd import _native
+    from alayalite_amd.utils import calc_gt_device, pack_allow
+    from workloads.datasets import gist_like, text_like
+
+    ext = _native._ext
+    st = torch.cuda.current_stream()
+    n, nq, ef, sq8 = args.n, args.nq, args.ef, args.space == "sq8"
+    metric = "ip" if sq8 else "l2"
+    base, queries = (text_like if sq8 else gist_like)(n, nq, dim=args.dim)
+    dev = ext.DeviceIndex(0)
+    dev.set_base(base, 1 if sq8 else 0)
+    dev.build_graph(32, 100, 100, 0, 0, 2)
+    if sq8:
+        mn, mx = ext.sq8_train(base)
+        dev.set_sq8(ext.sq8_encode(base, mn, mx, 16), mn, mx, ext.host_sq8_order())
+    print("index ready", file=sys.stderr, flush=True)
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    ids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+    dd = torch.empty((nq, K), dtype=torch.float32, device="cuda")
+    gids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+    gdd = torch.empty((nq, K), dtype=torch.float32, device="cuda")
+    cnt = torch.empty((nq, 4), dtype=torch.int32, device="cuda")
+    flags = torch.empty((nq,), dtype=torch.int32, device="cuda")
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim, k=K, ef=ef, metric=metric, space=args.space)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    def timed(run):
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(args.reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    def flat():
+        dev.flat_search_device(qd.data_ptr(), nq, K, ids.data_ptr(), dd.data_ptr(), flags.data_ptr(), st.cuda_stream)
+
+    flat_ms = sorted(timed(flat) for _ in range(args.rounds))
+    emit(dict(leg="exact-unmasked", ms=flat_ms, median=float(np.median(flat_ms)), qps=nq / float(np.median(flat_ms)) * 1e3,
+              flagged=int(flags.cpu().numpy().sum())))
+    table = []
+    for share in [float(s) for s in args.shares.split(",")]:
+        allow = np.ones(n, bool) if share >= 1.0 else np.random.default_rng(100 + round(1000 * share)).random(n) < share
+        words = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+        rows = np.flatnonzero(allow)
+
+        def exact():
+            dev.flat_search_filtered_device(qd.data_ptr(), nq, K, words.data_ptr(), 1, 0, ids.data_ptr(), dd.data_ptr(),
+                                            st.cuda_stream)
+
+        def graph():
+            if sq8:
+                dev.filtered_search_sq8_device(qd.data_ptr(), 0, nq, K, ef, K, words.data_ptr(), 1, 0, gids.data_ptr(),
+                                               gdd.data_ptr(), cnt.data_ptr(), st.cuda_stream)
+            else:
+                dev.filtered_search_device(qd.data_ptr(), nq, K, ef, words.data_ptr(), 1, 0, gids.data_ptr(), gdd.data_ptr(),
+                                           cnt.data_ptr(), st.cuda_stream)
+
+        exact_ms, graph_ms = [], []
+        for _ in range(args.rounds):  # alternated: same rows, graph, queries and clocks
+            exact_ms.append(timed(exact))
+            graph_ms.append(timed(graph))
+        last = [int(v) for v in dev.flat_filtered_last()]
+        got = ids.cpu().numpy().view(np.uint32)
+        got_d = dd.cpu().numpy()
+        ggot = gids.cpu().numpy().view(np.uint32)
+        gt_local, gt_d = calc_gt_device(base[rows], queries, K, metric=metric)
+        gt = np.where(gt_local >= 0, rows[np.clip(gt_local, 0, len(rows) - 1)], -1)
+        want = np.where(gt >= 0, gt, 0xFFFFFFFF).astype(np.uint32)
+        med_e, med_g = float(np.median(exact_ms)), float(np.median(graph_ms))
+        rec = dict(leg="exact", share=share, allowed=int(allow.sum()), exact_ms=sorted(exact_ms), graph_ms=sorted(graph_ms),
+                   exact_median=med_e, graph_median=med_g, exact_spread=(max(exact_ms) - min(exact_ms)) / med_e,
+                   graph_spread=(max(graph_ms) - min(graph_ms)) / med_g, exact_qps=nq / med_e * 1e3,
+                   ids_equal_ground_truth=bool(np.array_equal(got, want)),
+                   distance_bits_equal_ground_truth=bool(np.array_equal(got_d.view(np.uint32), gt_d.view(np.uint32))),
+                   graph_recall_at_10=recall(ggot, gt), allowed_valid=last[0], row_chunks=last[1], query_tile=last[2],
+                   scan_launches=last[3],
+                   # two f32 operations per element of every (query, allowed row) pair, over the whole call
+                   achieved_tflops=2.0 * nq * float(allow.sum()) * args.dim / (med_e * 1e-3) / 1e12,
+                   exact_below_graph_median=med_e < med_g, every_exact_below_every_graph=max(exact_ms) < min(graph_ms))
+        emit(rec)
+        table.append((share, med_e, med_g))
+
+    def crossover(against):
+        """The share at which the exact scan's median passes `against` (linear between sweep points)."""
+        for (s0, e0, g0), (s1, e1, g1) in zip(table, table[1:]):
+            a0, a1 = against(g0), against(g1)
+            if (e0 - a0) <= 0 < (e1 - a1):
+                t = (a0 - e0) / ((e1 - a1) - (e0 - a0))
+                return s0 + t * (s1 - s0)
+        return None
+
+    table.sort()
+    emit(dict(leg="exact-crossover", against_graph_share=crossover(lambda g: g),
+              against_unmasked_exact_share=crossover(lambda g: float(np.median(flat_ms)))))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab"), default="sweep")
+    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact"), default="sweep")
+    ap.add_argument("--space", choices=("f32", "sq8"), default="f32",
+                    help="exact leg: f32 = GIST-shaped L2 rows; sq8 = config 5's text-like IP rows with SQ8 codes")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--nq", type=int, default=1000)
     ap.add_argument("--dim", type=int, default=0, help="0 = 960 (768 for the sq8 legs)")
     ap.add_argument("--ef", type=int, default=0, help="0 = 387 (the sq8 legs: found on --ef-ladder)")
     ap.add_argument("--ef-ladder", default="40,60,80,100,120,160,200,260,340,440")
-    ap.add_argument("--shares", default="1,0.5,0.1,0.01")
+    ap.add_argument("--shares", default="", help="default 1,0.5,0.1,0.01 (exact leg: 0.001,0.01,0.05,0.1,0.2,0.5,1)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.leg == "exact":
+        args.shares = args.shares or "0.001,0.01,0.05,0.1,0.2,0.5,1"
+        args.dim = args.dim or (768 if args.space == "sq8" else 960)
+        args.ef = args.ef or (200 if args.space == "sq8" else 387)
+        return exact_leg(args)
+    args.shares = args.shares or "1,0.5,0.1,0.01"
     if args.leg in ("sq8", "sq8-ab"):
         args.dim = args.dim or 768
         return sq8_legs(args)
