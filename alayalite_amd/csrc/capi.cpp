@@ -132,6 +132,7 @@ struct alaya_index {
   // scratch
   DevBuf work, overflow, dirty, stab, q_buf, id_buf, dist_buf, cnt_buf, dlist_buf, dout_buf;
   DevBuf allow_buf, group_buf;  // the host filtered search's masks and per-query mask indices
+  DevBuf through_buf;           // the host through search's rows stepped through per query
   // exact filtered scan (alaya_index_flat_search_filtered*): the current mask's id list (n words), the
   // compaction's block sums and count, the partial lists of one scan launch (capped, see
   // alaya_amd::flat_filtered_plan) and the queries ordered by mask
@@ -364,9 +365,9 @@ bool helpers_requested(const alaya_index *ix, const SearchParams &p, uint64_t nq
 }
 
 // filter_k != 0: the filtered search -- its own kernel's registers, and a result pool of filter_k entries
-// in every wave's region.
+// in every wave's region (hop: the through search's kernel).
 uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchVariant &v, uint64_t nq, uint32_t ef,
-                      int W = 1, uint32_t filter_k = 0) {
+                      int W = 1, uint32_t filter_k = 0, bool hop = false) {
   const uint32_t lbits = std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2)));
   const int mode = ix->visited_mode_override;  // 0 auto, 1 compact, 2 wide, 3 compact + short probes
   auto set_mode = [&](uint32_t l, bool compact) {
@@ -413,6 +414,7 @@ uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchV
   int vgpr_blocks = 0;
   const size_t probe_lds = shared + W * (wave_fixed + (stab ? 1024 : 4096));
   hip_check(!filter_k ? alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks)
+            : hop ? alaya_amd::filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
             : p.sq8_order ? alaya_amd::filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, probe_lds, &vgpr_blocks)
                           : alaya_amd::filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks),
             "occupancy");
@@ -743,10 +745,15 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
 // the same plan for the mode-0 SQ8 request of the shape (four waves per workgroup beside the shared scale / min,
 // the spill-table second level where spill_table_log2 gives one); k is then the candidate pool's capacity m
 // and d_ids / d_dists receive the nq x m candidates by code distance, for the rerank.
+//
+// hop: the through search (alaya_index_filtered_search_hop*, filtered_hop_search_kernel; f32 rows only) -- the same
+// plan with that kernel's occupancy; d_through (nullable) receives the rows stepped through per query.
 void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef, const uint32_t *d_allow,
                         const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt,
-                        hipStream_t stream, bool sq8 = false) {
+                        hipStream_t stream, bool sq8 = false, bool hop = false, uint32_t *d_through = nullptr) {
   using namespace alaya_amd;
+  if (hop && (sq8 || ix->has_sq8))
+    throw ArgError("through search of an SQ8 index: alaya_index_filtered_search_hop searches f32 rows only");
   if (!ix->base.ptr) throw ArgError("index has no base vectors");
   if (!ix->has_graph) throw ArgError("index has no graph");
   if (sq8 && !ix->has_sq8) throw ArgError("index has no SQ8 codes");
@@ -770,7 +777,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   const SearchVariant &plain = resolve_search_variant({ix->dim, p.ip, p.sq8_order, ix->generic, 0});
   int W = search_waves(p);
   while (W > 1 && static_cast<uint64_t>(W) > nq) W /= 2;
-  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k);
+  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k, hop);
   const size_t traversal_lds = search_wave_lds_bytes(ix->stride, ef, p.hash_log2, p.vis_rbits != kVisWide, p.sq8_order);
   p.wave_lds = static_cast<uint32_t>(traversal_lds + filter_result_lds_bytes(k));
   FilterParams f{};
@@ -783,6 +790,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   if (lds > kLdsPerCu) throw ArgError("filtered search: k / ef / dim too large for the LDS budget");
   int per_cu = 0;
   hip_check(sq8 ? filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, lds, &per_cu)
+            : hop ? filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
                 : filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu),
             "occupancy");
   per_cu = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(per_cu, max_search_waves_per_cu() / W)));
@@ -806,7 +814,9 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   ix->work.reserve(4);
   p.work_counter = ix->work.as<uint32_t>();
   hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
-  hip_check(sq8 ? launch_filtered_sq8_search(p, f, grid, W, lds, stream) : launch_filtered_search(p, f, grid, W, lds, stream),
+  hip_check(sq8   ? launch_filtered_sq8_search(p, f, grid, W, lds, stream)
+            : hop ? launch_filtered_hop_search(p, f, HopParams{d_through}, grid, W, lds, stream)
+                  : launch_filtered_search(p, f, grid, W, lds, stream),
             "filtered search launch");
   scratch_release(ix, stream);
 }
@@ -1965,9 +1975,11 @@ int alaya_index_batch_search(alaya_index *ix, const float *queries, uint64_t nq,
   });
 }
 
-int alaya_index_filtered_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t ef,
+// alaya_index_filtered_search[_hop]_device / alaya_index_filtered_search[_hop]: one body each, hop = the through search
+static int filtered_search_device_call(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t ef,
                                        const uint32_t *d_allow_words, uint32_t n_masks, const uint32_t *d_mask_of_query,
-                                       uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream) {
+                                       uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream, bool hop,
+                                       uint32_t *d_through) {
   return guarded_scratch(ix, [&] {
     if (!ix || (nq && (!d_queries || !d_ids || !d_allow_words))) throw ArgError("invalid arguments");
     if (nq && (n_masks == 0 || (n_masks > 1 && !d_mask_of_query)))
@@ -1975,13 +1987,28 @@ int alaya_index_filtered_search_device(alaya_index *ix, const float *d_queries, 
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     do_filtered_search(ix, d_queries, nq, k, ef, d_allow_words, d_mask_of_query, d_ids, d_dists, d_counters,
-                       static_cast<hipStream_t>(stream));
+                       static_cast<hipStream_t>(stream), false, hop, d_through);
   });
 }
 
-int alaya_index_filtered_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t ef,
-                                const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
-                                uint32_t *ids, float *dists, uint32_t *counters) {
+int alaya_index_filtered_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                       const uint32_t *d_allow_words, uint32_t n_masks, const uint32_t *d_mask_of_query,
+                                       uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream) {
+  return filtered_search_device_call(ix, d_queries, nq, k, ef, d_allow_words, n_masks, d_mask_of_query, d_ids, d_dists,
+                                     d_counters, stream, false, nullptr);
+}
+
+int alaya_index_filtered_search_hop_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                           const uint32_t *d_allow_words, uint32_t n_masks,
+                                           const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
+                                           uint32_t *d_counters, uint32_t *d_n_through, void *stream) {
+  return filtered_search_device_call(ix, d_queries, nq, k, ef, d_allow_words, n_masks, d_mask_of_query, d_ids, d_dists,
+                                     d_counters, stream, true, d_n_through);
+}
+
+static int filtered_search_host_call(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                     const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                     uint32_t *ids, float *dists, uint32_t *counters, bool hop, uint32_t *n_through) {
   return guarded_scratch(ix, [&] {
     if (!ix || (nq && (!queries || !ids || !allow_words))) throw ArgError("invalid arguments");
     if (nq && (n_masks == 0 || (n_masks > 1 && !mask_of_query)))
@@ -2000,6 +2027,7 @@ int alaya_index_filtered_search(alaya_index *ix, const float *queries, uint64_t 
     ix->cnt_buf.reserve(nq * 16);
     ix->allow_buf.reserve(mask_bytes);
     ix->group_buf.reserve(nq * 4);
+    if (hop && n_through) ix->through_buf.reserve(nq * 4);
     hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
               "upload queries");
     hip_check(hipMemcpyAsync(ix->allow_buf.ptr, allow_words, mask_bytes, hipMemcpyHostToDevice, ix->stream),
@@ -2009,14 +2037,31 @@ int alaya_index_filtered_search(alaya_index *ix, const float *queries, uint64_t 
                 "upload mask indices");
     do_filtered_search(ix, ix->q_buf.as<float>(), nq, k, ef, ix->allow_buf.as<uint32_t>(),
                        mask_of_query ? ix->group_buf.as<uint32_t>() : nullptr, ix->id_buf.as<uint32_t>(),
-                       ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream);
+                       ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream, false, hop,
+                       hop && n_through ? ix->through_buf.as<uint32_t>() : nullptr);
     hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
     if (dists)
       hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
     if (counters)
       hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    if (hop && n_through)
+      hip_check(hipMemcpyAsync(n_through, ix->through_buf.ptr, nq * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
     hip_check(hipStreamSynchronize(ix->stream), "filtered search");
   });
+}
+
+int alaya_index_filtered_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                uint32_t *ids, float *dists, uint32_t *counters) {
+  return filtered_search_host_call(ix, queries, nq, k, ef, allow_words, n_masks, mask_of_query, ids, dists, counters, false,
+                                   nullptr);
+}
+
+int alaya_index_filtered_search_hop(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                    const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                    uint32_t *ids, float *dists, uint32_t *counters, uint32_t *n_through) {
+  return filtered_search_host_call(ix, queries, nq, k, ef, allow_words, n_masks, mask_of_query, ids, dists, counters, true,
+                                   n_through);
 }
 
 int alaya_index_profile_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k,

@@ -268,12 +268,15 @@ class PyIndexInterface : public LaunchControls {
   // (alaya_index_filtered_search).  allow_words: uint32 [n_masks, ceil(n / 32)] (utils.pack_allow);
   // mask_of_query: each query's mask, or None with one mask.  Empty slots as exact_search's.
   // SQ8 indexes run alaya_index_filtered_search_sq8 with batch_search's two query forms; pool: its
-  // candidate pool (0 = the default), which an unquantized index does not have.
+  // candidate pool (0 = the default), which an unquantized index does not have.  through: the traversal
+  // that steps through disallowed neighbours (alaya_index_filtered_search_hop; f32 indexes only), whose rows
+  // stepped through per query last_through() then holds.
   py::object filtered_search(py::array queries, uint32_t topk, uint32_t ef,
                              py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
-                             py::object mask_of_query, uint32_t pool) {
+                             py::object mask_of_query, uint32_t pool, bool through) {
     if (!graph_) throw std::runtime_error("Index is not init yet");
     const bool sq8 = params_.quantization_type_ == QuantizationType::SQ8;
+    if (through && (sq8 || pool != 0)) throw py::value_error("the through traversal searches f32 indexes only");
     if (!sq8 && params_.quantization_type_ != QuantizationType::NONE)
       throw std::runtime_error("filtered_search: the MI355X engine has float32 and SQ8 indexes only");
     if (!sq8 && pool != 0) throw py::value_error("pool applies to SQ8 indexes only");
@@ -292,6 +295,7 @@ class PyIndexInterface : public LaunchControls {
     std::vector<uint32_t> ids32(nq * topk);
     py::array_t<float> dists({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
     last_counters_.assign(nq * 4, 0);
+    last_through_.assign(through ? nq : 0, 0);
     const uint32_t *ap = allow_words.data();
     const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
     if (sq8) {
@@ -301,6 +305,11 @@ class PyIndexInterface : public LaunchControls {
       py::gil_scoped_release nogil;
       check(alaya_index_filtered_search_sq8(ix_, sq, rq, nq, topk, ef, pool, ap, n_masks, gp, ids32.data(),
                                             dists.mutable_data(), last_counters_.data()));
+    } else if (through) {
+      py::gil_scoped_release nogil;
+      check(alaya_index_filtered_search_hop(ix_, static_cast<const float *>(q.data()), nq, topk, ef, ap, n_masks, gp,
+                                            ids32.data(), dists.mutable_data(), last_counters_.data(),
+                                            last_through_.data()));
     } else {
       py::gil_scoped_release nogil;
       check(alaya_index_filtered_search(ix_, static_cast<const float *>(q.data()), nq, topk, ef, ap, n_masks, gp,
@@ -447,6 +456,12 @@ class PyIndexInterface : public LaunchControls {
   uint32_t get_data_dim() const { return dim_; }
 
   // --- extra (not in the reference binding): device counters of the last search ---
+  // rows stepped through per query of the last filtered_search(..., through=True); empty after any other
+  py::array last_through() const {
+    py::array_t<uint32_t> out(static_cast<py::ssize_t>(last_through_.size()));
+    if (!last_through_.empty()) std::memcpy(out.mutable_data(), last_through_.data(), last_through_.size() * 4);
+    return out;
+  }
   py::array last_counters() const {
     py::array_t<uint32_t> out({static_cast<py::ssize_t>(last_counters_.size() / 4), static_cast<py::ssize_t>(4)});
     std::memcpy(out.mutable_data(), last_counters_.data(), last_counters_.size() * 4);
@@ -792,6 +807,7 @@ class PyIndexInterface : public LaunchControls {
   bool updates_enabled_ = false;   // the device index holds an update mirror (alaya_index_enable_updates)
   bool graph_dirty_ = false;       // graph_ predates inserts (sync_graph refreshes it)
   std::vector<uint32_t> last_counters_;
+  std::vector<uint32_t> last_through_;
   int rerank_mode_ = 1;
   std::vector<float> raw_queries_;   // SQ8 + COS: the un-normalised queries the SQ8 search encodes
   std::vector<uint8_t> sq_codes_;
@@ -942,6 +958,18 @@ class DeviceIndex : public LaunchControls {
   py::tuple filtered_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
                             py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
                             py::object mask_of_query) {
+    return filtered_search_call(q, k, ef, allow_words, mask_of_query, false);
+  }
+  // the same under the traversal that steps through disallowed neighbours (alaya_index_filtered_search_hop):
+  // (ids, dists, counters[nq, 4], n_through[nq])
+  py::tuple filtered_search_hop(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
+                                py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
+                                py::object mask_of_query) {
+    return filtered_search_call(q, k, ef, allow_words, mask_of_query, true);
+  }
+  py::tuple filtered_search_call(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
+                                 py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
+                                 py::object mask_of_query, bool hop) {
     const uint64_t nq = q.shape(0);
     uint64_t n = 0;
     check(alaya_index_info(ix_, &n, nullptr, nullptr, nullptr, nullptr));
@@ -964,11 +992,30 @@ class DeviceIndex : public LaunchControls {
     uint32_t *ip = ids.mutable_data();
     float *dp = d.mutable_data();
     uint32_t *cp = c.mutable_data();
+    if (hop) {
+      py::array_t<uint32_t> t(static_cast<py::ssize_t>(nq));
+      uint32_t *tp = t.mutable_data();
+      {
+        py::gil_scoped_release nogil;
+        check(alaya_index_filtered_search_hop(ix_, qp, nq, k, ef, ap, n_masks, gp, ip, dp, cp, tp));
+      }
+      return py::make_tuple(ids, d, c, t);
+    }
     {
       py::gil_scoped_release nogil;
       check(alaya_index_filtered_search(ix_, qp, nq, k, ef, ap, n_masks, gp, ip, dp, cp));
     }
     return py::make_tuple(ids, d, c);
+  }
+  void filtered_search_hop_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t allow_words, uint32_t n_masks,
+                                  uintptr_t mask_of_query, uintptr_t ids, uintptr_t dists, uintptr_t counters,
+                                  uintptr_t n_through, uintptr_t stream) {
+    check(alaya_index_filtered_search_hop_device(ix_, reinterpret_cast<const float *>(q), nq, k, ef,
+                                                 reinterpret_cast<const uint32_t *>(allow_words), n_masks,
+                                                 reinterpret_cast<const uint32_t *>(mask_of_query),
+                                                 reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
+                                                 reinterpret_cast<uint32_t *>(counters),
+                                                 reinterpret_cast<uint32_t *>(n_through), reinterpret_cast<void *>(stream)));
   }
   void filtered_search_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t allow_words, uint32_t n_masks,
                               uintptr_t mask_of_query, uintptr_t ids, uintptr_t dists, uintptr_t counters,
@@ -1247,7 +1294,9 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("load", &PyIndexInterface::load, py::arg("index_path"), py::arg("data_path"),
            py::arg("quant_path") = std::string())
       .def("filtered_search", &PyIndexInterface::filtered_search, py::arg("queries"), py::arg("topk"), py::arg("ef"),
-           py::arg("allow_words"), py::arg("mask_of_query") = py::none(), py::arg("pool") = 0)
+           py::arg("allow_words"), py::arg("mask_of_query") = py::none(), py::arg("pool") = 0,
+           py::arg("through") = false)
+      .def("last_through", &PyIndexInterface::last_through)
       .def("get_data_dim", &PyIndexInterface::get_data_dim)
       .def("get_data_num", &PyIndexInterface::get_data_num)
       .def("last_counters", &PyIndexInterface::last_counters)
@@ -1285,6 +1334,9 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("filtered_search", &DeviceIndex::filtered_search, py::arg("queries"), py::arg("k"), py::arg("ef"),
            py::arg("allow_words"), py::arg("mask_of_query") = py::none())
       .def("filtered_search_device", &DeviceIndex::filtered_search_device)
+      .def("filtered_search_hop", &DeviceIndex::filtered_search_hop, py::arg("queries"), py::arg("k"), py::arg("ef"),
+           py::arg("allow_words"), py::arg("mask_of_query") = py::none())
+      .def("filtered_search_hop_device", &DeviceIndex::filtered_search_hop_device)
       .def("filtered_search_sq8", &DeviceIndex::filtered_search_sq8, py::arg("queries"), py::arg("k"), py::arg("ef"),
            py::arg("allow_words"), py::arg("mask_of_query") = py::none(), py::arg("pool") = 0,
            py::arg("rerank_queries") = py::none())

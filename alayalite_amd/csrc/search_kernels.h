@@ -134,6 +134,12 @@ struct FilterParams {
                                   // visited table: SearchParams::wave_lds - filter_result_lds_bytes(k))
 };
 
+// What the through search (filtered_hop_search_kernel) takes beyond SearchParams and FilterParams: its
+// third argument.
+struct HopParams {
+  uint32_t *n_through;  // nq: rows stepped through per query (nullable)
+};
+
 // PyIndex::rerank inputs (python/include/index.hpp:450-488).  Per query the kernel rescores
 // search_ids[0 .. n_take) (row stride n_src; kEmpty entries are skipped) plus `zeros` entries of id 0
 // -- the reference's res_pool slots [k, ef) that batch_search leaves zero (index.hpp:301) -- and
@@ -200,6 +206,11 @@ size_t filter_result_lds_bytes(uint32_t k);
 hipError_t filtered_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);
 hipError_t launch_filtered_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
                                   hipStream_t stream);
+// The through search (filtered_hop_search_kernel; f32 rows): the filtered search's plan and LDS layout, its
+// own kernel's resident workgroups per CU, and its launch.
+hipError_t filtered_hop_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);
+hipError_t launch_filtered_hop_search(const SearchParams &p, const FilterParams &f, const HopParams &h, int grid, int waves,
+                                      size_t lds, hipStream_t stream);
 // Filtered search of SQ8 codes (filtered_sq8_search_kernel): f.k = p.k = m, the candidate pool's capacity
 // (filter_result_lds_bytes(m) at the end of p.wave_lds); p is planned as the plain (mode 0) SQ8 search of
 // the shape and p.out_ids receives nq x m candidate ids, kEmpty in empty slots, for launch_rerank.

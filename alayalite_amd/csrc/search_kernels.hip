@@ -1948,4 +1948,248 @@ hipError_t filtered_sq8_search_occupancy(uint32_t dim, int sq8_order, bool ip, i
                                                       64 * waves, lds);
 }
 
+// --------------------------------------------------------------------------------------------
+// Through search: the filtered search with a second expansion rule.  passable(v) = v's allow bit is set
+// and (indexes with a bitmap) v is valid.  A popped node's neighbour that is not passable is neither
+// measured nor kept: it is marked visited and its own level-0 row is walked instead, one level deep, for
+// passable rows not yet visited (a row that is not passable is skipped there without a visited mark).  So
+// the traversal pool of ef entries holds passable rows only, beside the entry, which goes in whatever its
+// bit.  Per pop: the direct row's passable fresh neighbours, then each through row's, in adjacency order --
+// the order of the sequential pool.insert / result.insert calls this kernel equals (include/alaya_hip.h,
+// alaya_index_filtered_search_hop).  The candidates queue up in L.cid and are measured and merged 64 at the
+// most at a time: a flush.  LDS is the filtered kernel's; the through list is a ballot mask, and the
+// adjacency rows of kHopRows through nodes, with their allow bits, are in flight together in registers.
+// --------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kHopRows = 8;
+
+// A batch of through rows, one register each, as a queue: the next row is x0, and taking it moves the others
+// down.  (Nothing is ever selected by the wave-uniform row index: the compiler turns such a selection into an
+// indexed load, which puts the batch in scratch.)
+struct HopBatch {
+  uint32_t x0, x1, x2, x3, x4, x5, x6, x7;
+};
+static_assert(sizeof(HopBatch) == kHopRows * 4, "one register per row");
+
+__device__ __forceinline__ uint32_t hop_take(HopBatch &b) {
+  const uint32_t r = b.x0;
+  b.x0 = b.x1;
+  b.x1 = b.x2;
+  b.x2 = b.x3;
+  b.x3 = b.x4;
+  b.x4 = b.x5;
+  b.x5 = b.x6;
+  b.x6 = b.x7;
+  b.x7 = kEmpty;
+  return r;
+}
+
+// lanes of `m` append their id to the candidate queue, in lane order, behind its qn entries
+__device__ __forceinline__ void hop_append(const Lds &L, int qn, uint64_t m, uint32_t id) {
+  const int lane = lane_id();
+  if ((m >> lane) & 1ull) L.cid[qn + __popcll(m & ((1ull << lane) - 1ull))] = id;
+}
+
+template <bool kIP, int kChunks>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(search_min_waves<kChunks, 0, 0>() ? search_min_waves<kChunks, 0, 0>() : 1, 8)))
+    filtered_hop_search_kernel(SearchParams p, FilterParams f, HopParams h) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int kSpace = 0;
+  const int lane = lane_id();
+  const int wave = static_cast<int>(threadIdx.x >> 6);
+  const int W = static_cast<int>(blockDim.x >> 6);
+  const int R = static_cast<int>(p.R);
+  const Lds L = carve_lds<kSpace>(p, smem, wave);
+  const Lds Lr = result_lds(L, f);
+  const uint64_t bit_words = (p.n + 31) / 32;
+  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * W + wave;
+  uint32_t *slot_bits = p.overflow_bits + slot * bit_words;
+  uint32_t *slot_dirty = p.dirty_words + slot * p.dirty_cap;
+  constexpr bool kRegMerge = kChunks > 0 && kChunks <= 8;  // as the plain kernel's traversal merge
+
+  for (;;) {
+    uint32_t qi = 0;
+    if (lane == 0) qi = atomicAdd(p.work_counter, 1u);
+    qi = read_lane(qi, 0);
+    if (qi >= p.nq) break;
+    const uint32_t *mask = f.allow + static_cast<uint64_t>(f.mask_of_query != nullptr ? f.mask_of_query[qi] : 0u) * f.mask_words;
+    // the row's allow word, and-ed with its validity word: bit (id & 31) = passable
+    auto pass_word = [&](uint32_t id) {
+      uint32_t w = mask[id >> 5];
+      if (p.valid != nullptr) w &= p.valid[id >> 5];
+      return w;
+    };
+    for (uint32_t e = lane; e <= f.k; e += 64) {
+      Lr.pd[e] = 0.f;
+      Lr.pi[e] = 0u;
+    }
+    PoolState rs{0u, 0u, f.k};
+    Visited vs;
+    PoolState ps;
+    uint32_t n_dist = 0, n_expand = 0, n_dist_up = 0, n_hops_up = 0, n_through = 0;
+    // (query_begin's first wave_sync orders the reset above before any offer)
+    query_begin<kIP, kChunks, kSpace>(p, L, qi, slot_bits, slot_dirty, nullptr, vs, ps, n_dist_up, n_hops_up,
+                                      [&](bool has, uint32_t id, float d) {
+                                        bool ok = false;
+                                        if (has) ok = ((pass_word(id) >> (id & 31)) & 1u) != 0u;
+                                        result_offer(rs, Lr, ok, id, d);
+                                      });
+
+    uint32_t pred = kEmpty, pred_v = kEmpty;  // adjacency prefetch of the predicted next pop
+    while (ps.cur < ps.size) {
+      const uint32_t u = pool_pop(ps, L);
+      ++n_expand;
+      // ---- direct row: the bit decides candidate or through, so its word is read before the visit ----
+      const uint32_t v = u == pred ? pred_v : adjacency_row(p, R, u);
+      const int cnt = adjacency_count(R, v);
+      bool act = lane < cnt;
+      if (p.dedup_edges) {  // graphs with repeated ids in a row: keep the first occurrence only
+        for (int j = 0; j < cnt; ++j) {
+          const uint32_t vj = read_lane(v, j);
+          if (j < lane && vj == v) act = false;
+        }
+      }
+      bool pass = false;
+      if (act) pass = ((pass_word(v) >> (v & 31)) & 1u) != 0u;
+      if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin(vs);
+      const bool fresh = visit(vs, v, act);
+      const uint64_t fm = ballot(fresh && pass);
+      uint64_t rest = ballot(fresh && !pass);  // the through list, adjacency order
+      n_through += __popcll(rest);
+      int qn = __popcll(fm);                   // candidates queued in L.cid
+      pred = ps.cur < ps.size ? (L.pi[ps.cur] & kIdMask) : kEmpty;
+      if (pred != kEmpty) pred_v = adjacency_row(p, R, pred, pred_v);
+      if (qn == 0 && rest == 0ull) continue;
+      hop_append(L, 0, fm, v);
+
+      // ---- through rows, kHopRows at a time: row loads, then their allow words, all in flight ----
+      HopBatch x{kEmpty, kEmpty, kEmpty, kEmpty, kEmpty, kEmpty, kEmpty, kEmpty};
+      uint32_t okb = 0u;  // bit j: this lane's entry of the batch's row j is passable
+      int bn = 0;         // rows left in the batch
+      bool pend = false;   // a row whose fresh ids wait for the flush that makes room
+      uint32_t px = 0u;
+      uint64_t pm = 0ull;
+      for (;;) {
+        if (pend) {
+          hop_append(L, qn, pm, px);
+          qn += __popcll(pm);
+          pend = false;
+        }
+        while (rest != 0ull) {
+          if (bn == 0) {
+            uint64_t r2 = rest;
+            // the next through node's row, kEmpty in every lane past the list's end
+            auto next_row = [&]() {
+              if (r2 == 0ull) return kEmpty;
+              const uint32_t w = read_lane(v, __ffsll(static_cast<unsigned long long>(r2)) - 1);
+              r2 &= r2 - 1ull;
+              ++bn;
+              return adjacency_row(p, R, w);
+            };
+            x.x0 = next_row();
+            x.x1 = next_row();
+            x.x2 = next_row();
+            x.x3 = next_row();
+            x.x4 = next_row();
+            x.x5 = next_row();
+            x.x6 = next_row();
+            x.x7 = next_row();
+            // (every lane loads, a lane past its row the word of row 0: eight independent gathers, no branch)
+            auto pass_bit = [&](uint32_t id) {
+              const uint32_t at = id != kEmpty ? id : 0u;
+              const uint32_t bit = (pass_word(at) >> (at & 31)) & 1u;
+              return id != kEmpty ? bit : 0u;
+            };
+            okb = pass_bit(x.x0) | pass_bit(x.x1) << 1 | pass_bit(x.x2) << 2 | pass_bit(x.x3) << 3 | pass_bit(x.x4) << 4 |
+                  pass_bit(x.x5) << 5 | pass_bit(x.x6) << 6 | pass_bit(x.x7) << 7;
+          }
+          const uint32_t xr = hop_take(x);
+          const bool okr = (okb & 1u) != 0u;
+          okb >>= 1;
+          --bn;
+          rest &= rest - 1ull;
+          const int cnt2 = adjacency_count(R, xr);
+          bool act2 = lane < cnt2;
+          if (p.dedup_edges) {
+            for (int j = 0; j < cnt2; ++j) {
+              const uint32_t xj = read_lane(xr, j);
+              if (j < lane && xj == xr) act2 = false;
+            }
+          }
+          if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin(vs);
+          const uint64_t m2 = ballot(visit(vs, xr, act2 && okr));
+          if (m2 == 0ull) continue;
+          if (qn + __popcll(m2) > 64) {  // no room: flush first
+            px = xr;
+            pm = m2;
+            pend = true;
+            break;
+          }
+          hop_append(L, qn, m2, xr);
+          qn += __popcll(m2);
+        }
+        if (qn == 0) break;
+        // ---- flush: distances, traversal merge, result offer (every queued id is passable) ----
+        wave_sync();
+        const bool has = lane < qn;
+        const uint32_t cid = has ? L.cid[lane] : 0u;
+        space_distances<kIP, kChunks, kSpace>(p, L, L.cid, qn, L.cd);
+        n_dist += qn;
+        const float cd = has ? L.cd[lane] : 0.f;
+        wave_sync();
+        pool_merge<kRegMerge>(ps, L, has, cid, cd, [&](uint32_t nx) {
+          if (nx != pred) {
+            pred = nx;
+            pred_v = adjacency_row(p, R, nx, pred_v);
+          }
+        });
+        result_offer(rs, Lr, has, cid, cd);
+        wave_sync();
+        qn = 0;
+        if (!pend && rest == 0ull) break;
+      }
+    }
+
+    query_end(p, Lr, rs, qi, n_dist, n_expand, n_dist_up, n_hops_up);
+    if (h.n_through != nullptr && lane == 0) h.n_through[qi] = n_through;
+    visit_end(vs);
+    wave_sync();
+  }
+}
+}  // namespace
+
+// The through kernels: the filtered kernels' set.
+template <int... kChunks>
+static const void *filtered_hop_symbol_of(int chunks, bool ip) {
+  const void *sym = nullptr;
+  ((chunks == kChunks ? (sym = ip ? reinterpret_cast<const void *>(&filtered_hop_search_kernel<true, kChunks>)
+                                  : reinterpret_cast<const void *>(&filtered_hop_search_kernel<false, kChunks>),
+                         0)
+                      : 0),
+   ...);
+  return sym;
+}
+
+static const void *filtered_hop_kernel_symbol(uint32_t dim, bool generic, bool ip) {
+  const void *sym = filtered_hop_symbol_of<4, 8, 16, 24, 30, 32>(search_chunks(dim, generic), ip);
+  return sym != nullptr ? sym : filtered_hop_symbol_of<0>(0, ip);
+}
+
+hipError_t launch_filtered_hop_search(const SearchParams &p, const FilterParams &f, const HopParams &h, int grid, int waves,
+                                      size_t lds, hipStream_t stream) {
+  SearchParams arg = p;
+  FilterParams farg = f;
+  HopParams harg = h;
+  void *args[] = {&arg, &farg, &harg};
+  return hipLaunchKernel(filtered_hop_kernel_symbol(p.dim, p.generic, p.ip), dim3(grid), dim3(64 * waves), args, lds,
+                         stream);
+}
+
+hipError_t filtered_hop_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, filtered_hop_kernel_symbol(dim, generic, ip), 64 * waves,
+                                                      lds);
+}
+
 }  // namespace alaya_amd

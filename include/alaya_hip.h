@@ -144,6 +144,48 @@ int alaya_index_filtered_search_device(alaya_index *ix, const float *d_queries, 
                                        const uint32_t *d_allow_words, uint32_t n_masks,
                                        const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
                                        uint32_t *d_counters, void *stream);
+/* Through search: filtered graph search that expands through disallowed neighbours (f32 rows; opt-in, the
+ * default stays alaya_index_filtered_search).  A neighbour the query may not see is not measured and not kept:
+ * the search steps through it to its own neighbours, so the pool of ef entries holds allowed rows only and ef
+ * keeps its usual meaning.  It is meant for small and middling allowed shares, where the plain traversal loses
+ * recall, and the caller chooses: at the same ef it computes about 5x the plain traversal's distances at a share
+ * of 0.5 and fewer from 0.05 down, and it reads one adjacency row per row stepped through, which is what its time
+ * goes to at small shares ("Round 17", has the measured sweep; below a share of about 0.1
+ * alaya_index_flat_search_filtered is exact and faster).
+ *
+ * passable(v): the query's allow bit of row v is set and, on an index with a validity bitmap, v is valid.
+ * For one query, with a traversal pool `pool` (LinearPool, capacity ef), a result pool `result` (capacity k)
+ * and a visited set:
+ *   1. Entry.  The overlay descent is alaya_index_batch_search's, with distances on any row; n_dist_upper and
+ *      n_hops_upper are unchanged.  The level-0 entry is marked visited and inserted into `pool` whatever its
+ *      bit; it is offered to `result` only when passable.  On a graph without overlay this holds for every
+ *      entry point in turn, repeats included.
+ *   2. Pop and direct pass.  While pool.has_next(): u = pool.pop(), n_expand += 1.  Walk u's level-0 row in
+ *      adjacency order, to the first empty slot (graphs flagged for repeated edges: first occurrence only).
+ *      Each neighbour v not yet visited is marked visited.  If passable(v): d = dist(q, v), n_dist += 1,
+ *      pool.insert(v, d), result.insert(v, d).  Otherwise v is appended to this pop's through list T; no
+ *      distance is computed for it and it never enters a pool.
+ *   3. Through pass.  For each w in T, in order: n_through += 1, then walk w's level-0 row under the same
+ *      rules.  A row x that is not passable is skipped and is not marked visited (it may later be stepped
+ *      through as somebody's direct neighbour).  A passable x not yet visited is marked visited, then
+ *      d = dist(q, x), n_dist += 1, pool.insert(x, d), result.insert(x, d).  One level only: no recursion.
+ *   4. Output.  `result` in order, then empty slots (0xffffffff, FLT_MAX).  counters per query are (n_dist,
+ *      n_expand, n_dist_upper, n_hops_upper), nq x 4 as everywhere; n_through (nullable) receives nq uint32.
+ * The kernel gathers candidates of several through rows into one distance pass and one merge; the observable
+ * state equals that of the sequential inserts in the arrival order above.  So: with a mask of all ones and no
+ * bitmap T is always empty, and the answer and the four counters are alaya_index_filtered_search's (hence
+ * alaya_index_batch_search's); a removed row is stepped through instead of entering the pool at FLT_MAX; with
+ * an all-zero mask the query ends after the entry's pop with n_dist = 0 and every slot empty.
+ * Arguments, their errors and ALAYA_FILTER_GRID as for alaya_index_filtered_search; an index with SQ8 codes is
+ * refused. */
+int alaya_index_filtered_search_hop(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                    const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                    uint32_t *ids, float *dists, uint32_t *counters, uint32_t *n_through);
+/* Same on device buffers, asynchronous on `stream`; the indices of d_mask_of_query are not checked. */
+int alaya_index_filtered_search_hop_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t ef,
+                                           const uint32_t *d_allow_words, uint32_t n_masks,
+                                           const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
+                                           uint32_t *d_counters, uint32_t *d_n_through, void *stream);
 /* Filtered graph search of an index with SQ8 codes (alaya_index_set_sq8): the k nearest rows, by exact
  * f32 distance, among the candidates a filtered SQ8 traversal collects.
  *   1. Traversal: alaya_index_batch_search_sq8's at the same ef -- the query encoded to codes, code-to-code

@@ -1,6 +1,6 @@
 """Filtered graph search on a GIST-shaped device-built index: rate and recall per allowed share.
 
-usage: python tools/filter_sweep.py [--leg sweep|filtered|plain] [--n 1000000] [--nq 1000] [--ef 387]
+usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact|through] [--n 1000000] [--nq 1000] [--ef 387]
                                     [--shares 1,0.5,0.1,0.01] [--reps 20] [--out FILE]
 
   sweep     per share of allowed rows: queries/s of DeviceIndex.filtered_search_device, recall@10 of its
@@ -30,6 +30,13 @@ usage: python tools/filter_sweep.py [--leg sweep|filtered|plain] [--n 1000000] [
             flat search's time, last the two crossover shares.  --space sq8 runs config 5's shape
             (768-d IP, SQ8 codes) against filtered_search_sq8_device at m = k, ef 200; --dim 128 the
             narrow L2 shape.
+  through   the through search (DeviceIndex.filtered_search_hop_device: the traversal that steps through
+            disallowed neighbours) alternated with the plain filtered search and the exact filtered scan in
+            one process, --rounds rounds of --reps launches each after 3 warm-ups, per share of 1 .. 0.01:
+            medians and spreads, distances and rows stepped through per query, recall@10 over the allowed
+            rows against calc_gt_device(base[rows]) -- at --ef, and at the smallest ef of --hop-ladder that
+            reaches recall 0.95, where one does -- and which of the three calls is the fastest that reaches
+            0.95.  At share 1 the through / plain ratio is the all-ones launch's cost.
 Every leg prints one JSON line per measurement; --out appends them to a file."""
 import argparse
 import json
@@ -278,9 +285,122 @@ def exact_leg(args):
               against_unmasked_exact_share=crossover(lambda g: float(np.median(flat_ms)))))
 
 
+def through_leg(args):
+    """The through search against the plain filtered search and the exact filtered scan, alternated."""
+    import torch
+    from alayalite_amd import _native
+    from alayalite_amd.utils import calc_gt_device, pack_allow
+    from workloads.datasets import gist_like
+
+    ext = _native._ext
+    st = torch.cuda.current_stream()
+    n, nq, ef = args.n, args.nq, args.ef
+    base, queries = gist_like(n, nq, dim=args.dim)
+    dev = ext.DeviceIndex(0)
+    dev.set_base(base, 0)
+    dev.build_graph(32, 100, 100, 0, 0, 2)
+    print("index ready", file=sys.stderr, flush=True)
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    ids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+    dd = torch.empty((nq, K), dtype=torch.float32, device="cuda")
+    pids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+    eids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+    cnt = torch.empty((nq, 4), dtype=torch.int32, device="cuda")
+    pcnt = torch.empty((nq, 4), dtype=torch.int32, device="cuda")
+    thr = torch.empty((nq,), dtype=torch.int32, device="cuda")
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim, k=K, metric="l2")
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    def timed(run, reps):
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def stats(ms):
+        med = float(np.median(ms))
+        return dict(ms=sorted(ms), median=med, spread=(max(ms) - min(ms)) / med, qps=nq / med * 1e3)
+
+    for share in [float(s) for s in args.shares.split(",")]:
+        allow = np.ones(n, bool) if share >= 1.0 else np.random.default_rng(100 + round(1000 * share)).random(n) < share
+        words = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+        rows = np.flatnonzero(allow)
+        gt_local, _ = calc_gt_device(base[rows], queries, K)
+        gt = np.where(gt_local >= 0, rows[np.clip(gt_local, 0, len(rows) - 1)], -1)
+
+        def through(e=ef):
+            dev.filtered_search_hop_device(qd.data_ptr(), nq, K, e, words.data_ptr(), 1, 0, ids.data_ptr(), dd.data_ptr(),
+                                           cnt.data_ptr(), thr.data_ptr(), st.cuda_stream)
+
+        def plain():
+            dev.filtered_search_device(qd.data_ptr(), nq, K, ef, words.data_ptr(), 1, 0, pids.data_ptr(), dd.data_ptr(),
+                                       pcnt.data_ptr(), st.cuda_stream)
+
+        def exact():
+            dev.flat_search_filtered_device(qd.data_ptr(), nq, K, words.data_ptr(), 1, 0, eids.data_ptr(), dd.data_ptr(),
+                                            st.cuda_stream)
+
+        def measured():
+            torch.cuda.synchronize()
+            return (recall(ids.cpu().numpy().view(np.uint32), gt), float(cnt.cpu().numpy()[:, 0].mean()),
+                    float(cnt.cpu().numpy()[:, 1].mean()), float(thr.cpu().numpy().mean()))
+
+        # the exact scan costs allowed rows x queries: fewer launches per round at the large shares
+        exact_reps = max(2, min(args.reps, int(args.reps * 0.05 / share)))
+        t_ms, p_ms, e_ms = [], [], []
+        for _ in range(args.rounds):  # alternated: same rows, graph, queries and clocks
+            t_ms.append(timed(through, args.reps))
+            p_ms.append(timed(plain, args.reps))
+            e_ms.append(timed(exact, exact_reps))
+        through()
+        t_recall, t_dist, t_pops, t_rows = measured()
+        plan_t = {k: int(v) for k, v in dev.last_plan().items()}
+        plain()
+        torch.cuda.synchronize()
+        plan_p = {k: int(v) for k, v in dev.last_plan().items()}
+        p_recall = recall(pids.cpu().numpy().view(np.uint32), gt)
+        rec = dict(leg="through", share=share, allowed=int(allow.sum()), ef=ef, through=stats(t_ms), plain=stats(p_ms),
+                   exact=stats(e_ms), through_recall_at_10=t_recall, plain_recall_at_10=p_recall,
+                   exact_recall_at_10=recall(eids.cpu().numpy().view(np.uint32), gt), through_n_dist=t_dist,
+                   through_pops=t_pops, through_rows=t_rows, plain_n_dist=float(pcnt.cpu().numpy()[:, 0].mean()),
+                   through_over_plain=float(np.median(t_ms)) / float(np.median(p_ms)), through_plan=plan_t, plain_plan=plan_p)
+        # the smallest ef of the ladder at which the through search reaches recall 0.95
+        small = None
+        for e in [int(v) for v in args.hop_ladder.split(",")]:
+            if e >= ef:
+                break
+            through(e)
+            r, nd, pops, nr = measured()
+            if r >= 0.95:
+                ms = [timed(lambda: through(e), args.reps) for _ in range(args.rounds)]
+                small = dict(ef=e, recall_at_10=r, n_dist=nd, pops=pops, rows=nr, **stats(ms))
+                break
+        rec["through_smallest_ef_at_0.95"] = small
+        calls = {"exact": float(np.median(e_ms))}
+        if p_recall >= 0.95:
+            calls["plain"] = float(np.median(p_ms))
+        if small is not None:
+            calls["through"] = small["median"]
+        elif t_recall >= 0.95:
+            calls["through"] = float(np.median(t_ms))
+        rec["fastest_call_at_0.95"] = min(calls, key=calls.get)
+        emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact"), default="sweep")
+    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact", "through"), default="sweep")
     ap.add_argument("--space", choices=("f32", "sq8"), default="f32",
                     help="exact leg: f32 = GIST-shaped L2 rows; sq8 = config 5's text-like IP rows with SQ8 codes")
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -289,6 +409,7 @@ def main():
     ap.add_argument("--ef", type=int, default=0, help="0 = 387 (the sq8 legs: found on --ef-ladder)")
     ap.add_argument("--ef-ladder", default="40,60,80,100,120,160,200,260,340,440")
     ap.add_argument("--shares", default="", help="default 1,0.5,0.1,0.01 (exact leg: 0.001,0.01,0.05,0.1,0.2,0.5,1)")
+    ap.add_argument("--hop-ladder", default="10,16,24,32,48,64,96,128,192,256", help="through leg: the short ef sweep")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default="")
@@ -298,6 +419,11 @@ def main():
         args.dim = args.dim or (768 if args.space == "sq8" else 960)
         args.ef = args.ef or (200 if args.space == "sq8" else 387)
         return exact_leg(args)
+    if args.leg == "through":
+        args.shares = args.shares or "1,0.5,0.2,0.1,0.05,0.02,0.01"
+        args.dim = args.dim or 960
+        args.ef = args.ef or 387
+        return through_leg(args)
     args.shares = args.shares or "1,0.5,0.1,0.01"
     if args.leg in ("sq8", "sq8-ab"):
         args.dim = args.dim or 768
