@@ -671,6 +671,39 @@ SearchParams graph_search_params(alaya_index *ix, const float *d_q, uint64_t nq,
   return p;
 }
 
+// The search space of one launch: the SQ8 codes with their scale and min (sq8; the caller has checked
+// ix->has_sq8), and the visited second level that goes with the space -- spill table or bitset.
+void set_search_space(alaya_index *ix, SearchParams &p, bool sq8, uint32_t ef) {
+  if (sq8) {
+    p.sq8_order = ix->sq8_order;
+    p.codes = ix->codes.as<uint8_t>();
+    p.code_stride = ix->code_stride;
+    p.sq_min = ix->sq_min.as<float>();
+    p.sq_max = ix->sq_max.as<float>();
+  }
+  p.stab_log2 = spill_table_log2(p.sq8_order, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2))), ef);
+}
+
+// Records the plan of the launch about to go out (alaya_index_last_launch / _last_plan, and which of the
+// scout, helper and screen counters its `searchers` will have written) and resets the work counter.
+void record_launch(alaya_index *ix, SearchParams &p, int grid, int wg_waves, size_t lds, int per_cu, uint64_t searchers,
+                   hipStream_t stream) {
+  ix->last_grid = static_cast<uint32_t>(grid);
+  ix->last_waves = static_cast<uint32_t>(wg_waves);
+  ix->last_lds = static_cast<uint32_t>(lds);
+  ix->last_hash_log2 = p.hash_log2;
+  ix->last_compact = p.vis_rbits != alaya_amd::kVisWide ? 1u : 0u;
+  ix->last_per_cu = static_cast<uint32_t>(per_cu);
+  ix->last_scout = p.scout;
+  ix->last_scout_policy = p.scout_policy;
+  ix->scout_stats_slots = p.scout ? searchers : 0;
+  ix->help_stats_slots = p.help ? searchers : 0;
+  ix->screen_stats_slots = p.screen ? searchers : 0;
+  ix->work.reserve(4);
+  p.work_counter = ix->work.as<uint32_t>();
+  hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
+}
+
 void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef,
                uint32_t *d_ids, float *d_dists, uint32_t *d_cnt, hipStream_t stream,
                uint64_t *d_stamps = nullptr, bool sq8 = false, uint32_t fill_id = 0) {
@@ -682,16 +715,8 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   SearchParams p = graph_search_params(ix, d_q, nq, k, ef, d_ids, d_dists, d_cnt);
   p.stamps = d_stamps;
   p.fill_id = fill_id;
-  if (sq8) {
-    if (!ix->has_sq8) throw ArgError("index has no SQ8 codes");
-    p.sq8_order = ix->sq8_order;
-    p.codes = ix->codes.as<uint8_t>();
-    p.code_stride = ix->code_stride;
-    p.sq_min = ix->sq_min.as<float>();
-    p.sq_max = ix->sq_max.as<float>();
-  }
-  // the visited second level: spill table or bitset
-  p.stab_log2 = spill_table_log2(p.sq8_order, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2))), ef);
+  if (sq8 && !ix->has_sq8) throw ArgError("index has no SQ8 codes");
+  set_search_space(ix, p, sq8, ef);
   if (const char *e = std::getenv("ALAYA_HELP_FLAGS")) p.help_flags = static_cast<uint32_t>(std::strtoul(e, nullptr, 10));
   const SearchPlan plan = plan_search(ix, p, search_request(ix, p, nq, ef, stream), nq, ef, stream);
   if (p.screen >= 2) {  // 2 and 3 read the same records
@@ -703,35 +728,22 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
   scratch_acquire(ix, stream);
   const uint64_t searchers = static_cast<uint64_t>(plan.grid) * plan.W;
   prepare_spill(ix, p, searchers, stream);
-  ix->last_grid = static_cast<uint32_t>(plan.grid);
   const int wg_waves = p.scout ? 2 * plan.W : plan.W;  // a scout wave beside every searcher
-  ix->last_waves = static_cast<uint32_t>(wg_waves);
-  ix->last_lds = static_cast<uint32_t>(plan.lds);
-  ix->last_hash_log2 = p.hash_log2;
-  ix->last_compact = p.vis_rbits != alaya_amd::kVisWide ? 1u : 0u;
-  ix->last_per_cu = static_cast<uint32_t>(plan.per_cu);
-  ix->last_scout = p.scout;
-  ix->scout_stats_slots = p.scout ? searchers : 0;
   if (p.scout) {
     ix->scout_stats.reserve(searchers * 16);
     p.scout_stats = ix->scout_stats.as<uint32_t>();
     ix->scout_policy_stats.reserve(searchers * 12);
     p.scout_policy_stats = ix->scout_policy_stats.as<uint32_t>();
   }
-  ix->last_scout_policy = p.scout_policy;
-  ix->help_stats_slots = p.help ? searchers : 0;
   if (p.help) {
     ix->help_stats.reserve(searchers * 12);
     p.help_stats = ix->help_stats.as<uint32_t>();
   }
-  ix->screen_stats_slots = p.screen ? searchers : 0;
   if (p.screen) {
     ix->screen_stats.reserve(searchers * 8);
     p.screen_stats = ix->screen_stats.as<uint32_t>();
   }
-  ix->work.reserve(4);
-  p.work_counter = ix->work.as<uint32_t>();
-  hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
+  record_launch(ix, p, plan.grid, wg_waves, plan.lds, plan.per_cu, searchers, stream);
   hip_check(alaya_amd::launch_search(*plan.variant, p, plan.grid, wg_waves, plan.lds, stream), "search launch");
   scratch_release(ix, stream);
 }
@@ -765,15 +777,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   if (ix->graph_n > ix->n) throw ArgError("graph has more nodes than base vectors");
   SearchParams p = graph_search_params(ix, d_q, nq, k, ef, d_ids, d_dists, d_cnt);
   p.fill_id = 0xffffffffu;  // empty result slots: (all-ones id, FLT_MAX), exact_search's convention
-  if (sq8) {
-    p.sq8_order = ix->sq8_order;
-    p.codes = ix->codes.as<uint8_t>();
-    p.code_stride = ix->code_stride;
-    p.sq_min = ix->sq_min.as<float>();
-    p.sq_max = ix->sq_max.as<float>();
-    // the visited second level: spill table or bitset, as do_search plans it
-    p.stab_log2 = spill_table_log2(p.sq8_order, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2))), ef);
-  }
+  set_search_space(ix, p, sq8, ef);  // (f32 rows: the bitset, as do_search plans it)
   const SearchVariant &plain = resolve_search_variant({ix->dim, p.ip, p.sq8_order, ix->generic, 0});
   int W = search_waves(p);
   while (W > 1 && static_cast<uint64_t>(W) > nq) W /= 2;
@@ -802,18 +806,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   scratch_acquire(ix, stream);
   const uint64_t searchers = static_cast<uint64_t>(grid) * W;
   prepare_spill(ix, p, searchers, stream);
-  ix->last_grid = static_cast<uint32_t>(grid);
-  ix->last_waves = static_cast<uint32_t>(W);
-  ix->last_lds = static_cast<uint32_t>(lds);
-  ix->last_hash_log2 = p.hash_log2;
-  ix->last_compact = p.vis_rbits != kVisWide ? 1u : 0u;
-  ix->last_per_cu = static_cast<uint32_t>(per_cu);
-  ix->last_scout = 0;
-  ix->last_scout_policy = 0;
-  ix->scout_stats_slots = ix->help_stats_slots = ix->screen_stats_slots = 0;
-  ix->work.reserve(4);
-  p.work_counter = ix->work.as<uint32_t>();
-  hip_check(hipMemsetAsync(p.work_counter, 0, 4, stream), "hipMemsetAsync");
+  record_launch(ix, p, grid, W, lds, per_cu, searchers, stream);  // (no scout, helpers or screen: p has none set)
   hip_check(sq8   ? launch_filtered_sq8_search(p, f, grid, W, lds, stream)
             : hop ? launch_filtered_hop_search(p, f, HopParams{d_through}, grid, W, lds, stream)
                   : launch_filtered_search(p, f, grid, W, lds, stream),
@@ -981,9 +974,23 @@ void ensure_tiles(alaya_index *ix, int base_exp, hipStream_t stream) {
 // The sample's 32nd is about the whole base's (32 S)-th, so the full scan appends ~S candidates
 // per (query, chunk) instead of ~32 (1 + ln(chunk rows / 32)).  Results are unchanged: the
 // threshold only rejects rows that cannot reach the merged 32, and the merge's bound uses it.
-void flat_prescan(alaya_index *ix, alaya_amd::FlatParams &p, int *blocks, hipStream_t s) {
+void flat_prescan(alaya_index *ix, alaya_amd::FlatParams &p, hipStream_t s) {
   const char *env = std::getenv("ALAYA_FLAT_PRESCAN");
   const uint64_t step = env ? std::strtoull(env, nullptr, 10) : 0;
+  // the scan of the sample `q` describes, over nqg query groups, then the thresholds, which p starts from
+  auto sample_scan = [&](alaya_amd::FlatParams q, int nqg) {
+    q.tau_init = nullptr;
+    q.out_ids = nullptr;
+    q.out_dists = nullptr;
+    q.flags = nullptr;
+    q.merge_count = nullptr;
+    q.ablate = 0;
+    ix->flat_tau.reserve(p.nq * 4);
+    q.tau_out = ix->flat_tau.as<float>();
+    hip_check(alaya_amd::launch_flat_scan(q, nqg * q.n_chunks, s), "flat prescan");
+    hip_check(alaya_amd::launch_flat_threshold(q, s), "flat threshold");
+    p.tau_init = q.tau_out;
+  };
   if (p.tiles != nullptr) {
     // The single-role scan's prescan: group minima over a sample of whole tile records (every S-th;
     // default S = records / 4096, on when the base has >= 8192 records, ALAYA_FLAT_PRESCAN=S forces S,
@@ -1005,19 +1012,8 @@ void flat_prescan(alaya_index *ix, alaya_amd::FlatParams &p, int *blocks, hipStr
     q.tile_step = static_cast<uint32_t>(S);
     q.n_scan_tiles = sample;
     q.n_chunks = static_cast<int>(groups);
-    q.tau_init = nullptr;
-    q.out_ids = nullptr;
-    q.out_dists = nullptr;
-    q.flags = nullptr;
-    q.merge_count = nullptr;
-    q.ablate = 0;
-    ix->flat_tau.reserve(p.nq * 4);
-    q.tau_out = ix->flat_tau.as<float>();
     const int qpb = alaya_amd::flat_tiles_queries();
-    const int nqg = static_cast<int>((p.nq + qpb - 1) / qpb);
-    hip_check(alaya_amd::launch_flat_scan(q, nqg * q.n_chunks, s), "flat prescan");
-    hip_check(alaya_amd::launch_flat_threshold(q, s), "flat threshold");
-    p.tau_init = q.tau_out;
+    sample_scan(q, static_cast<int>((p.nq + qpb - 1) / qpb));
     return;
   }
   if (step < 2 || p.n / step < 1024) return;
@@ -1029,18 +1025,7 @@ void flat_prescan(alaya_index *ix, alaya_amd::FlatParams &p, int *blocks, hipStr
   q.row_step = static_cast<uint32_t>(step);
   const int nqg = static_cast<int>((p.nq + 127) / 128);
   q.n_chunks = flat_chunks(ix, nqg, q.n);  // <= p.n_chunks: the candidate buffers fit
-  q.tau_init = nullptr;
-  q.out_ids = nullptr;
-  q.out_dists = nullptr;
-  q.flags = nullptr;
-  q.merge_count = nullptr;
-  q.ablate = 0;
-  ix->flat_tau.reserve(p.nq * 4);
-  q.tau_out = ix->flat_tau.as<float>();
-  hip_check(alaya_amd::launch_flat_scan(q, nqg * q.n_chunks, s), "flat prescan");
-  hip_check(alaya_amd::launch_flat_threshold(q, s), "flat threshold");
-  p.tau_init = q.tau_out;
-  (void)blocks;
+  sample_scan(q, nqg);
 }
 
 alaya_amd::FlatParams flat_params(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t *d_ids,
@@ -1127,6 +1112,93 @@ alaya_amd::FlatParams flat_params(alaya_index *ix, const float *d_q, uint64_t nq
   *blocks = nqg * chunks;
   return p;
 }
+
+// One flat search on device buffers: row norms (first call only), the launch's parameters, the optional
+// prescan, the scan and the merge.  Returns the parameters (the host entry point reads p.single).
+alaya_amd::FlatParams flat_scan_merge(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t *d_ids,
+                                      float *d_dists, uint32_t *d_flags, hipStream_t s, bool no_single = false) {
+  ensure_norms(ix, s);
+  int blocks = 0;
+  alaya_amd::FlatParams p = flat_params(ix, d_q, nq, k, d_ids, d_dists, d_flags, &blocks, s, no_single);
+  flat_prescan(ix, p, s);
+  hip_check(alaya_amd::launch_flat_scan(p, blocks, s), "flat scan");
+  hip_check(alaya_amd::launch_flat_merge(p, s), "flat merge");
+  return p;
+}
+
+// The rerank of an SQ8 search: rescores on the f32 rows, against d_q, the ids the search stage left in
+// ix->sq_ids (r.n_src per query) and writes the first r.k to d_ids / d_dists.  The caller sets r.k, r.n_src,
+// r.n_take, r.zeros and r.fill_id.
+void rerank_sq_ids(alaya_index *ix, const float *d_q, uint64_t nq, alaya_amd::RerankParams r, uint32_t *d_ids,
+                   float *d_dists, hipStream_t s) {
+  SearchParams p = base_params(ix);
+  p.queries = d_q;
+  p.nq = nq;
+  p.q_stride = ix->dim;
+  r.search_ids = ix->sq_ids.as<uint32_t>();
+  r.out_ids = d_ids;
+  r.out_dists = d_dists;
+  hip_check(alaya_amd::launch_rerank(p, r, s), "rerank launch");
+  scratch_release(ix, s);  // the rerank read the search's ids from the index's sq_ids buffer
+}
+
+// ---- what the filtered entry points check of their masks ------------------------------------------
+// what: the message's prefix, "filtered search" or "flat filtered search".
+void check_mask_indices(const char *what, const uint32_t *h_mask_of_query, uint64_t nq, uint32_t n_masks) {
+  for (uint64_t i = 0; i < nq; ++i)
+    if (h_mask_of_query[i] >= n_masks) throw ArgError(std::string(what) + ": mask_of_query holds an index past n_masks");
+}
+// host_indices: mask_of_query can be read here (the host entry points'); a device pointer is taken as it is.
+void check_masks(const char *what, uint64_t nq, uint32_t n_masks, const uint32_t *mask_of_query, bool host_indices) {
+  if (nq && (n_masks == 0 || (n_masks > 1 && !mask_of_query)))
+    throw ArgError(std::string(what) + ": mask_of_query may be null only with one mask");
+  if (host_indices && mask_of_query) check_mask_indices(what, mask_of_query, nq, n_masks);
+}
+
+// ---- staging of the host entry points: the index's own buffers, on ix->stream ----------------------
+// `what` labels a failed copy; the entry points' labels differ and are part of their error texts.
+const float *stage_rows(alaya_index *ix, DevBuf &buf, const float *rows, uint64_t nq, const char *what) {
+  buf.reserve(nq * ix->dim * 4);
+  hip_check(hipMemcpyAsync(buf.ptr, rows, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream), what);
+  return buf.as<float>();
+}
+// Reserves the query buffer and the (nq, k) result buffers the call uses, then uploads the queries.
+const float *stage_queries(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k,
+                           const char *what = "upload queries", bool dists = true, bool counters = true) {
+  ix->q_buf.reserve(nq * ix->dim * 4);
+  ix->id_buf.reserve(nq * k * 4);
+  if (dists) ix->dist_buf.reserve(nq * k * 4);
+  if (counters) ix->cnt_buf.reserve(nq * 16);
+  return stage_rows(ix, ix->q_buf, queries, nq, what);
+}
+// The SQ8 rerank's own query form: uploaded only when given and not the queries themselves, else null.
+const float *stage_rerank_queries(alaya_index *ix, const float *rerank_queries, const float *queries, uint64_t nq,
+                                  const char *what = "upload rerank queries") {
+  if (!rerank_queries || rerank_queries == queries) return nullptr;
+  return stage_rows(ix, ix->rr_q_buf, rerank_queries, nq, what);
+}
+const uint32_t *stage_masks(alaya_index *ix, const uint32_t *allow_words, uint32_t n_masks) {
+  const size_t bytes = static_cast<size_t>(n_masks) * ((ix->n + 31) / 32) * 4;
+  ix->allow_buf.reserve(bytes);
+  hip_check(hipMemcpyAsync(ix->allow_buf.ptr, allow_words, bytes, hipMemcpyHostToDevice, ix->stream), "upload masks");
+  return ix->allow_buf.as<uint32_t>();
+}
+// group_buf is reserved for nq indices even when none are given (null then, as the kernels expect)
+const uint32_t *stage_mask_indices(alaya_index *ix, const uint32_t *mask_of_query, uint64_t nq) {
+  ix->group_buf.reserve(nq * 4);
+  if (!mask_of_query) return nullptr;
+  hip_check(hipMemcpyAsync(ix->group_buf.ptr, mask_of_query, nq * 4, hipMemcpyHostToDevice, ix->stream),
+            "upload mask indices");
+  return ix->group_buf.as<uint32_t>();
+}
+// ids, and dists / counters where asked for, back to the host; the caller synchronises (stream_sync)
+void fetch_results(alaya_index *ix, uint64_t nq, uint32_t k, uint32_t *ids, float *dists, uint32_t *counters) {
+  hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+  if (dists) hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+  if (counters)
+    hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
+}
+void stream_sync(alaya_index *ix, const char *what) { hip_check(hipStreamSynchronize(ix->stream), what); }
 
 }  // namespace
 
@@ -1958,20 +2030,11 @@ int alaya_index_batch_search(alaya_index *ix, const float *queries, uint64_t nq,
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     if (nq == 0 || k == 0) return;
-    ix->q_buf.reserve(nq * ix->dim * 4);
-    ix->id_buf.reserve(nq * k * 4);
-    ix->dist_buf.reserve(nq * k * 4);
-    ix->cnt_buf.reserve(nq * 16);
-    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice,
-                             ix->stream), "upload queries");
-    do_search(ix, ix->q_buf.as<float>(), nq, k, ef, ix->id_buf.as<uint32_t>(),
-              ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream);
-    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (dists)
-      hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (counters)
-      hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    hip_check(hipStreamSynchronize(ix->stream), "search");
+    const float *d_q = stage_queries(ix, queries, nq, k);
+    do_search(ix, d_q, nq, k, ef, ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(),
+              ix->stream);
+    fetch_results(ix, nq, k, ids, dists, counters);
+    stream_sync(ix, "search");
   });
 }
 
@@ -1982,8 +2045,7 @@ static int filtered_search_device_call(alaya_index *ix, const float *d_queries, 
                                        uint32_t *d_through) {
   return guarded_scratch(ix, [&] {
     if (!ix || (nq && (!d_queries || !d_ids || !d_allow_words))) throw ArgError("invalid arguments");
-    if (nq && (n_masks == 0 || (n_masks > 1 && !d_mask_of_query)))
-      throw ArgError("filtered search: mask_of_query may be null only with one mask");
+    check_masks("filtered search", nq, n_masks, d_mask_of_query, false);
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     do_filtered_search(ix, d_queries, nq, k, ef, d_allow_words, d_mask_of_query, d_ids, d_dists, d_counters,
@@ -2011,42 +2073,23 @@ static int filtered_search_host_call(alaya_index *ix, const float *queries, uint
                                      uint32_t *ids, float *dists, uint32_t *counters, bool hop, uint32_t *n_through) {
   return guarded_scratch(ix, [&] {
     if (!ix || (nq && (!queries || !ids || !allow_words))) throw ArgError("invalid arguments");
-    if (nq && (n_masks == 0 || (n_masks > 1 && !mask_of_query)))
-      throw ArgError("filtered search: mask_of_query may be null only with one mask");
-    if (mask_of_query)
-      for (uint64_t i = 0; i < nq; ++i)
-        if (mask_of_query[i] >= n_masks) throw ArgError("filtered search: mask_of_query holds an index past n_masks");
+    check_masks("filtered search", nq, n_masks, mask_of_query, true);
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     if (k == 0 || k > 224) throw ArgError("filtered search: k must be in 1..224");
     if (nq == 0) return;
-    const size_t mask_bytes = static_cast<size_t>(n_masks) * ((ix->n + 31) / 32) * 4;
-    ix->q_buf.reserve(nq * ix->dim * 4);
-    ix->id_buf.reserve(nq * k * 4);
-    ix->dist_buf.reserve(nq * k * 4);
-    ix->cnt_buf.reserve(nq * 16);
-    ix->allow_buf.reserve(mask_bytes);
-    ix->group_buf.reserve(nq * 4);
-    if (hop && n_through) ix->through_buf.reserve(nq * 4);
-    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
-              "upload queries");
-    hip_check(hipMemcpyAsync(ix->allow_buf.ptr, allow_words, mask_bytes, hipMemcpyHostToDevice, ix->stream),
-              "upload masks");
-    if (mask_of_query)
-      hip_check(hipMemcpyAsync(ix->group_buf.ptr, mask_of_query, nq * 4, hipMemcpyHostToDevice, ix->stream),
-                "upload mask indices");
-    do_filtered_search(ix, ix->q_buf.as<float>(), nq, k, ef, ix->allow_buf.as<uint32_t>(),
-                       mask_of_query ? ix->group_buf.as<uint32_t>() : nullptr, ix->id_buf.as<uint32_t>(),
-                       ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream, false, hop,
-                       hop && n_through ? ix->through_buf.as<uint32_t>() : nullptr);
-    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (dists)
-      hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (counters)
-      hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (hop && n_through)
+    const bool through_out = hop && n_through;  // through_buf only for the through call that asks for the counts
+    const float *d_q = stage_queries(ix, queries, nq, k);
+    const uint32_t *d_allow = stage_masks(ix, allow_words, n_masks);
+    const uint32_t *d_groups = stage_mask_indices(ix, mask_of_query, nq);
+    if (through_out) ix->through_buf.reserve(nq * 4);
+    do_filtered_search(ix, d_q, nq, k, ef, d_allow, d_groups, ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(),
+                       ix->cnt_buf.as<uint32_t>(), ix->stream, false, hop,
+                       through_out ? ix->through_buf.as<uint32_t>() : nullptr);
+    fetch_results(ix, nq, k, ids, dists, counters);
+    if (through_out)
       hip_check(hipMemcpyAsync(n_through, ix->through_buf.ptr, nq * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    hip_check(hipStreamSynchronize(ix->stream), "filtered search");
+    stream_sync(ix, "filtered search");
   });
 }
 
@@ -2071,20 +2114,15 @@ int alaya_index_profile_search(alaya_index *ix, const float *queries, uint64_t n
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     if (nq == 0 || k == 0) return;
-    ix->q_buf.reserve(nq * ix->dim * 4);
-    ix->id_buf.reserve(nq * k * 4);
-    ix->cnt_buf.reserve(nq * 16);
     DevBuf st;
     st.reserve(nq * 64);
     hip_check(hipMemsetAsync(st.ptr, 0, nq * 64, ix->stream), "memset");
-    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream), "H2D");
-    do_search(ix, ix->q_buf.as<float>(), nq, k, ef, ix->id_buf.as<uint32_t>(), nullptr,
-              ix->cnt_buf.as<uint32_t>(), ix->stream, st.as<uint64_t>(), space == 1);
-    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (counters)
-      hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    const float *d_q = stage_queries(ix, queries, nq, k, "H2D", /*dists=*/false);
+    do_search(ix, d_q, nq, k, ef, ix->id_buf.as<uint32_t>(), nullptr, ix->cnt_buf.as<uint32_t>(), ix->stream,
+              st.as<uint64_t>(), space == 1);
+    fetch_results(ix, nq, k, ids, nullptr, counters);
     hip_check(hipMemcpyAsync(stamps, st.ptr, nq * 64, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    hip_check(hipStreamSynchronize(ix->stream), "profile search");
+    stream_sync(ix, "profile search");
   });
 }
 
@@ -2213,21 +2251,13 @@ static void sq8_search_dev(alaya_index *ix, const float *d_q, const float *d_rq,
   const uint32_t search_fill = (corrected || shard == 0) ? 0xffffffffu : 0u;
   do_search(ix, d_q, nq, ks, ef, ix->sq_ids.as<uint32_t>(), ix->sq_d.as<float>(), d_cnt, s, nullptr, true,
             search_fill);
-  SearchParams p = base_params(ix);
-  p.queries = d_rq ? d_rq : d_q;
-  p.nq = nq;
-  p.q_stride = ix->dim;
   alaya_amd::RerankParams r{};
-  r.search_ids = ix->sq_ids.as<uint32_t>();
   r.k = k;
   r.n_src = ks;
   r.n_take = corrected ? ef : std::min(k, ef);
   r.zeros = (!corrected && shard != 0 && ef > k) ? ef - k : 0u;
   r.fill_id = shard >= 0 ? 0xffffffffu : 0u;
-  r.out_ids = d_ids;
-  r.out_dists = d_dists;
-  hip_check(alaya_amd::launch_rerank(p, r, s), "rerank launch");
-  scratch_release(ix, s);  // the rerank read the search's ids from the index's sq_ids buffer
+  rerank_sq_ids(ix, d_rq ? d_rq : d_q, nq, r, d_ids, d_dists, s);
 }
 
 int alaya_index_batch_search_sq8(alaya_index *ix, const float *queries, const float *rerank_queries,
@@ -2238,25 +2268,13 @@ int alaya_index_batch_search_sq8(alaya_index *ix, const float *queries, const fl
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     if (nq == 0 || k == 0) return;
-    ix->q_buf.reserve(nq * ix->dim * 4);
-    ix->id_buf.reserve(nq * k * 4);
-    ix->dist_buf.reserve(nq * k * 4);
-    ix->cnt_buf.reserve(nq * 16);
-    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream), "H2D");
-    const float *d_rq = nullptr;
-    if (rerank && rerank_queries && rerank_queries != queries) {
-      ix->rr_q_buf.reserve(nq * ix->dim * 4);
-      hip_check(hipMemcpyAsync(ix->rr_q_buf.ptr, rerank_queries, nq * ix->dim * 4, hipMemcpyHostToDevice,
-                               ix->stream), "H2D");
-      d_rq = ix->rr_q_buf.as<float>();
-    }
-    sq8_search_dev(ix, ix->q_buf.as<float>(), d_rq, nq, k, ef, rerank, ix->id_buf.as<uint32_t>(),
-                   ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream);
-    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (dists) hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (counters)
-      hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    hip_check(hipStreamSynchronize(ix->stream), "sq8 search");
+    const float *d_q = stage_queries(ix, queries, nq, k, "H2D");
+    // without a rerank nothing reads the second query form: not uploaded (the filtered call always uploads it)
+    const float *d_rq = rerank ? stage_rerank_queries(ix, rerank_queries, queries, nq, "H2D") : nullptr;
+    sq8_search_dev(ix, d_q, d_rq, nq, k, ef, rerank, ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(),
+                   ix->cnt_buf.as<uint32_t>(), ix->stream);
+    fetch_results(ix, nq, k, ids, dists, counters);
+    stream_sync(ix, "sq8 search");
   });
 }
 
@@ -2305,21 +2323,13 @@ static void filtered_sq8_dev(alaya_index *ix, const float *d_q, const float *d_r
   // are then not written
   if (const char *e = std::getenv("ALAYA_FILTER_RERANK"))
     if (std::atoi(e) == 0) return;
-  SearchParams p = base_params(ix);
-  p.queries = d_rq ? d_rq : d_q;
-  p.nq = nq;
-  p.q_stride = ix->dim;
   alaya_amd::RerankParams r{};
-  r.search_ids = ix->sq_ids.as<uint32_t>();
   r.k = k;
   r.n_src = m;
   r.n_take = m;
   r.zeros = 0u;
   r.fill_id = 0xffffffffu;
-  r.out_ids = d_ids;
-  r.out_dists = d_dists;
-  hip_check(alaya_amd::launch_rerank(p, r, s), "rerank launch");
-  scratch_release(ix, s);  // the rerank read the candidates from the index's sq_ids buffer
+  rerank_sq_ids(ix, d_rq ? d_rq : d_q, nq, r, d_ids, d_dists, s);
 }
 
 int alaya_index_filtered_search_sq8_device(alaya_index *ix, const float *d_queries, const float *d_rerank_queries,
@@ -2329,8 +2339,7 @@ int alaya_index_filtered_search_sq8_device(alaya_index *ix, const float *d_queri
                                            uint32_t *d_counters, void *stream) {
   return guarded_scratch(ix, [&] {
     if (!ix || (nq && (!d_queries || !d_ids || !d_allow_words))) throw ArgError("invalid arguments");
-    if (nq && (n_masks == 0 || (n_masks > 1 && !d_mask_of_query)))
-      throw ArgError("filtered search: mask_of_query may be null only with one mask");
+    check_masks("filtered search", nq, n_masks, d_mask_of_query, false);
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     filtered_sq8_dev(ix, d_queries, d_rerank_queries, nq, k, ef, pool, d_allow_words, d_mask_of_query, d_ids, d_dists,
@@ -2343,45 +2352,19 @@ int alaya_index_filtered_search_sq8(alaya_index *ix, const float *queries, const
                                     const uint32_t *mask_of_query, uint32_t *ids, float *dists, uint32_t *counters) {
   return guarded_scratch(ix, [&] {
     if (!ix || (nq && (!queries || !ids || !allow_words))) throw ArgError("invalid arguments");
-    if (nq && (n_masks == 0 || (n_masks > 1 && !mask_of_query)))
-      throw ArgError("filtered search: mask_of_query may be null only with one mask");
-    if (mask_of_query)
-      for (uint64_t i = 0; i < nq; ++i)
-        if (mask_of_query[i] >= n_masks) throw ArgError("filtered search: mask_of_query holds an index past n_masks");
+    check_masks("filtered search", nq, n_masks, mask_of_query, true);
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     if (k == 0 || k > 224) throw ArgError("filtered search: k must be in 1..224");
     if (nq == 0) return;
-    const size_t mask_bytes = static_cast<size_t>(n_masks) * ((ix->n + 31) / 32) * 4;
-    ix->q_buf.reserve(nq * ix->dim * 4);
-    ix->id_buf.reserve(nq * k * 4);
-    ix->dist_buf.reserve(nq * k * 4);
-    ix->cnt_buf.reserve(nq * 16);
-    ix->allow_buf.reserve(mask_bytes);
-    ix->group_buf.reserve(nq * 4);
-    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
-              "upload queries");
-    const float *d_rq = nullptr;
-    if (rerank_queries && rerank_queries != queries) {
-      ix->rr_q_buf.reserve(nq * ix->dim * 4);
-      hip_check(hipMemcpyAsync(ix->rr_q_buf.ptr, rerank_queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
-                "upload rerank queries");
-      d_rq = ix->rr_q_buf.as<float>();
-    }
-    hip_check(hipMemcpyAsync(ix->allow_buf.ptr, allow_words, mask_bytes, hipMemcpyHostToDevice, ix->stream),
-              "upload masks");
-    if (mask_of_query)
-      hip_check(hipMemcpyAsync(ix->group_buf.ptr, mask_of_query, nq * 4, hipMemcpyHostToDevice, ix->stream),
-                "upload mask indices");
-    filtered_sq8_dev(ix, ix->q_buf.as<float>(), d_rq, nq, k, ef, pool, ix->allow_buf.as<uint32_t>(),
-                     mask_of_query ? ix->group_buf.as<uint32_t>() : nullptr, ix->id_buf.as<uint32_t>(),
+    const float *d_q = stage_queries(ix, queries, nq, k);
+    const float *d_rq = stage_rerank_queries(ix, rerank_queries, queries, nq);
+    const uint32_t *d_allow = stage_masks(ix, allow_words, n_masks);
+    const uint32_t *d_groups = stage_mask_indices(ix, mask_of_query, nq);
+    filtered_sq8_dev(ix, d_q, d_rq, nq, k, ef, pool, d_allow, d_groups, ix->id_buf.as<uint32_t>(),
                      ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream);
-    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (dists)
-      hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (counters)
-      hip_check(hipMemcpyAsync(counters, ix->cnt_buf.ptr, nq * 16, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    hip_check(hipStreamSynchronize(ix->stream), "filtered sq8 search");
+    fetch_results(ix, nq, k, ids, dists, counters);
+    stream_sync(ix, "filtered sq8 search");
   });
 }
 
@@ -2397,7 +2380,7 @@ int alaya_index_flat_diag(alaya_index *ix, const float *d_queries, uint64_t nq, 
     ensure_norms(ix, s);
     int blocks = 0;
     alaya_amd::FlatParams p = flat_params(ix, d_queries, nq, k, d_ids, d_dists, d_flags, &blocks, s);
-    flat_prescan(ix, p, &blocks, s);
+    flat_prescan(ix, p, s);
     p.ablate = ablate;
     p.merge_count = d_merge_count;
     hip_check(alaya_amd::launch_flat_scan(p, blocks, s), "flat scan");
@@ -2414,12 +2397,7 @@ int alaya_index_flat_search_device(alaya_index *ix, const float *d_queries, uint
     if (nq == 0) return;
     hipStream_t s = static_cast<hipStream_t>(stream);
     scratch_acquire(ix, s);
-    ensure_norms(ix, s);
-    int blocks = 0;
-    alaya_amd::FlatParams p = flat_params(ix, d_queries, nq, k, d_ids, d_dists, d_flags, &blocks, s);
-    flat_prescan(ix, p, &blocks, s);
-    hip_check(alaya_amd::launch_flat_scan(p, blocks, s), "flat scan");
-    hip_check(alaya_amd::launch_flat_merge(p, s), "flat merge");
+    flat_scan_merge(ix, d_queries, nq, k, d_ids, d_dists, d_flags, s);
     scratch_release(ix, s);
   });
 }
@@ -2433,39 +2411,26 @@ int alaya_index_flat_search(alaya_index *ix, const float *queries, uint64_t nq, 
     if (n_recomputed) *n_recomputed = 0;
     if (nq == 0) return;
     scratch_acquire(ix, ix->stream);
-    ensure_norms(ix, ix->stream);
-    ix->q_buf.reserve(nq * ix->dim * 4);
-    ix->id_buf.reserve(nq * k * 4);
-    ix->dist_buf.reserve(nq * k * 4);
+    ensure_norms(ix, ix->stream);  // ahead of the upload, where it always ran: flat_scan_merge's own call then returns at once
+    const float *d_q = stage_queries(ix, queries, nq, k, "H2D", /*dists=*/true, /*counters=*/false);
     ix->flag_buf.reserve(nq * 4);
-    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream), "H2D");
-    int blocks = 0;
-    alaya_amd::FlatParams p = flat_params(ix, ix->q_buf.as<float>(), nq, k, ix->id_buf.as<uint32_t>(),
-                                          ix->dist_buf.as<float>(), ix->flag_buf.as<uint32_t>(), &blocks, ix->stream);
-    flat_prescan(ix, p, &blocks, ix->stream);
     std::vector<uint32_t> flags(nq);
     std::vector<float> dv(nq * k);
-    auto run = [&]() {
-      hip_check(alaya_amd::launch_flat_scan(p, blocks, ix->stream), "flat scan");
-      hip_check(alaya_amd::launch_flat_merge(p, ix->stream), "flat merge");
-      hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-      hip_check(hipMemcpyAsync(dv.data(), ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    auto run = [&](bool no_single) {
+      const alaya_amd::FlatParams p = flat_scan_merge(ix, d_q, nq, k, ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(),
+                                                      ix->flag_buf.as<uint32_t>(), ix->stream, no_single);
+      fetch_results(ix, nq, k, ids, dv.data(), nullptr);
       hip_check(hipMemcpyAsync(flags.data(), ix->flag_buf.ptr, nq * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-      hip_check(hipStreamSynchronize(ix->stream), "flat search");
+      stream_sync(ix, "flat search");
+      return p.single;
     };
-    run();
-    if (p.single) {
+    if (run(false)) {
       // the single pass's bound is ~8x the split's: on data whose 10th and 32nd distances are that
       // close, more than 1 % of the queries flagged reruns the launch with the bf16 hi/lo split
       // before any exhaustive redo
       uint64_t nflag = 0;
       for (uint64_t q = 0; q < nq; ++q) nflag += flags[q] ? 1 : 0;
-      if (nflag * 100 > nq) {
-        p = flat_params(ix, ix->q_buf.as<float>(), nq, k, ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(),
-                        ix->flag_buf.as<uint32_t>(), &blocks, ix->stream, /*no_single=*/true);
-        flat_prescan(ix, p, &blocks, ix->stream);
-        run();
-      }
+      if (nflag * 100 > nq) run(true);
     }
     scratch_release(ix, ix->stream);
     // queries whose shortlist bound did not hold: exhaustive exact distances on the device, over
@@ -2543,8 +2508,7 @@ static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uin
     groups_read.resize(nq);
     hip_check(hipMemcpyAsync(groups_read.data(), d_groups, nq * 4, hipMemcpyDeviceToHost, stream), "D2H");
     hip_check(hipStreamSynchronize(stream), "flat filtered search");
-    for (uint32_t g : groups_read)
-      if (g >= n_masks) throw ArgError("flat filtered search: mask_of_query holds an index past n_masks");
+    check_mask_indices("flat filtered search", groups_read.data(), nq, n_masks);
     h_groups = groups_read.data();
   }
   // the queries of each mask as an index list, so outputs land in the caller's order
@@ -2632,8 +2596,7 @@ int alaya_index_flat_search_filtered_device(alaya_index *ix, const float *d_quer
                                             void *stream) {
   return guarded([&] {
     if (!ix || (nq && (!d_queries || !d_ids || !d_allow_words))) throw ArgError("invalid arguments");
-    if (nq && (n_masks == 0 || (n_masks > 1 && !d_mask_of_query)))
-      throw ArgError("flat filtered search: mask_of_query may be null only with one mask");
+    check_masks("flat filtered search", nq, n_masks, d_mask_of_query, false);  // (do_flat_filtered reads them back)
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     do_flat_filtered(ix, d_queries, nq, k, d_allow_words, n_masks, nullptr, d_mask_of_query, d_ids, d_dists,
@@ -2646,32 +2609,20 @@ int alaya_index_flat_search_filtered(alaya_index *ix, const float *queries, uint
                                      uint32_t *ids, float *dists) {
   return guarded([&] {
     if (!ix || (nq && (!queries || !ids || !allow_words))) throw ArgError("invalid arguments");
-    if (nq && (n_masks == 0 || (n_masks > 1 && !mask_of_query)))
-      throw ArgError("flat filtered search: mask_of_query may be null only with one mask");
-    if (mask_of_query)
-      for (uint64_t i = 0; i < nq; ++i)
-        if (mask_of_query[i] >= n_masks) throw ArgError("flat filtered search: mask_of_query holds an index past n_masks");
+    check_masks("flat filtered search", nq, n_masks, mask_of_query, true);
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     if (k == 0 || k > 224) throw ArgError("flat filtered search: k must be in 1..224");
     if (nq == 0) return;
-    const size_t mask_bytes = static_cast<size_t>(n_masks) * ((ix->n + 31) / 32) * 4;
     scratch_acquire(ix, ix->stream);  // the upload buffers below are the index's, shared with other launches
-    ix->q_buf.reserve(nq * ix->dim * 4);
-    ix->id_buf.reserve(nq * k * 4);
-    ix->dist_buf.reserve(nq * k * 4);
-    ix->allow_buf.reserve(mask_bytes);
-    hip_check(hipMemcpyAsync(ix->q_buf.ptr, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, ix->stream),
-              "upload queries");
-    hip_check(hipMemcpyAsync(ix->allow_buf.ptr, allow_words, mask_bytes, hipMemcpyHostToDevice, ix->stream),
-              "upload masks");
-    do_flat_filtered(ix, ix->q_buf.as<float>(), nq, k, ix->allow_buf.as<uint32_t>(), n_masks,
-                     n_masks > 1 ? mask_of_query : nullptr, nullptr, ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(),
-                     ix->stream);
-    hip_check(hipMemcpyAsync(ids, ix->id_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    if (dists)
-      hip_check(hipMemcpyAsync(dists, ix->dist_buf.ptr, nq * k * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-    hip_check(hipStreamSynchronize(ix->stream), "flat filtered search");
+    const float *d_q = stage_queries(ix, queries, nq, k, "upload queries", /*dists=*/true, /*counters=*/false);
+    const uint32_t *d_allow = stage_masks(ix, allow_words, n_masks);
+    // the scan orders the queries by mask on the host: it takes the host's indices (no group_buf), and only
+    // where there is more than one mask to order by
+    do_flat_filtered(ix, d_q, nq, k, d_allow, n_masks, n_masks > 1 ? mask_of_query : nullptr, nullptr,
+                     ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(), ix->stream);
+    fetch_results(ix, nq, k, ids, dists, nullptr);
+    stream_sync(ix, "flat filtered search");
   });
 }
 

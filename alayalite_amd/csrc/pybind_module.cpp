@@ -49,6 +49,51 @@ void check(int rc) {
   throw std::runtime_error(msg);
 }
 
+// numpy arguments as C-contiguous arrays of one element type, converted on the way in where need be
+template <typename T>
+using CArray = py::array_t<T, py::array::c_style | py::array::forcecast>;
+using F32Array = CArray<float>;
+using U32Array = CArray<uint32_t>;
+using U8Array = CArray<uint8_t>;
+
+// "no row" as a 64-bit id: an empty result slot (widen_ids), alaya_index_insert on a full index
+constexpr uint64_t kNoId64 = UINT64_MAX;
+
+template <typename T>
+py::array_t<T> out2d(uint64_t rows, uint64_t cols) {
+  return py::array_t<T>({static_cast<py::ssize_t>(rows), static_cast<py::ssize_t>(cols)});
+}
+
+// a device address (or stream handle) handed over as an integer, e.g. torch's data_ptr()
+template <typename T>
+T *dptr(uintptr_t p) {
+  return reinterpret_cast<T *>(p);
+}
+
+// The filtered calls' masks: allow_words uint32 [n_masks, ceil(n / 32)] over n rows, and mask_of_query, each of
+// the nq queries' mask or None (the C call then accepts one mask only).  `indices` owns what of_query points to.
+struct Masks {
+  const uint32_t *words = nullptr;
+  uint32_t n_masks = 0;
+  const uint32_t *of_query = nullptr;
+  U32Array indices;
+};
+
+Masks parse_masks(const U32Array &allow_words, const py::object &mask_of_query, uint64_t n, uint64_t nq) {
+  if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n + 31) / 32 || allow_words.shape(0) < 1)
+    throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
+  Masks m;
+  m.words = allow_words.data();
+  m.n_masks = static_cast<uint32_t>(allow_words.shape(0));
+  if (!mask_of_query.is_none()) {
+    m.indices = U32Array(mask_of_query);
+    if (m.indices.ndim() != 1 || static_cast<uint64_t>(m.indices.shape(0)) != nq)
+      throw py::value_error("mask_of_query must hold one index per query");
+    m.of_query = m.indices.data();
+  }
+  return m;
+}
+
 enum DType { kF32 = 0, kI8, kU8, kF64, kI32, kU32 };
 
 DType dtype_code(const py::dtype &dt) {
@@ -86,6 +131,24 @@ void to_float(const void *src, DType t, size_t count, float *dst) {
 // get_l2_sqr_sq8_func / get_ip_sqr_sq8_func pick the AVX-512 kernel on AVX-512F hosts, else AVX2
 // (distance_l2.ipp:694-708): the device reproduces the order this host's reference build uses.
 int host_sq8_order() { return __builtin_cpu_supports("avx512f") ? 2 : 1; }
+
+// A host graph's arrays: (n x R l0, levels, upper_off, upper_edges, ep, upper_R, eps); levels and upper_off
+// are None for a graph without overlay.
+py::tuple graph_arrays_of(const alaya_graph *g) {
+  uint64_t n, nue;
+  uint32_t R, upper_R, ep, max_level, n_eps;
+  int has_overlay;
+  check(alaya_graph_info(g, &n, &R, &has_overlay, &upper_R, &ep, &max_level, &nue, &n_eps));
+  py::array_t<uint32_t> l0 = out2d<uint32_t>(n, R);
+  py::array_t<uint32_t> levels(static_cast<py::ssize_t>(has_overlay ? n : 0));
+  py::array_t<uint64_t> off(static_cast<py::ssize_t>(has_overlay ? n : 0));
+  py::array_t<uint32_t> ue(static_cast<py::ssize_t>(nue));
+  py::array_t<uint32_t> eps(static_cast<py::ssize_t>(n_eps));
+  check(alaya_graph_export(g, l0.mutable_data(), levels.mutable_data(), off.mutable_data(), ue.mutable_data(),
+                           eps.mutable_data()));
+  return py::make_tuple(l0, has_overlay ? py::object(levels) : py::none(), has_overlay ? py::object(off) : py::none(), ue,
+                        ep, upper_R, eps);
+}
 
 // The launch controls and the device counters of the last search, as both index classes expose them.
 class LaunchControls {
@@ -248,20 +311,13 @@ class PyIndexInterface : public LaunchControls {
     py::array q = prepare_queries(queries);
     const uint64_t nq = q.shape(0);
     std::vector<uint32_t> ids32(nq * topk);
-    py::array_t<float> dists({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    py::array_t<float> dists = out2d<float>(nq, topk);
     {
       py::gil_scoped_release nogil;
       check(alaya_index_flat_search(ix_, static_cast<const float *>(q.data()), nq, topk, ids32.data(),
                                     dists.mutable_data(), nullptr));
     }
-    py::array ids(params_.id_type_, std::vector<py::ssize_t>{static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
-    if (id_bytes_ == 4) {
-      std::memcpy(ids.mutable_data(), ids32.data(), ids32.size() * 4);
-    } else {
-      auto *o = static_cast<uint64_t *>(ids.mutable_data());
-      for (size_t i = 0; i < ids32.size(); ++i) o[i] = ids32[i] == 0xffffffffu ? UINT64_MAX : ids32[i];
-    }
-    return py::make_tuple(ids, dists);
+    return py::make_tuple(widen_ids(ids32, nq, topk, true), dists);
   }
 
   // --- extra (not in the reference binding): the topk nearest rows among those a mask allows
@@ -271,8 +327,7 @@ class PyIndexInterface : public LaunchControls {
   // candidate pool (0 = the default), which an unquantized index does not have.  through: the traversal
   // that steps through disallowed neighbours (alaya_index_filtered_search_hop; f32 indexes only), whose rows
   // stepped through per query last_through() then holds.
-  py::object filtered_search(py::array queries, uint32_t topk, uint32_t ef,
-                             py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
+  py::object filtered_search(py::array queries, uint32_t topk, uint32_t ef, U32Array allow_words,
                              py::object mask_of_query, uint32_t pool, bool through) {
     if (!graph_) throw std::runtime_error("Index is not init yet");
     const bool sq8 = params_.quantization_type_ == QuantizationType::SQ8;
@@ -282,86 +337,47 @@ class PyIndexInterface : public LaunchControls {
     if (!sq8 && pool != 0) throw py::value_error("pool applies to SQ8 indexes only");
     py::array q = prepare_queries(queries);
     const uint64_t nq = q.shape(0);
-    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n_ + 31) / 32 || allow_words.shape(0) < 1)
-      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
-    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
-    const uint32_t *gp = nullptr;
-    if (!mask_of_query.is_none()) {
-      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
-      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
-        throw py::value_error("mask_of_query must hold one index per query");
-      gp = groups.data();
-    }
+    const Masks m = parse_masks(allow_words, mask_of_query, n_, nq);
     std::vector<uint32_t> ids32(nq * topk);
-    py::array_t<float> dists({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    py::array_t<float> dists = out2d<float>(nq, topk);
     last_counters_.assign(nq * 4, 0);
     last_through_.assign(through ? nq : 0, 0);
-    const uint32_t *ap = allow_words.data();
-    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
+    const float *qp = static_cast<const float *>(q.data());
     if (sq8) {
       // the traversal encodes the query as given, the rerank's f32 distance takes the normalised one (run())
-      const float *rq = static_cast<const float *>(q.data());
-      const float *sq = raw_queries_.empty() ? rq : raw_queries_.data();
+      const float *sq = raw_queries_.empty() ? qp : raw_queries_.data();
       py::gil_scoped_release nogil;
-      check(alaya_index_filtered_search_sq8(ix_, sq, rq, nq, topk, ef, pool, ap, n_masks, gp, ids32.data(),
+      check(alaya_index_filtered_search_sq8(ix_, sq, qp, nq, topk, ef, pool, m.words, m.n_masks, m.of_query, ids32.data(),
                                             dists.mutable_data(), last_counters_.data()));
     } else if (through) {
       py::gil_scoped_release nogil;
-      check(alaya_index_filtered_search_hop(ix_, static_cast<const float *>(q.data()), nq, topk, ef, ap, n_masks, gp,
-                                            ids32.data(), dists.mutable_data(), last_counters_.data(),
-                                            last_through_.data()));
+      check(alaya_index_filtered_search_hop(ix_, qp, nq, topk, ef, m.words, m.n_masks, m.of_query, ids32.data(),
+                                            dists.mutable_data(), last_counters_.data(), last_through_.data()));
     } else {
       py::gil_scoped_release nogil;
-      check(alaya_index_filtered_search(ix_, static_cast<const float *>(q.data()), nq, topk, ef, ap, n_masks, gp,
-                                        ids32.data(), dists.mutable_data(), last_counters_.data()));
+      check(alaya_index_filtered_search(ix_, qp, nq, topk, ef, m.words, m.n_masks, m.of_query, ids32.data(),
+                                        dists.mutable_data(), last_counters_.data()));
     }
-    py::array ids(params_.id_type_, std::vector<py::ssize_t>{static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
-    if (id_bytes_ == 4) {
-      std::memcpy(ids.mutable_data(), ids32.data(), ids32.size() * 4);
-    } else {
-      auto *o = static_cast<uint64_t *>(ids.mutable_data());
-      for (size_t i = 0; i < ids32.size(); ++i) o[i] = ids32[i] == 0xffffffffu ? UINT64_MAX : ids32[i];
-    }
-    return py::make_tuple(ids, dists);
+    return py::make_tuple(widen_ids(ids32, nq, topk, true), dists);
   }
 
   // --- extra (not in the reference binding): exact_search over the rows a mask allows
   // (alaya_index_flat_search_filtered: a scan of the allowed valid rows, for small allowed shares).
   // allow_words / mask_of_query as for filtered_search; the query forms and the empty slots are
   // exact_search's.  An SQ8 index is scanned on its f32 rows.
-  py::object exact_search_filtered(py::array queries, uint32_t topk,
-                                   py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
-                                   py::object mask_of_query) {
+  py::object exact_search_filtered(py::array queries, uint32_t topk, U32Array allow_words, py::object mask_of_query) {
     if (!graph_) throw std::runtime_error("Index is not init yet");
     py::array q = prepare_queries(queries);
     const uint64_t nq = q.shape(0);
-    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n_ + 31) / 32 || allow_words.shape(0) < 1)
-      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
-    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
-    const uint32_t *gp = nullptr;
-    if (!mask_of_query.is_none()) {
-      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
-      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
-        throw py::value_error("mask_of_query must hold one index per query");
-      gp = groups.data();
-    }
+    const Masks m = parse_masks(allow_words, mask_of_query, n_, nq);
     std::vector<uint32_t> ids32(nq * topk);
-    py::array_t<float> dists({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
-    const uint32_t *ap = allow_words.data();
-    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
+    py::array_t<float> dists = out2d<float>(nq, topk);
     {
       py::gil_scoped_release nogil;
-      check(alaya_index_flat_search_filtered(ix_, static_cast<const float *>(q.data()), nq, topk, ap, n_masks, gp,
-                                             ids32.data(), dists.mutable_data()));
+      check(alaya_index_flat_search_filtered(ix_, static_cast<const float *>(q.data()), nq, topk, m.words, m.n_masks,
+                                             m.of_query, ids32.data(), dists.mutable_data()));
     }
-    py::array ids(params_.id_type_, std::vector<py::ssize_t>{static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
-    if (id_bytes_ == 4) {
-      std::memcpy(ids.mutable_data(), ids32.data(), ids32.size() * 4);
-    } else {
-      auto *o = static_cast<uint64_t *>(ids.mutable_data());
-      for (size_t i = 0; i < ids32.size(); ++i) o[i] = ids32[i] == 0xffffffffu ? UINT64_MAX : ids32[i];
-    }
-    return py::make_tuple(ids, dists);
+    return py::make_tuple(widen_ids(ids32, nq, topk, true), dists);
   }
 
   uint64_t get_data_num() const { return n_; }
@@ -398,7 +414,7 @@ class PyIndexInterface : public LaunchControls {
       py::gil_scoped_release nogil;
       check(alaya_index_insert(ix_, q.data(), row.data(), ef, &id));
     }
-    if (id == UINT64_MAX) return py::int_(id_bytes_ == 4 ? uint64_t{0xffffffffu} : UINT64_MAX);
+    if (id == kNoId64) return py::int_(id_bytes_ == 4 ? uint64_t{0xffffffffu} : kNoId64);
     const size_t es = dtype_size(dtype_);
     raw_.insert(raw_.end(), static_cast<const char *>(arr.data()), static_cast<const char *>(arr.data()) + dim_ * es);
     rows_f32_.insert(rows_f32_.end(), row.begin(), row.end());
@@ -463,7 +479,7 @@ class PyIndexInterface : public LaunchControls {
     return out;
   }
   py::array last_counters() const {
-    py::array_t<uint32_t> out({static_cast<py::ssize_t>(last_counters_.size() / 4), static_cast<py::ssize_t>(4)});
+    py::array_t<uint32_t> out = out2d<uint32_t>(last_counters_.size() / 4, 4);
     std::memcpy(out.mutable_data(), last_counters_.data(), last_counters_.size() * 4);
     return out;
   }
@@ -475,10 +491,10 @@ class PyIndexInterface : public LaunchControls {
   int rerank_mode() const { return rerank_mode_; }
   py::array device_distances(py::array queries, py::array_t<uint32_t> ids) {
     py::array q = prepare_queries(queries);
-    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> idc(ids);
+    U32Array idc(ids);
     const uint64_t nq = q.shape(0);
     const uint32_t n = static_cast<uint32_t>(idc.size());
-    py::array_t<float> out({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(n)});
+    py::array_t<float> out = out2d<float>(nq, n);
     check(alaya_index_distances(ix_, static_cast<const float *>(q.data()), nq, idc.data(), n,
                                 out.mutable_data()));
     return out;
@@ -487,19 +503,7 @@ class PyIndexInterface : public LaunchControls {
   py::tuple graph_arrays() {
     if (!graph_) throw std::runtime_error("index is not fitted");
     sync_graph();
-    uint64_t n, nue;
-    uint32_t R, upper_R, ep, max_level, n_eps;
-    int has_overlay;
-    check(alaya_graph_info(graph_, &n, &R, &has_overlay, &upper_R, &ep, &max_level, &nue, &n_eps));
-    py::array_t<uint32_t> l0({static_cast<py::ssize_t>(n), static_cast<py::ssize_t>(R)});
-    py::array_t<uint32_t> levels(static_cast<py::ssize_t>(has_overlay ? n : 0));
-    py::array_t<uint64_t> off(static_cast<py::ssize_t>(has_overlay ? n : 0));
-    py::array_t<uint32_t> ue(static_cast<py::ssize_t>(nue));
-    py::array_t<uint32_t> eps(static_cast<py::ssize_t>(n_eps));
-    check(alaya_graph_export(graph_, l0.mutable_data(), levels.mutable_data(), off.mutable_data(),
-                             ue.mutable_data(), eps.mutable_data()));
-    return py::make_tuple(l0, has_overlay ? py::object(levels) : py::none(),
-                          has_overlay ? py::object(off) : py::none(), ue, ep, upper_R, eps);
+    return graph_arrays_of(graph_);
   }
 
  private:
@@ -548,7 +552,7 @@ class PyIndexInterface : public LaunchControls {
       to_float(arr.data(), dtype_, nq * dim_, raw_queries_.data());
     }
     if (params_.metric_ == MetricType::COS) normalize_in_place(arr, nq);  // raw_space.hpp:267-269
-    py::array_t<float> qf({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(dim_)});
+    py::array_t<float> qf = out2d<float>(nq, dim_);
     to_float(arr.data(), dtype_, nq * dim_, qf.mutable_data());
     return qf;
   }
@@ -558,7 +562,7 @@ class PyIndexInterface : public LaunchControls {
     py::array q = prepare_queries(queries);
     const uint64_t nq = q.shape(0);
     std::vector<uint32_t> ids32(nq * topk);
-    py::array_t<float> dists({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
+    py::array_t<float> dists = out2d<float>(nq, topk);
     last_counters_.assign(nq * 4, 0);
     if (params_.quantization_type_ == QuantizationType::SQ8) {
       // SQ8Space::QueryComputer encodes the query as given (no COS normalisation), the rerank's
@@ -579,14 +583,21 @@ class PyIndexInterface : public LaunchControls {
       check(alaya_index_batch_search(ix_, static_cast<const float *>(q.data()), nq, topk, ef,
                                      ids32.data(), dists.mutable_data(), last_counters_.data()));
     }
+    // no empty id to map here: batch_search fills short results with id 0, as the reference does
+    return {widen_ids(ids32, nq, topk, false), want_dist ? py::array(dists) : py::array()};
+  }
+
+  // The device's 32-bit ids in the index's id type.  map_empty: the empty slot 0xffffffff becomes the 64-bit
+  // type's maximum (the filtered and exact calls; a 32-bit id type holds it as it is).
+  py::array widen_ids(const std::vector<uint32_t> &ids32, uint64_t nq, uint32_t topk, bool map_empty) const {
     py::array ids(params_.id_type_, std::vector<py::ssize_t>{static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(topk)});
     if (id_bytes_ == 4) {
       std::memcpy(ids.mutable_data(), ids32.data(), ids32.size() * 4);
     } else {
       auto *o = static_cast<uint64_t *>(ids.mutable_data());
-      for (size_t i = 0; i < ids32.size(); ++i) o[i] = ids32[i];
+      for (size_t i = 0; i < ids32.size(); ++i) o[i] = map_empty && ids32[i] == 0xffffffffu ? kNoId64 : ids32[i];
     }
-    return {ids, want_dist ? py::array(dists) : py::array()};
+    return ids;
   }
 
   // first insert/remove: hand the device index a host mirror of the graph, rows and bitmap
@@ -631,43 +642,38 @@ class PyIndexInterface : public LaunchControls {
   }
 
   // RawSpace save/load (raw_space.hpp:219-250) + SequentialStorage (sequential_storage.hpp:110-142)
-  void save_raw(const std::string &path) const {
-    std::ofstream w(path, std::ios::binary);
-    if (!w.is_open()) throw std::runtime_error("Cannot open file " + path);
+  // What the raw and the SQ8 space files share: the space header, then SequentialStorage's -- its header, the
+  // capacity's rows of `item` bytes each padded to 64, the validity bitmap (valid empty = every row).
+  void write_space(std::ofstream &w, uint32_t item, uint64_t delete_cnt, const void *rows,
+                   const std::vector<uint8_t> &valid) const {
     const int32_t metric = static_cast<int32_t>(params_.metric_);
-    const size_t es = dtype_size(dtype_);
-    const uint32_t data_size = static_cast<uint32_t>(dim_ * es);
     const uint64_t cap = std::max<uint64_t>(params_.capacity_, n_);
     w.write(reinterpret_cast<const char *>(&metric), 4);
-    w.write(reinterpret_cast<const char *>(&data_size), 4);
+    w.write(reinterpret_cast<const char *>(&item), 4);  // data_size_
     w.write(reinterpret_cast<const char *>(&dim_), 4);
-    auto put_id = [&](uint64_t v) {
-      if (id_bytes_ == 4) {
-        uint32_t x = static_cast<uint32_t>(v);
-        w.write(reinterpret_cast<const char *>(&x), 4);
-      } else {
-        w.write(reinterpret_cast<const char *>(&v), 8);
-      }
-    };
-    put_id(n_);   // item_cnt_
-    put_id(delete_cnt_);  // delete_cnt_
-    put_id(cap);  // capacity_
-    const uint64_t item = data_size, aligned = (item + 63) / 64 * 64, align = 64;
-    w.write(reinterpret_cast<const char *>(&item), 8);
-    w.write(reinterpret_cast<const char *>(&aligned), 8);
-    w.write(reinterpret_cast<const char *>(&cap), 8);
-    w.write(reinterpret_cast<const char *>(&n_), 8);
-    w.write(reinterpret_cast<const char *>(&align), 8);
-    std::vector<char> row(aligned, 0);
+    for (uint64_t v : {n_, delete_cnt, cap}) {  // item_cnt_, delete_cnt_, capacity_ in the id type
+      const uint32_t x = static_cast<uint32_t>(v);
+      if (id_bytes_ == 4) w.write(reinterpret_cast<const char *>(&x), 4);
+      else w.write(reinterpret_cast<const char *>(&v), 8);
+    }
+    const uint64_t hdr[5] = {item, (item + 63ull) / 64 * 64, cap, n_, 64};  // item, aligned item, capacity, pos, alignment
+    w.write(reinterpret_cast<const char *>(hdr), sizeof(hdr));
+    std::vector<char> row(hdr[1], 0);
     for (uint64_t i = 0; i < cap; ++i) {
       std::fill(row.begin(), row.end(), 0);
-      if (i < n_) std::memcpy(row.data(), raw_.data() + i * item, item);
-      w.write(row.data(), static_cast<std::streamsize>(aligned));
+      if (i < n_) std::memcpy(row.data(), static_cast<const char *>(rows) + i * item, item);
+      w.write(row.data(), static_cast<std::streamsize>(row.size()));
     }
     std::vector<uint8_t> bitmap((cap + 7) / 8, 0);
     for (uint64_t i = 0; i < n_; ++i)
-      if (valid_.empty() || (valid_[i / 8] >> (i % 8)) & 1) bitmap[i / 8] |= static_cast<uint8_t>(1u << (i % 8));
+      if (valid.empty() || (valid[i / 8] >> (i % 8)) & 1) bitmap[i / 8] |= static_cast<uint8_t>(1u << (i % 8));
     w.write(reinterpret_cast<const char *>(bitmap.data()), static_cast<std::streamsize>(bitmap.size()));
+  }
+
+  void save_raw(const std::string &path) const {
+    std::ofstream w(path, std::ios::binary);
+    if (!w.is_open()) throw std::runtime_error("Cannot open file " + path);
+    write_space(w, static_cast<uint32_t>(dim_ * dtype_size(dtype_)), delete_cnt_, raw_.data(), valid_);
     if (!w) throw std::runtime_error("write failed: " + path);
   }
 
@@ -726,38 +732,7 @@ class PyIndexInterface : public LaunchControls {
   void save_sq8(const std::string &path) const {
     std::ofstream w(path, std::ios::binary);
     if (!w.is_open()) throw std::runtime_error("Cannot open file " + path);
-    const int32_t metric = static_cast<int32_t>(params_.metric_);
-    const uint32_t data_size = dim_;
-    const uint64_t cap = std::max<uint64_t>(params_.capacity_, n_);
-    w.write(reinterpret_cast<const char *>(&metric), 4);
-    w.write(reinterpret_cast<const char *>(&data_size), 4);
-    w.write(reinterpret_cast<const char *>(&dim_), 4);
-    auto put_id = [&](uint64_t v) {
-      if (id_bytes_ == 4) {
-        uint32_t x = static_cast<uint32_t>(v);
-        w.write(reinterpret_cast<const char *>(&x), 4);
-      } else {
-        w.write(reinterpret_cast<const char *>(&v), 8);
-      }
-    };
-    put_id(n_);
-    put_id(0);
-    put_id(cap);
-    const uint64_t item = dim_, aligned = (item + 63) / 64 * 64, align = 64;
-    w.write(reinterpret_cast<const char *>(&item), 8);
-    w.write(reinterpret_cast<const char *>(&aligned), 8);
-    w.write(reinterpret_cast<const char *>(&cap), 8);
-    w.write(reinterpret_cast<const char *>(&n_), 8);
-    w.write(reinterpret_cast<const char *>(&align), 8);
-    std::vector<char> row(aligned, 0);
-    for (uint64_t i = 0; i < cap; ++i) {
-      std::fill(row.begin(), row.end(), 0);
-      if (i < n_) std::memcpy(row.data(), sq_codes_.data() + i * item, item);
-      w.write(row.data(), static_cast<std::streamsize>(aligned));
-    }
-    std::vector<uint8_t> bitmap((cap + 7) / 8, 0);
-    for (uint64_t i = 0; i < n_; ++i) bitmap[i / 8] |= static_cast<uint8_t>(1u << (i % 8));
-    w.write(reinterpret_cast<const char *>(bitmap.data()), static_cast<std::streamsize>(bitmap.size()));
+    write_space(w, dim_, 0, sq_codes_.data(), {});  // one byte per dimension, no delete count, every row valid
     w.write(reinterpret_cast<const char *>(&dim_), 4);
     w.write(reinterpret_cast<const char *>(sq_min_.data()), dim_ * 4);
     w.write(reinterpret_cast<const char *>(sq_max_.data()), dim_ * 4);
@@ -826,8 +801,7 @@ class Graph {
   Graph(const Graph &) = delete;
   Graph &operator=(const Graph &) = delete;
 
-  static std::shared_ptr<Graph> build(py::array_t<float, py::array::c_style | py::array::forcecast> data,
-                                      int metric, uint32_t R, uint32_t efc, uint32_t threads,
+  static std::shared_ptr<Graph> build(F32Array data, int metric, uint32_t R, uint32_t efc, uint32_t threads,
                                       uint64_t seed) {
     if (data.ndim() != 2) throw py::value_error("data must be 2D");
     alaya_graph *g = nullptr;
@@ -845,20 +819,19 @@ class Graph {
     check(alaya_graph_load(path.c_str(), id_bytes, &g));
     return std::make_shared<Graph>(g);
   }
-  static std::shared_ptr<Graph> from_arrays(py::array_t<uint32_t, py::array::c_style | py::array::forcecast> l0,
-                                            py::object levels, py::object upper_off, py::object upper_edges,
+  static std::shared_ptr<Graph> from_arrays(U32Array l0, py::object levels, py::object upper_off, py::object upper_edges,
                                             uint32_t upper_R, uint32_t ep, py::object eps) {
     alaya_graph *g = nullptr;
     const uint64_t n = l0.shape(0);
     const uint32_t R = static_cast<uint32_t>(l0.shape(1));
     if (!levels.is_none()) {
-      auto lv = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(levels);
-      auto off = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>(upper_off);
-      auto ue = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(upper_edges);
+      auto lv = U32Array(levels);
+      auto off = CArray<uint64_t>(upper_off);
+      auto ue = U32Array(upper_edges);
       check(alaya_graph_import(n, R, l0.data(), lv.data(), off.data(), ue.data(), ue.size(), upper_R, ep,
                                nullptr, 0, &g));
     } else {
-      auto e = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(eps);
+      auto e = U32Array(eps);
       check(alaya_graph_import(n, R, l0.data(), nullptr, nullptr, nullptr, 0, 0, 0, e.data(),
                                static_cast<uint32_t>(e.size()), &g));
     }
@@ -867,21 +840,7 @@ class Graph {
   void save(const std::string &path, int id_bytes, uint64_t capacity) const {
     check(alaya_graph_save(g_, path.c_str(), id_bytes, capacity, nullptr));
   }
-  py::tuple arrays() const {
-    uint64_t n, nue;
-    uint32_t R, upper_R, ep, max_level, n_eps;
-    int has_overlay;
-    check(alaya_graph_info(g_, &n, &R, &has_overlay, &upper_R, &ep, &max_level, &nue, &n_eps));
-    py::array_t<uint32_t> l0({static_cast<py::ssize_t>(n), static_cast<py::ssize_t>(R)});
-    py::array_t<uint32_t> levels(static_cast<py::ssize_t>(has_overlay ? n : 0));
-    py::array_t<uint64_t> off(static_cast<py::ssize_t>(has_overlay ? n : 0));
-    py::array_t<uint32_t> ue(static_cast<py::ssize_t>(nue));
-    py::array_t<uint32_t> eps(static_cast<py::ssize_t>(n_eps));
-    check(alaya_graph_export(g_, l0.mutable_data(), levels.mutable_data(), off.mutable_data(),
-                             ue.mutable_data(), eps.mutable_data()));
-    return py::make_tuple(l0, has_overlay ? py::object(levels) : py::none(),
-                          has_overlay ? py::object(off) : py::none(), ue, ep, upper_R, eps);
-  }
+  py::tuple arrays() const { return graph_arrays_of(g_); }
   alaya_graph *get() const { return g_; }
 
  private:
@@ -897,12 +856,11 @@ class DeviceIndex : public LaunchControls {
   }
   DeviceIndex(const DeviceIndex &) = delete;
   DeviceIndex &operator=(const DeviceIndex &) = delete;
-  void set_base(py::array_t<float, py::array::c_style | py::array::forcecast> rows, int metric,
-                py::object valid) {
+  void set_base(F32Array rows, int metric, py::object valid) {
     const uint8_t *vp = nullptr;
-    py::array_t<uint8_t, py::array::c_style | py::array::forcecast> v;
+    U8Array v;
     if (!valid.is_none()) {
-      v = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>(valid);
+      v = U8Array(valid);
       vp = v.data();
     }
     const float *ptr = rows.data();
@@ -932,206 +890,142 @@ class DeviceIndex : public LaunchControls {
     stats["max_level"] = st[7];
     return py::make_tuple(std::make_shared<Graph>(g), stats);
   }
-  py::tuple search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef) {
+  py::tuple search(F32Array q, uint32_t k, uint32_t ef) {
     const uint64_t nq = q.shape(0);
-    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<uint32_t> c({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(4)});
+    Results r(nq, k);
     const float *qp = q.data();
-    uint32_t *ip = ids.mutable_data();
-    float *dp = d.mutable_data();
-    uint32_t *cp = c.mutable_data();
     {
       py::gil_scoped_release nogil;
-      check(alaya_index_batch_search(ix_, qp, nq, k, ef, ip, dp, cp));
+      check(alaya_index_batch_search(ix_, qp, nq, k, ef, r.ip, r.dp, r.cp));
     }
-    return py::make_tuple(ids, d, c);
+    return py::make_tuple(r.ids, r.d, r.c);
   }
   void search_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t ids, uintptr_t dists,
                      uintptr_t counters, uintptr_t stream) {
-    check(alaya_index_batch_search_device(ix_, reinterpret_cast<const float *>(q), nq, k, ef,
-                                          reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                          reinterpret_cast<uint32_t *>(counters), reinterpret_cast<void *>(stream)));
+    check(alaya_index_batch_search_device(ix_, dptr<const float>(q), nq, k, ef, dptr<uint32_t>(ids), dptr<float>(dists),
+                                          dptr<uint32_t>(counters), dptr<void>(stream)));
   }
   // the k nearest rows among those allow_words (uint32 [n_masks, ceil(n / 32)], utils.pack_allow) allows;
   // mask_of_query: each query's mask, or None with one mask
-  py::tuple filtered_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
-                            py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
-                            py::object mask_of_query) {
+  py::tuple filtered_search(F32Array q, uint32_t k, uint32_t ef, U32Array allow_words, py::object mask_of_query) {
     return filtered_search_call(q, k, ef, allow_words, mask_of_query, false);
   }
   // the same under the traversal that steps through disallowed neighbours (alaya_index_filtered_search_hop):
   // (ids, dists, counters[nq, 4], n_through[nq])
-  py::tuple filtered_search_hop(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
-                                py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
-                                py::object mask_of_query) {
+  py::tuple filtered_search_hop(F32Array q, uint32_t k, uint32_t ef, U32Array allow_words, py::object mask_of_query) {
     return filtered_search_call(q, k, ef, allow_words, mask_of_query, true);
   }
-  py::tuple filtered_search_call(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
-                                 py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
-                                 py::object mask_of_query, bool hop) {
+  py::tuple filtered_search_call(F32Array q, uint32_t k, uint32_t ef, U32Array allow_words, py::object mask_of_query,
+                                 bool hop) {
     const uint64_t nq = q.shape(0);
-    uint64_t n = 0;
-    check(alaya_index_info(ix_, &n, nullptr, nullptr, nullptr, nullptr));
-    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n + 31) / 32 || allow_words.shape(0) < 1)
-      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
-    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
-    const uint32_t *gp = nullptr;
-    if (!mask_of_query.is_none()) {
-      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
-      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
-        throw py::value_error("mask_of_query must hold one index per query");
-      gp = groups.data();
-    }
-    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<uint32_t> c({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(4)});
+    const Masks m = parse_masks(allow_words, mask_of_query, rows(), nq);
+    Results r(nq, k);
     const float *qp = q.data();
-    const uint32_t *ap = allow_words.data();
-    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
-    uint32_t *ip = ids.mutable_data();
-    float *dp = d.mutable_data();
-    uint32_t *cp = c.mutable_data();
     if (hop) {
       py::array_t<uint32_t> t(static_cast<py::ssize_t>(nq));
       uint32_t *tp = t.mutable_data();
       {
         py::gil_scoped_release nogil;
-        check(alaya_index_filtered_search_hop(ix_, qp, nq, k, ef, ap, n_masks, gp, ip, dp, cp, tp));
+        check(alaya_index_filtered_search_hop(ix_, qp, nq, k, ef, m.words, m.n_masks, m.of_query, r.ip, r.dp, r.cp, tp));
       }
-      return py::make_tuple(ids, d, c, t);
+      return py::make_tuple(r.ids, r.d, r.c, t);
     }
     {
       py::gil_scoped_release nogil;
-      check(alaya_index_filtered_search(ix_, qp, nq, k, ef, ap, n_masks, gp, ip, dp, cp));
+      check(alaya_index_filtered_search(ix_, qp, nq, k, ef, m.words, m.n_masks, m.of_query, r.ip, r.dp, r.cp));
     }
-    return py::make_tuple(ids, d, c);
+    return py::make_tuple(r.ids, r.d, r.c);
   }
   void filtered_search_hop_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t allow_words, uint32_t n_masks,
                                   uintptr_t mask_of_query, uintptr_t ids, uintptr_t dists, uintptr_t counters,
                                   uintptr_t n_through, uintptr_t stream) {
-    check(alaya_index_filtered_search_hop_device(ix_, reinterpret_cast<const float *>(q), nq, k, ef,
-                                                 reinterpret_cast<const uint32_t *>(allow_words), n_masks,
-                                                 reinterpret_cast<const uint32_t *>(mask_of_query),
-                                                 reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                                 reinterpret_cast<uint32_t *>(counters),
-                                                 reinterpret_cast<uint32_t *>(n_through), reinterpret_cast<void *>(stream)));
+    check(alaya_index_filtered_search_hop_device(ix_, dptr<const float>(q), nq, k, ef, dptr<const uint32_t>(allow_words),
+                                                 n_masks, dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(ids),
+                                                 dptr<float>(dists), dptr<uint32_t>(counters), dptr<uint32_t>(n_through),
+                                                 dptr<void>(stream)));
   }
   void filtered_search_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t allow_words, uint32_t n_masks,
                               uintptr_t mask_of_query, uintptr_t ids, uintptr_t dists, uintptr_t counters,
                               uintptr_t stream) {
-    check(alaya_index_filtered_search_device(ix_, reinterpret_cast<const float *>(q), nq, k, ef,
-                                             reinterpret_cast<const uint32_t *>(allow_words), n_masks,
-                                             reinterpret_cast<const uint32_t *>(mask_of_query),
-                                             reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                             reinterpret_cast<uint32_t *>(counters), reinterpret_cast<void *>(stream)));
+    check(alaya_index_filtered_search_device(ix_, dptr<const float>(q), nq, k, ef, dptr<const uint32_t>(allow_words),
+                                             n_masks, dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(ids),
+                                             dptr<float>(dists), dptr<uint32_t>(counters), dptr<void>(stream)));
   }
   // the same over the index's SQ8 codes, reranked on the f32 rows (alaya_index_filtered_search_sq8); pool: the
   // candidate pool's capacity, 0 = min(224, max(k, ef)); rerank_queries: None = queries
-  py::tuple filtered_search_sq8(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k, uint32_t ef,
-                                py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
-                                py::object mask_of_query, uint32_t pool, py::object rerank_queries) {
+  py::tuple filtered_search_sq8(F32Array q, uint32_t k, uint32_t ef, U32Array allow_words, py::object mask_of_query,
+                                uint32_t pool, py::object rerank_queries) {
     const uint64_t nq = q.shape(0);
-    uint64_t n = 0;
-    check(alaya_index_info(ix_, &n, nullptr, nullptr, nullptr, nullptr));
-    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n + 31) / 32 || allow_words.shape(0) < 1)
-      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
-    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
-    const uint32_t *gp = nullptr;
-    if (!mask_of_query.is_none()) {
-      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
-      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
-        throw py::value_error("mask_of_query must hold one index per query");
-      gp = groups.data();
-    }
-    py::array_t<float, py::array::c_style | py::array::forcecast> rq;
+    const Masks m = parse_masks(allow_words, mask_of_query, rows(), nq);
+    F32Array rq;
     const float *rqp = nullptr;
     if (!rerank_queries.is_none()) {
-      rq = py::array_t<float, py::array::c_style | py::array::forcecast>(rerank_queries);
+      rq = F32Array(rerank_queries);
       if (rq.ndim() != 2 || rq.shape(0) != q.shape(0) || rq.shape(1) != q.shape(1))
         throw py::value_error("rerank_queries must have the queries' shape");
       rqp = rq.data();
     }
-    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<uint32_t> c({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(4)});
+    Results r(nq, k);
     const float *qp = q.data();
-    const uint32_t *ap = allow_words.data();
-    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
-    uint32_t *ip = ids.mutable_data();
-    float *dp = d.mutable_data();
-    uint32_t *cp = c.mutable_data();
     {
       py::gil_scoped_release nogil;
-      check(alaya_index_filtered_search_sq8(ix_, qp, rqp, nq, k, ef, pool, ap, n_masks, gp, ip, dp, cp));
+      check(alaya_index_filtered_search_sq8(ix_, qp, rqp, nq, k, ef, pool, m.words, m.n_masks, m.of_query, r.ip, r.dp,
+                                            r.cp));
     }
-    return py::make_tuple(ids, d, c);
+    return py::make_tuple(r.ids, r.d, r.c);
   }
   void filtered_search_sq8_device(uintptr_t q, uintptr_t rq, uint64_t nq, uint32_t k, uint32_t ef, uint32_t pool,
                                   uintptr_t allow_words, uint32_t n_masks, uintptr_t mask_of_query, uintptr_t ids,
                                   uintptr_t dists, uintptr_t counters, uintptr_t stream) {
-    check(alaya_index_filtered_search_sq8_device(ix_, reinterpret_cast<const float *>(q), reinterpret_cast<const float *>(rq),
-                                                 nq, k, ef, pool, reinterpret_cast<const uint32_t *>(allow_words), n_masks,
-                                                 reinterpret_cast<const uint32_t *>(mask_of_query),
-                                                 reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                                 reinterpret_cast<uint32_t *>(counters), reinterpret_cast<void *>(stream)));
+    check(alaya_index_filtered_search_sq8_device(ix_, dptr<const float>(q), dptr<const float>(rq), nq, k, ef, pool,
+                                                 dptr<const uint32_t>(allow_words), n_masks,
+                                                 dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(ids),
+                                                 dptr<float>(dists), dptr<uint32_t>(counters), dptr<void>(stream)));
   }
   void shard_search_device(uintptr_t q, uint64_t nq, uint32_t k, uint32_t ef, uintptr_t ids, uintptr_t dists,
                            uintptr_t counters, uintptr_t stream) {
-    check(alaya_index_shard_search_device(ix_, reinterpret_cast<const float *>(q), nq, k, ef,
-                                          reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                          reinterpret_cast<uint32_t *>(counters), reinterpret_cast<void *>(stream)));
+    check(alaya_index_shard_search_device(ix_, dptr<const float>(q), nq, k, ef, dptr<uint32_t>(ids), dptr<float>(dists),
+                                          dptr<uint32_t>(counters), dptr<void>(stream)));
   }
-  py::array distances(py::array_t<float, py::array::c_style | py::array::forcecast> q,
-                      py::array_t<uint32_t, py::array::c_style | py::array::forcecast> ids) {
+  py::array distances(F32Array q, U32Array ids) {
     const uint64_t nq = q.shape(0);
     const uint32_t n = static_cast<uint32_t>(ids.size());
-    py::array_t<float> out({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(n)});
+    py::array_t<float> out = out2d<float>(nq, n);
     check(alaya_index_distances(ix_, q.data(), nq, ids.data(), n, out.mutable_data()));
     return out;
   }
-  void set_sq8(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> codes,
-               py::array_t<float, py::array::c_style | py::array::forcecast> mn,
-               py::array_t<float, py::array::c_style | py::array::forcecast> mx, int order) {
+  void set_sq8(U8Array codes, F32Array mn, F32Array mx, int order) {
     check(alaya_index_set_sq8(ix_, codes.data(), codes.shape(0), static_cast<uint32_t>(codes.shape(1)),
                               mn.data(), mx.data(), order));
   }
-  py::tuple search_sq8(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k,
-                       uint32_t ef, int rerank, py::object rerank_queries) {
+  py::tuple search_sq8(F32Array q, uint32_t k, uint32_t ef, int rerank, py::object rerank_queries) {
     const uint64_t nq = q.shape(0);
-    py::array_t<float, py::array::c_style | py::array::forcecast> rq;
+    F32Array rq;
     const float *rqp = nullptr;
     if (!rerank_queries.is_none()) {
-      rq = py::array_t<float, py::array::c_style | py::array::forcecast>(rerank_queries);
+      rq = F32Array(rerank_queries);
       rqp = rq.data();
     }
-    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<uint32_t> c({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(4)});
-    check(alaya_index_batch_search_sq8(ix_, q.data(), rqp, nq, k, ef, rerank, ids.mutable_data(),
-                                       d.mutable_data(), c.mutable_data()));
-    return py::make_tuple(ids, d, c);
+    Results r(nq, k);
+    check(alaya_index_batch_search_sq8(ix_, q.data(), rqp, nq, k, ef, rerank, r.ip, r.dp, r.cp));
+    return py::make_tuple(r.ids, r.d, r.c);
   }
   void search_sq8_device(uintptr_t q, uintptr_t rq, uint64_t nq, uint32_t k, uint32_t ef, int rerank,
                          uintptr_t ids, uintptr_t dists, uintptr_t counters, uintptr_t stream) {
-    check(alaya_index_batch_search_sq8_device(ix_, reinterpret_cast<const float *>(q),
-                                              reinterpret_cast<const float *>(rq), nq, k, ef, rerank,
-                                              reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                              reinterpret_cast<uint32_t *>(counters),
-                                              reinterpret_cast<void *>(stream)));
+    check(alaya_index_batch_search_sq8_device(ix_, dptr<const float>(q), dptr<const float>(rq), nq, k, ef, rerank,
+                                              dptr<uint32_t>(ids), dptr<float>(dists), dptr<uint32_t>(counters),
+                                              dptr<void>(stream)));
   }
   void shard_search_sq8_device(uintptr_t q, uintptr_t rq, uint64_t nq, uint32_t k, uint32_t ef, bool holds_row0,
                                uintptr_t ids, uintptr_t dists, uintptr_t counters, uintptr_t stream) {
-    check(alaya_index_shard_search_sq8_device(ix_, reinterpret_cast<const float *>(q),
-                                              reinterpret_cast<const float *>(rq), nq, k, ef, holds_row0 ? 1 : 0,
-                                              reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                              reinterpret_cast<uint32_t *>(counters),
-                                              reinterpret_cast<void *>(stream)));
+    check(alaya_index_shard_search_sq8_device(ix_, dptr<const float>(q), dptr<const float>(rq), nq, k, ef,
+                                              holds_row0 ? 1 : 0, dptr<uint32_t>(ids), dptr<float>(dists),
+                                              dptr<uint32_t>(counters), dptr<void>(stream)));
   }
-  py::tuple flat_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k) {
+  py::tuple flat_search(F32Array q, uint32_t k) {
     const uint64_t nq = q.shape(0);
-    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
+    py::array_t<uint32_t> ids = out2d<uint32_t>(nq, k);
+    py::array_t<float> d = out2d<float>(nq, k);
     uint32_t redo = 0;
     const float *qp = q.data();
     uint32_t *ip = ids.mutable_data();
@@ -1144,48 +1038,30 @@ class DeviceIndex : public LaunchControls {
   }
   void flat_search_device(uintptr_t q, uint64_t nq, uint32_t k, uintptr_t ids, uintptr_t dists,
                           uintptr_t flags, uintptr_t stream) {
-    check(alaya_index_flat_search_device(ix_, reinterpret_cast<const float *>(q), nq, k,
-                                         reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                         reinterpret_cast<uint32_t *>(flags), reinterpret_cast<void *>(stream)));
+    check(alaya_index_flat_search_device(ix_, dptr<const float>(q), nq, k, dptr<uint32_t>(ids), dptr<float>(dists),
+                                         dptr<uint32_t>(flags), dptr<void>(stream)));
   }
   // the exact k nearest among the valid rows allow_words (uint32 [n_masks, ceil(n / 32)], utils.pack_allow)
   // allows: a scan of those rows (alaya_index_flat_search_filtered); mask_of_query as for filtered_search
-  py::tuple flat_search_filtered(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k,
-                                 py::array_t<uint32_t, py::array::c_style | py::array::forcecast> allow_words,
-                                 py::object mask_of_query) {
+  py::tuple flat_search_filtered(F32Array q, uint32_t k, U32Array allow_words, py::object mask_of_query) {
     const uint64_t nq = q.shape(0);
-    uint64_t n = 0;
-    check(alaya_index_info(ix_, &n, nullptr, nullptr, nullptr, nullptr));
-    if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n + 31) / 32 || allow_words.shape(0) < 1)
-      throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
-    py::array_t<uint32_t, py::array::c_style | py::array::forcecast> groups;
-    const uint32_t *gp = nullptr;
-    if (!mask_of_query.is_none()) {
-      groups = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>(mask_of_query);
-      if (groups.ndim() != 1 || static_cast<uint64_t>(groups.shape(0)) != nq)
-        throw py::value_error("mask_of_query must hold one index per query");
-      gp = groups.data();
-    }
-    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<float> d({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
+    const Masks m = parse_masks(allow_words, mask_of_query, rows(), nq);
+    py::array_t<uint32_t> ids = out2d<uint32_t>(nq, k);
+    py::array_t<float> d = out2d<float>(nq, k);
     const float *qp = q.data();
-    const uint32_t *ap = allow_words.data();
-    const uint32_t n_masks = static_cast<uint32_t>(allow_words.shape(0));
     uint32_t *ip = ids.mutable_data();
     float *dp = d.mutable_data();
     {
       py::gil_scoped_release nogil;
-      check(alaya_index_flat_search_filtered(ix_, qp, nq, k, ap, n_masks, gp, ip, dp));
+      check(alaya_index_flat_search_filtered(ix_, qp, nq, k, m.words, m.n_masks, m.of_query, ip, dp));
     }
     return py::make_tuple(ids, d);
   }
   void flat_search_filtered_device(uintptr_t q, uint64_t nq, uint32_t k, uintptr_t allow_words, uint32_t n_masks,
                                    uintptr_t mask_of_query, uintptr_t ids, uintptr_t dists, uintptr_t stream) {
-    check(alaya_index_flat_search_filtered_device(ix_, reinterpret_cast<const float *>(q), nq, k,
-                                                  reinterpret_cast<const uint32_t *>(allow_words), n_masks,
-                                                  reinterpret_cast<const uint32_t *>(mask_of_query),
-                                                  reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                                  reinterpret_cast<void *>(stream)));
+    check(alaya_index_flat_search_filtered_device(ix_, dptr<const float>(q), nq, k, dptr<const uint32_t>(allow_words),
+                                                  n_masks, dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(ids),
+                                                  dptr<float>(dists), dptr<void>(stream)));
   }
   // (allowed valid rows over the masks, row chunks of the last scan, its query tile, scan launches)
   py::tuple flat_filtered_last() const {
@@ -1200,17 +1076,14 @@ class DeviceIndex : public LaunchControls {
   }
   void flat_diag(uintptr_t q, uint64_t nq, uint32_t k, int ablate, uintptr_t ids, uintptr_t dists,
                  uintptr_t flags, uintptr_t mc, uintptr_t stream) {
-    check(alaya_index_flat_diag(ix_, reinterpret_cast<const float *>(q), nq, k, ablate,
-                                reinterpret_cast<uint32_t *>(ids), reinterpret_cast<float *>(dists),
-                                reinterpret_cast<uint32_t *>(flags), reinterpret_cast<uint32_t *>(mc),
-                                reinterpret_cast<void *>(stream)));
+    check(alaya_index_flat_diag(ix_, dptr<const float>(q), nq, k, ablate, dptr<uint32_t>(ids), dptr<float>(dists),
+                                dptr<uint32_t>(flags), dptr<uint32_t>(mc), dptr<void>(stream)));
   }
-  py::tuple profile_search(py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t k,
-                           uint32_t ef, int space) {
+  py::tuple profile_search(F32Array q, uint32_t k, uint32_t ef, int space) {
     const uint64_t nq = q.shape(0);
-    py::array_t<uint32_t> ids({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(k)});
-    py::array_t<uint32_t> c({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(4)});
-    py::array_t<uint64_t> st({static_cast<py::ssize_t>(nq), static_cast<py::ssize_t>(8)});
+    py::array_t<uint32_t> ids = out2d<uint32_t>(nq, k);
+    py::array_t<uint32_t> c = out2d<uint32_t>(nq, 4);
+    py::array_t<uint64_t> st = out2d<uint64_t>(nq, 8);
     check(alaya_index_profile_search(ix_, q.data(), nq, k, ef, space, ids.mutable_data(), c.mutable_data(),
                                      st.mutable_data()));
     return py::make_tuple(ids, c, st);
@@ -1222,6 +1095,24 @@ class DeviceIndex : public LaunchControls {
   }
 
  private:
+  // the (nq, k) ids and distances and the (nq, 4) counters of a search, with their data pointers (taken
+  // while the GIL is held)
+  struct Results {
+    py::array_t<uint32_t> ids;
+    py::array_t<float> d;
+    py::array_t<uint32_t> c;
+    uint32_t *ip;
+    float *dp;
+    uint32_t *cp;
+    Results(uint64_t nq, uint32_t k)
+        : ids(out2d<uint32_t>(nq, k)), d(out2d<float>(nq, k)), c(out2d<uint32_t>(nq, 4)), ip(ids.mutable_data()),
+          dp(d.mutable_data()), cp(c.mutable_data()) {}
+  };
+  uint64_t rows() const {  // the rows the masks of a filtered call cover
+    uint64_t n = 0;
+    check(alaya_index_info(ix_, &n, nullptr, nullptr, nullptr, nullptr));
+    return n;
+  }
 };
 
 }  // namespace alaya_py
@@ -1368,15 +1259,13 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("profile_search", &DeviceIndex::profile_search, py::arg("q"), py::arg("k"), py::arg("ef"),
            py::arg("space") = 0)
       .def("device_bytes", &DeviceIndex::device_bytes);
-  m.def("sq8_train", [](py::array_t<float, py::array::c_style | py::array::forcecast> data) {
+  m.def("sq8_train", [](F32Array data) {
     const uint32_t d = static_cast<uint32_t>(data.shape(1));
     py::array_t<float> mn(d), mx(d);
     check(alaya_sq8_train(data.data(), data.shape(0), d, mn.mutable_data(), mx.mutable_data()));
     return py::make_tuple(mn, mx);
   });
-  m.def("sq8_encode", [](py::array_t<float, py::array::c_style | py::array::forcecast> data,
-                         py::array_t<float, py::array::c_style | py::array::forcecast> mn,
-                         py::array_t<float, py::array::c_style | py::array::forcecast> mx, uint32_t threads) {
+  m.def("sq8_encode", [](F32Array data, F32Array mn, F32Array mx, uint32_t threads) {
     py::array_t<uint8_t> codes({data.shape(0), data.shape(1)});
     check(alaya_sq8_encode(data.data(), data.shape(0), static_cast<uint32_t>(data.shape(1)), mn.data(), mx.data(),
                            codes.mutable_data(), threads));
@@ -1384,8 +1273,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
   }, py::arg("data"), py::arg("min"), py::arg("max"), py::arg("num_threads") = 1u);
   m.def("host_sq8_order", &host_sq8_order);
   m.def("build_info", [] { return std::string(alaya_build_info()); });
-  m.def("screen_lower_bound", [](py::array_t<float, py::array::c_style | py::array::forcecast> d_tilde,
-                                 py::array_t<float, py::array::c_style | py::array::forcecast> e_row, uint32_t dim) {
+  m.def("screen_lower_bound", [](F32Array d_tilde, F32Array e_row, uint32_t dim) {
     if (d_tilde.size() != e_row.size()) throw std::invalid_argument("d_tilde and e_row differ in size");
     py::array_t<float> out(d_tilde.size());
     check(alaya_screen_lower_bound(d_tilde.data(), e_row.data(), static_cast<uint64_t>(d_tilde.size()), dim,
@@ -1393,7 +1281,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
     return out;
   });
   // the 8-bit screening copy on the host: (codes, header (e_row, lo, scale, 0), values the codes stand for)
-  m.def("screen_u8_quantize", [](py::array_t<float, py::array::c_style | py::array::forcecast> rows) {
+  m.def("screen_u8_quantize", [](F32Array rows) {
     if (rows.ndim() != 2) throw std::invalid_argument("rows must be 2-D");
     py::array_t<uint8_t> codes({rows.shape(0), rows.shape(1)});
     py::array_t<float> header({rows.shape(0), static_cast<py::ssize_t>(4)});
@@ -1404,8 +1292,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
   });
   // the integer screen's bound on the host, pair i = (queries[i], rows[i]): (d_in <= ||q^ - y^||^2,
   // e_sum >= ||x - y^|| + ||q - q^||, the bound, sums (n x 5: A1, A2, C1, C2, AC))
-  m.def("screen_int_bound", [](py::array_t<float, py::array::c_style | py::array::forcecast> queries,
-                               py::array_t<float, py::array::c_style | py::array::forcecast> rows) {
+  m.def("screen_int_bound", [](F32Array queries, F32Array rows) {
     if (rows.ndim() != 2 || queries.ndim() != 2 || rows.shape(0) != queries.shape(0) || rows.shape(1) != queries.shape(1))
       throw std::invalid_argument("queries and rows must be 2-D of one shape");
     py::array_t<float> d_in(rows.shape(0)), e_sum(rows.shape(0)), bound(rows.shape(0));
@@ -1423,9 +1310,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
     return py::make_tuple(o[0], o[1], o[2], o[3], o[4]);
   }, py::arg("n_allowed"), py::arg("nq"), py::arg("k"), py::arg("stride"), py::arg("cus"));
   // the flat search's inner-product bound on the host (flat_bound.h): slack per query, and the test
-  m.def("flat_ip_slack", [](int contraction, uint32_t k_acc,
-                            py::array_t<float, py::array::c_style | py::array::forcecast> q_norm2,
-                            py::array_t<int, py::array::c_style | py::array::forcecast> q_exp, float b_max, int base_exp) {
+  m.def("flat_ip_slack", [](int contraction, uint32_t k_acc, F32Array q_norm2, CArray<int> q_exp, float b_max,
+                            int base_exp) {
     if (q_exp.size() != 0 && q_exp.size() != q_norm2.size()) throw std::invalid_argument("q_norm2 and q_exp differ in size");
     py::array_t<float> out(q_norm2.size());
     check(alaya_flat_ip_slack(contraction, k_acc, q_norm2.data(), q_exp.size() ? q_exp.data() : nullptr,
@@ -1433,9 +1319,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
     return out;
   }, py::arg("contraction"), py::arg("k_acc"), py::arg("q_norm2"), py::arg("q_exp"), py::arg("b_max"),
      py::arg("base_exp") = 0);
-  m.def("flat_ip_proven", [](py::array_t<float, py::array::c_style | py::array::forcecast> kth_d,
-                             py::array_t<float, py::array::c_style | py::array::forcecast> cutoff,
-                             py::array_t<float, py::array::c_style | py::array::forcecast> slack) {
+  m.def("flat_ip_proven", [](F32Array kth_d, F32Array cutoff, F32Array slack) {
     if (kth_d.size() != cutoff.size() || kth_d.size() != slack.size()) throw std::invalid_argument("sizes differ");
     py::array_t<uint8_t> out(kth_d.size());
     check(alaya_flat_ip_proven(kth_d.data(), cutoff.data(), slack.data(), static_cast<uint64_t>(kth_d.size()),
@@ -1443,7 +1327,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
     return out;
   }, py::arg("kth_d"), py::arg("cutoff"), py::arg("slack"));
   // a float32 copy with each row normalised as fit does for COS (alaya_amd::normalize_row)
-  m.def("normalize_rows", [](py::array_t<float, py::array::c_style | py::array::forcecast> a) {
+  m.def("normalize_rows", [](F32Array a) {
     if (a.ndim() != 2) throw std::invalid_argument("normalize_rows needs a 2D array");
     py::array_t<float> out({a.shape(0), a.shape(1)});
     if (a.size()) std::memcpy(out.mutable_data(), a.data(), static_cast<size_t>(a.size()) * 4);
@@ -1486,5 +1370,5 @@ PYBIND11_MODULE(_alayalitepy, m) {
     check(alaya_stream_create_reserving(device, reserved_cus, &s));
     return reinterpret_cast<uintptr_t>(s);
   }, py::arg("device"), py::arg("reserved_cus"));
-  m.def("stream_destroy", [](uintptr_t s) { check(alaya_stream_destroy(reinterpret_cast<void *>(s))); });
+  m.def("stream_destroy", [](uintptr_t s) { check(alaya_stream_destroy(dptr<void>(s))); });
 }
