@@ -52,8 +52,12 @@ struct BuildParams {
 size_t build_lds_bytes(uint32_t stride, uint32_t ef, uint32_t hash_log2, bool compact);
 hipError_t build_search_occupancy(const BuildParams &p, size_t lds, int *blocks_per_cu);
 hipError_t launch_build_search(const BuildParams &p, int grid, size_t lds, hipStream_t stream);
-hipError_t launch_build_select(const BuildParams &p, int grid, hipStream_t stream);
-hipError_t launch_build_apply(const BuildParams &p, int grid, hipStream_t stream);
+// tombstones: s.valid has cleared bits (an extension of an index with removed rows); the candidates
+// whose bit is clear are dropped before the selection.  cand_ids / cand_d are compacted in place.
+hipError_t launch_build_select(const BuildParams &p, int grid, hipStream_t stream, bool tombstones = false);
+// duplicates: adjacency rows may repeat an id (rows the update job rewrote); the prune's sort then
+// orders equal entries by position.
+hipError_t launch_build_apply(const BuildParams &p, int grid, hipStream_t stream, bool duplicates = false);
 // Radix sort of (key, dist) pairs, keys ascending.  tmp == nullptr: *tmp_bytes = scratch needed.
 hipError_t sort_edges(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out,
                       const float *d_in, float *d_out, uint64_t n, hipStream_t stream);

@@ -231,6 +231,30 @@ __global__ void __launch_bounds__(64) build_search_kernel(BuildParams bp) {
 // ---------------------------------------------------------------------------------------------
 // 2. neighbour selection for the new points + reverse edges
 // ---------------------------------------------------------------------------------------------
+// Drop the candidates whose validity bit is clear from a pool (ascending distance, global memory),
+// in place and in order; returns how many stay.  A slot is written at or below the slot it was
+// read from, by the wave that read it, so no chunk reads what an earlier one wrote.
+__device__ __forceinline__ uint32_t drop_removed(const uint32_t *valid, uint32_t *ci, float *cd, uint32_t C) {
+  const int lane = lane_id();
+  uint32_t kept = 0;
+  for (uint32_t b = 0; b < C; b += 64) {
+    const uint32_t i = b + lane;
+    const bool in = i < C;
+    const uint32_t id = in ? ci[i] : 0u;
+    const float d = in ? cd[i] : 0.f;
+    const bool keep = in && ((valid[id >> 5] >> (id & 31)) & 1u);
+    const uint64_t km = ballot(keep);
+    if (keep) {
+      const uint32_t o = kept + __popcll(km & ((1ull << lane) - 1ull));
+      ci[o] = id;
+      cd[o] = d;
+    }
+    kept += __popcll(km);
+  }
+  wave_sync();
+  return kept;
+}
+
 template <bool kIP, int kChunks>
 __global__ void __launch_bounds__(64) build_select_kernel(BuildParams bp) {
   const SearchParams &p = bp.s;
@@ -259,10 +283,46 @@ __global__ void __launch_bounds__(64) build_select_kernel(BuildParams bp) {
   if (bp.counters && lane == 0 && n_dist) atomicAdd(&bp.counters[2], static_cast<unsigned long long>(n_dist));
 }
 
+// The selection on an index with removed rows (SearchParams::valid with cleared bits).  The build
+// search measured them as FLT_MAX, as a query does; they leave the pool here, before the heuristic
+// and before its "fewer than M: keep all" path, so a new point neither links to a removed row nor
+// sends it a reverse edge, and next[] is never one.  A kernel of its own, the rest a copy of
+// build_select_kernel's body: the plain kernel's generated code stays the pinned build's.
+template <bool kIP, int kChunks>
+__global__ void __launch_bounds__(64) build_select_tomb_kernel(BuildParams bp) {
+  const SearchParams &p = bp.s;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t *sel_i = reinterpret_cast<uint32_t *>(smem);
+  float *sel_d = reinterpret_cast<float *>(sel_i + 64);
+  float *tmp = sel_d + 64;
+  const int lane = lane_id();
+  const uint32_t W = level_width(p, bp.level);
+  uint32_t n_dist = 0;
+  for (uint64_t qi = blockIdx.x; qi < p.nq; qi += gridDim.x) {
+    const uint32_t pt = bp.pts[qi];
+    const uint32_t C = drop_removed(p.valid, bp.cand_ids + qi * p.ef, bp.cand_d + qi * p.ef, bp.cand_n[qi]);
+    const uint32_t nsel = heuristic<kIP, kChunks>(p, bp.cand_ids + qi * p.ef, bp.cand_d + qi * p.ef, C, bp.M,
+                                                  sel_i, sel_d, tmp, &n_dist);
+    // own list in the max-heap pop order: farthest first (hnswlib.hpp:527-551)
+    uint32_t *row = adj_row_w(bp, pt, bp.level);
+    for (uint32_t j = lane; j < W; j += 64) row[j] = j < nsel ? sel_i[nsel - 1 - j] : kEmpty;
+    if (lane == 0) bp.next[pt - bp.batch_first] = nsel ? sel_i[0] : p.ep;
+    for (uint32_t j = lane; j < bp.M; j += 64) {
+      bp.edge_keys[qi * bp.M + j] = j < nsel ? (static_cast<uint64_t>(sel_i[j]) << 32) | pt : kNoEdge;
+      bp.edge_d[qi * bp.M + j] = j < nsel ? sel_d[j] : 0.f;
+    }
+    wave_sync();
+  }
+  if (bp.counters && lane == 0 && n_dist) atomicAdd(&bp.counters[2], static_cast<unsigned long long>(n_dist));
+}
+
 // ---------------------------------------------------------------------------------------------
 // 3. reverse edges: one wave per destination segment of the sorted edge list
 // ---------------------------------------------------------------------------------------------
-template <bool kIP, int kChunks>
+// kDup: rows may repeat an id (the zero padding and the repeats the update job writes, alaya_index's
+// dedup flag).  The rank sort's ties then fall to the row position, so every entry still gets a slot
+// of its own; the heuristic drops a repeat (it is at distance 0 from its kept copy).
+template <bool kIP, int kChunks, bool kDup = false>
 __device__ void apply_segment(const BuildParams &bp, uint64_t s, unsigned char *smem, uint32_t *n_dist,
                               uint32_t *n_prune, uint32_t *n_append) {
   const SearchParams &p = bp.s;
@@ -327,7 +387,11 @@ __device__ void apply_segment(const BuildParams &bp, uint64_t s, unsigned char *
       uint32_t r = 0;
       for (uint32_t k = 0; k < c; ++k) {
         const float dk = ld[k];
-        r += (dk < dj || (dk == dj && li[k] < ij)) ? 1u : 0u;
+        if constexpr (kDup) {
+          r += (dk < dj || (dk == dj && (li[k] < ij || (li[k] == ij && k < j)))) ? 1u : 0u;
+        } else {
+          r += (dk < dj || (dk == dj && li[k] < ij)) ? 1u : 0u;
+        }
       }
       si[r] = ij;
       sdd[r] = dj;
@@ -377,6 +441,32 @@ __global__ void __launch_bounds__(64) build_apply_kernel(BuildParams bp) {
   }
 }
 
+// build_apply_kernel over rows that may repeat an id (apply_segment's kDup); a kernel of its own for
+// the same reason as build_select_tomb_kernel.
+template <bool kIP, int kChunks>
+__global__ void __launch_bounds__(64) build_apply_dup_kernel(BuildParams bp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = lane_id();
+  uint32_t n_dist = 0, n_prune = 0, n_append = 0;
+  for (uint64_t b = static_cast<uint64_t>(blockIdx.x) * 64; b < bp.n_edges; b += static_cast<uint64_t>(gridDim.x) * 64) {
+    const uint64_t i = b + lane;
+    const uint64_t key = i < bp.n_edges ? bp.edge_keys[i] : kNoEdge;
+    const uint64_t prev = (i > 0 && i < bp.n_edges) ? bp.edge_keys[i - 1] : kNoEdge;
+    const bool head = key != kNoEdge && (i == 0 || (prev >> 32) != (key >> 32) || prev == kNoEdge);
+    uint64_t heads = ballot(head);
+    while (heads) {
+      const int h = __ffsll(static_cast<unsigned long long>(heads)) - 1;
+      heads &= heads - 1;
+      apply_segment<kIP, kChunks, true>(bp, b + h, smem, &n_dist, &n_prune, &n_append);
+    }
+  }
+  if (bp.counters && lane == 0) {
+    if (n_prune) atomicAdd(&bp.counters[0], static_cast<unsigned long long>(n_prune));
+    if (n_append) atomicAdd(&bp.counters[1], static_cast<unsigned long long>(n_append));
+    if (n_dist) atomicAdd(&bp.counters[2], static_cast<unsigned long long>(n_dist));
+  }
+}
+
 // d = 128 / 768 / 960 specialised (the benchmark shapes), every other d runs the generic kernel
 #define ALAYA_BUILD_CHUNKS(X) X(4) X(24) X(30)
 
@@ -386,14 +476,20 @@ template <bool kIP, int kChunks>
 const void *select_ptr() { return reinterpret_cast<const void *>(&build_select_kernel<kIP, kChunks>); }
 template <bool kIP, int kChunks>
 const void *apply_ptr() { return reinterpret_cast<const void *>(&build_apply_kernel<kIP, kChunks>); }
+template <bool kIP, int kChunks>
+const void *select_tomb_ptr() { return reinterpret_cast<const void *>(&build_select_tomb_kernel<kIP, kChunks>); }
+template <bool kIP, int kChunks>
+const void *apply_dup_ptr() { return reinterpret_cast<const void *>(&build_apply_dup_kernel<kIP, kChunks>); }
 
-enum class Which { kSearch, kSelect, kApply };
+enum class Which { kSearch, kSelect, kApply, kSelectTomb, kApplyDup };
 
 template <int C>
 const void *sym(Which w, bool ip) {
   switch (w) {
     case Which::kSearch: return ip ? search_ptr<true, C>() : search_ptr<false, C>();
     case Which::kSelect: return ip ? select_ptr<true, 0>() : select_ptr<false, 0>();
+    case Which::kSelectTomb: return ip ? select_tomb_ptr<true, 0>() : select_tomb_ptr<false, 0>();
+    case Which::kApplyDup: return ip ? apply_dup_ptr<true, 0>() : apply_dup_ptr<false, 0>();
     default: return ip ? apply_ptr<true, 0>() : apply_ptr<false, 0>();
   }
 }
@@ -433,12 +529,13 @@ hipError_t launch_build_search(const BuildParams &p, int grid, size_t lds, hipSt
   return launch(Which::kSearch, p, grid, lds, stream);
 }
 
-hipError_t launch_build_select(const BuildParams &p, int grid, hipStream_t stream) {
-  return launch(Which::kSelect, p, grid, select_lds(p.s.stride), stream);
+hipError_t launch_build_select(const BuildParams &p, int grid, hipStream_t stream, bool tombstones) {
+  if (tombstones && !p.s.valid) return hipErrorInvalidValue;
+  return launch(tombstones ? Which::kSelectTomb : Which::kSelect, p, grid, select_lds(p.s.stride), stream);
 }
 
-hipError_t launch_build_apply(const BuildParams &p, int grid, hipStream_t stream) {
-  return launch(Which::kApply, p, grid, apply_lds(p.s.stride), stream);
+hipError_t launch_build_apply(const BuildParams &p, int grid, hipStream_t stream, bool duplicates) {
+  return launch(duplicates ? Which::kApplyDup : Which::kApply, p, grid, apply_lds(p.s.stride), stream);
 }
 
 hipError_t sort_edges(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out,

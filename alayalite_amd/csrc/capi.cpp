@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "build_kernels.h"
+#include "extend_kernels.h"
 #include "graph_update.h"
 #include "hnsw_build.h"
 #include "flat_bound.h"
@@ -1766,14 +1767,16 @@ struct BuildStep {
 // Batch schedule (label order): batch size max(1, min(max_batch, inserted / batch_div)); a point
 // whose level exceeds the graph's max level closes its batch, so the entry point / max level a
 // batch sees are exactly the sequential ones (hnswlib.hpp:740-748).
-std::vector<BuildStep> build_schedule(const std::vector<uint32_t> &lv, uint32_t batch_div, uint32_t max_batch,
-                                      uint32_t refine, std::vector<uint32_t> &act, uint32_t *final_ep,
-                                      int *final_max) {
+// The schedule of rows [start, n) of a graph that holds rows [0, start) with entry point `ep` (whose
+// level is the graph's max level): a build from scratch is start = 1, ep = 0.  The batch size
+// depends on the rows inserted so far only, so a schedule continued from one of its own batch
+// boundaries is the rest of the whole schedule.  `ends` (optional) receives every batch's end.
+std::vector<BuildStep> build_schedule(const uint32_t *lv, uint64_t n, uint64_t start, uint32_t ep, uint32_t batch_div,
+                                      uint32_t max_batch, uint32_t refine, std::vector<uint32_t> &act,
+                                      uint32_t *final_ep, int *final_max, std::vector<uint64_t> *ends = nullptr) {
   std::vector<BuildStep> steps;
-  const uint64_t n = lv.size();
-  uint32_t ep = 0;
-  int maxl = n ? static_cast<int>(lv[0]) : 0;
-  uint64_t i = 1;
+  int maxl = n ? static_cast<int>(lv[ep]) : 0;
+  uint64_t i = start;
   while (i < n) {
     const uint64_t b = std::max<uint64_t>(1, std::min<uint64_t>(max_batch, i / batch_div));
     uint64_t end = std::min<uint64_t>(n, i + b);
@@ -1802,11 +1805,159 @@ std::vector<BuildStep> build_schedule(const std::vector<uint32_t> &lv, uint32_t 
       ep = static_cast<uint32_t>(end - 1);
       maxl = static_cast<int>(lv[end - 1]);
     }
+    if (ends) ends->push_back(end);
     i = end;
   }
   *final_ep = ep;
   *final_max = maxl;
   return steps;
+}
+
+// What a run of build steps reports (alaya_index_build_graph's stats, steps of this run only).
+struct BuildRun {
+  uint64_t batches = 0, launches = 0;
+  unsigned long long counters[8] = {0};  // [0] prunes, [1] appends, [2] heuristic distances
+  float ms = 0.f;
+  uint32_t bmax = 1;
+  void write(uint64_t *stats, int max_level) const {
+    if (!stats) return;
+    stats[0] = batches;
+    stats[1] = launches;
+    stats[2] = counters[0];
+    stats[3] = counters[1];
+    stats[4] = counters[2];
+    stats[5] = static_cast<uint64_t>(ms * 1000.0);
+    stats[6] = bmax;
+    stats[7] = static_cast<uint64_t>(max_level);
+  }
+};
+
+// Run `steps` (build_schedule; `act` their active points) on the index's device graph: rows, levels,
+// upper_off and empty adjacency slots of every scheduled point are in HBM, ix->n covers them.
+// tombstones: the validity bitmap has cleared bits -- the searches measure those rows as a query does
+// (FLT_MAX) and the selection drops them (launch_build_select).  duplicates: adjacency rows may
+// repeat an id (launch_build_apply).  `before_sync` queues the caller's downloads behind the steps;
+// the call returns after the stream has drained.
+template <typename F>
+BuildRun run_build_steps(alaya_index *ix, uint32_t R, uint32_t ef, uint32_t max_batch,
+                         const std::vector<BuildStep> &steps, const std::vector<uint32_t> &act, bool tombstones,
+                         bool duplicates, F &&before_sync) {
+  const uint32_t M = R / 2;  // hnsw_builder.hpp:71-72: M = R/2, M0 = R
+  hipStream_t st = ix->stream;
+  BuildRun run;
+  for (const BuildStep &s : steps) run.bmax = std::max(run.bmax, s.cnt);
+  const uint32_t bmax = run.bmax;
+  hipEvent_t e0, e1;
+  hip_check(hipEventCreate(&e0), "event");
+  hip_check(hipEventCreate(&e1), "event");
+  DevBuf d_act, d_next, c_ids, c_d, c_n, k_in, k_out, dd_in, dd_out, sort_tmp, cnt;
+  d_act.reserve(std::max<size_t>(act.size(), 1) * 4);
+  if (!act.empty())
+    hip_check(hipMemcpyAsync(d_act.ptr, act.data(), act.size() * 4, hipMemcpyHostToDevice, st), "H2D");
+  d_next.reserve(static_cast<size_t>(max_batch) * 4);
+  c_ids.reserve(static_cast<size_t>(bmax) * ef * 4);
+  c_d.reserve(static_cast<size_t>(bmax) * ef * 4);
+  c_n.reserve(static_cast<size_t>(bmax) * 4);
+  const size_t n_edge_max = static_cast<size_t>(bmax) * M;
+  k_in.reserve(n_edge_max * 8);
+  k_out.reserve(n_edge_max * 8);
+  dd_in.reserve(n_edge_max * 4);
+  dd_out.reserve(n_edge_max * 4);
+  size_t tmp_bytes = 0;
+  hip_check(alaya_amd::sort_edges(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, n_edge_max, st), "sort size");
+  sort_tmp.reserve(tmp_bytes);
+  cnt.reserve(8 * 8);
+  hip_check(hipMemsetAsync(cnt.ptr, 0, 8 * 8, st), "memset");
+  ix->work.reserve(4);
+
+  alaya_amd::BuildParams bp{};
+  bp.s = base_params(ix);
+  if (!tombstones) bp.s.valid = nullptr;
+  bp.s.l0 = ix->l0.as<uint32_t>();
+  bp.s.R = R;
+  bp.s.levels = ix->levels.as<uint32_t>();
+  bp.s.upper_off = ix->upper_off.as<uint64_t>();
+  bp.s.upper_edges = ix->upper_edges.as<uint32_t>();
+  bp.s.upper_R = R;
+  bp.s.queries = nullptr;
+  bp.s.ef = ef;
+  bp.s.work_counter = ix->work.as<uint32_t>();
+  bp.l0w = ix->l0.as<uint32_t>();
+  bp.upw = ix->upper_edges.as<uint32_t>();
+  bp.next = d_next.as<uint32_t>();
+  bp.cand_ids = c_ids.as<uint32_t>();
+  bp.cand_d = c_d.as<float>();
+  bp.cand_n = c_n.as<uint32_t>();
+  bp.M = M;
+  bp.counters = cnt.as<unsigned long long>();
+  // visited-set sizing and the spill area for the largest batch (sized once: kernels in flight)
+  {
+    SearchParams probe = bp.s;
+    const uint32_t hl = size_visited(ix, probe, alaya_amd::resolve_search_variant({ix->dim, probe.ip, 0, ix->generic, 0}),
+                                     bmax, ef);
+    const size_t lds = alaya_amd::build_lds_bytes(ix->stride, ef, hl, probe.vis_rbits != alaya_amd::kVisWide);
+    bp.s.hash_log2 = hl;
+    bp.s.vis_rbits = probe.vis_rbits;
+    bp.s.vis_lbits = probe.vis_lbits;
+    bp.s.vis_max_disp = probe.vis_max_disp;
+    bp.s.vis_limit = probe.vis_limit;
+    if (lds > kLdsPerCu) throw ArgError("ef_construction / dim too large for the LDS budget");
+  }
+  const size_t lds = alaya_amd::build_lds_bytes(ix->stride, ef, bp.s.hash_log2, bp.s.vis_rbits != alaya_amd::kVisWide);
+  int per_cu = 0;
+  hip_check(alaya_amd::build_search_occupancy(bp, lds, &per_cu), "occupancy");
+  per_cu = std::max(1, per_cu);
+  const uint64_t grid_max = static_cast<uint64_t>(per_cu) * ix->num_cus;
+  prepare_spill(ix, bp.s, std::min<uint64_t>(grid_max, bmax), st);
+
+  hip_check(hipEventRecord(e0, st), "event");
+  for (const BuildStep &s : steps) {
+    bp.s.nq = s.cnt;
+    bp.s.ep = s.ep;
+    bp.pts = d_act.as<uint32_t>() + s.off;
+    bp.batch_first = s.first;
+    bp.level = s.level;
+    bp.max_level = s.max_level;
+    bp.refine = s.refine;
+    bp.Mmax = s.level == 0 ? R : M;
+    bp.edge_keys = k_in.as<uint64_t>();
+    bp.edge_d = dd_in.as<float>();
+    const int grid = static_cast<int>(std::min<uint64_t>(s.cnt, grid_max));
+    const int wide = static_cast<int>(std::min<uint64_t>(s.cnt, static_cast<uint64_t>(ix->num_cus) * 16));
+    hip_check(hipMemsetAsync(bp.s.work_counter, 0, 4, st), "memset");
+    hip_check(alaya_amd::launch_build_search(bp, grid, lds, st), "build search");
+    hip_check(alaya_amd::launch_build_select(bp, wide, st, tombstones), "build select");
+    const uint64_t ne = static_cast<uint64_t>(s.cnt) * M;
+    size_t tb = tmp_bytes;
+    hip_check(alaya_amd::sort_edges(sort_tmp.ptr, &tb, k_in.as<uint64_t>(), k_out.as<uint64_t>(), dd_in.as<float>(),
+                                    dd_out.as<float>(), ne, st), "sort edges");
+    bp.edge_keys = k_out.as<uint64_t>();
+    bp.edge_d = dd_out.as<float>();
+    bp.n_edges = ne;
+    const int agrid = static_cast<int>(std::min<uint64_t>((ne + 63) / 64, static_cast<uint64_t>(ix->num_cus) * 16));
+    hip_check(alaya_amd::launch_build_apply(bp, agrid, st, duplicates), "build apply");
+    run.launches += 4;
+  }
+  hip_check(hipEventRecord(e1, st), "event");
+  before_sync();
+  hip_check(hipMemcpyAsync(run.counters, cnt.ptr, sizeof(run.counters), hipMemcpyDeviceToHost, st), "D2H");
+  hip_check(hipStreamSynchronize(st), "device build");
+  hip_check(hipEventElapsedTime(&run.ms, e0, e1), "event");
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  run.batches = steps.empty() ? 0 : 1;
+  for (size_t i = 1; i < steps.size(); ++i) run.batches += steps[i].first != steps[i - 1].first ? 1 : 0;
+  return run;
+}
+
+// The device graph's l0 and overlay rows into a host graph whose levels and offsets the caller set.
+void queue_graph_download(alaya_index *ix, HostGraph &g, uint64_t n_upper) {
+  g.l0.resize(g.n * g.R);
+  g.upper_edges.resize(n_upper);
+  hip_check(hipMemcpyAsync(g.l0.data(), ix->l0.ptr, g.n * g.R * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+  if (n_upper)
+    hip_check(hipMemcpyAsync(g.upper_edges.data(), ix->upper_edges.ptr, n_upper * 4, hipMemcpyDeviceToHost,
+                             ix->stream), "D2H");
 }
 
 }  // namespace
@@ -1830,9 +1981,6 @@ int alaya_index_build_graph(alaya_index *ix, uint32_t R, uint32_t ef_constructio
     batch_div = batch_div ? batch_div : 16;
     max_batch = max_batch ? max_batch : 65536;
     hipStream_t st = ix->stream;
-    hipEvent_t e0, e1;
-    hip_check(hipEventCreate(&e0), "event");
-    hip_check(hipEventCreate(&e1), "event");
 
     // levels and overlay offsets are known up front (upper lists R wide, HNSWBuilder's export)
     const std::vector<uint32_t> lv = alaya_amd::hnsw_levels(n, M, seed);
@@ -1842,14 +1990,13 @@ int alaya_index_build_graph(alaya_index *ix, uint32_t R, uint32_t ef_constructio
       off[i] = n_upper;
       n_upper += static_cast<uint64_t>(lv[i]) * R;
     }
+    // the build is an extension of the one-row graph {row 0}
     std::vector<uint32_t> act;
     uint32_t ep = 0;
     int maxl = 0;
-    const std::vector<BuildStep> steps = build_schedule(lv, batch_div, max_batch, refine, act, &ep, &maxl);
-    uint32_t bmax = 1;
-    for (const BuildStep &s : steps) bmax = std::max(bmax, s.cnt);
+    const std::vector<BuildStep> steps = build_schedule(lv.data(), n, 1, 0, batch_div, max_batch, refine, act, &ep, &maxl);
 
-    // device graph (installed as the index's search graph) + scratch
+    // device graph (installed as the index's search graph)
     ix->has_graph = false;
     ix->upd_graph.reset();
     ix->upd_rows.reset();
@@ -1866,116 +2013,17 @@ int alaya_index_build_graph(alaya_index *ix, uint32_t R, uint32_t ef_constructio
     if (n_upper) hip_check(hipMemsetAsync(ix->upper_edges.ptr, 0xff, n_upper * 4, st), "memset");
     hip_check(hipMemcpyAsync(ix->levels.ptr, lv.data(), n * 4, hipMemcpyHostToDevice, st), "H2D");
     hip_check(hipMemcpyAsync(ix->upper_off.ptr, off.data(), n * 8, hipMemcpyHostToDevice, st), "H2D");
-    DevBuf d_act, d_next, c_ids, c_d, c_n, k_in, k_out, dd_in, dd_out, sort_tmp, cnt;
-    d_act.reserve(std::max<size_t>(act.size(), 1) * 4);
-    if (!act.empty())
-      hip_check(hipMemcpyAsync(d_act.ptr, act.data(), act.size() * 4, hipMemcpyHostToDevice, st), "H2D");
-    d_next.reserve(static_cast<size_t>(max_batch) * 4);
-    c_ids.reserve(static_cast<size_t>(bmax) * ef * 4);
-    c_d.reserve(static_cast<size_t>(bmax) * ef * 4);
-    c_n.reserve(static_cast<size_t>(bmax) * 4);
-    const size_t n_edge_max = static_cast<size_t>(bmax) * M;
-    k_in.reserve(n_edge_max * 8);
-    k_out.reserve(n_edge_max * 8);
-    dd_in.reserve(n_edge_max * 4);
-    dd_out.reserve(n_edge_max * 4);
-    size_t tmp_bytes = 0;
-    hip_check(alaya_amd::sort_edges(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, n_edge_max, st), "sort size");
-    sort_tmp.reserve(tmp_bytes);
-    cnt.reserve(8 * 8);
-    hip_check(hipMemsetAsync(cnt.ptr, 0, 8 * 8, st), "memset");
-    ix->work.reserve(4);
 
-    alaya_amd::BuildParams bp{};
-    bp.s = base_params(ix);
-    bp.s.valid = nullptr;
-    bp.s.l0 = ix->l0.as<uint32_t>();
-    bp.s.R = R;
-    bp.s.levels = ix->levels.as<uint32_t>();
-    bp.s.upper_off = ix->upper_off.as<uint64_t>();
-    bp.s.upper_edges = ix->upper_edges.as<uint32_t>();
-    bp.s.upper_R = R;
-    bp.s.queries = nullptr;
-    bp.s.ef = ef;
-    bp.s.work_counter = ix->work.as<uint32_t>();
-    bp.l0w = ix->l0.as<uint32_t>();
-    bp.upw = ix->upper_edges.as<uint32_t>();
-    bp.next = d_next.as<uint32_t>();
-    bp.cand_ids = c_ids.as<uint32_t>();
-    bp.cand_d = c_d.as<float>();
-    bp.cand_n = c_n.as<uint32_t>();
-    bp.M = M;
-    bp.counters = cnt.as<unsigned long long>();
-    // visited-set sizing and the spill area for the largest batch (sized once: kernels in flight)
-    {
-      SearchParams probe = bp.s;
-      const uint32_t hl = size_visited(ix, probe, alaya_amd::resolve_search_variant({ix->dim, probe.ip, 0, ix->generic, 0}),
-                                       bmax, ef);
-      const size_t lds = alaya_amd::build_lds_bytes(ix->stride, ef, hl, probe.vis_rbits != alaya_amd::kVisWide);
-      bp.s.hash_log2 = hl;
-      bp.s.vis_rbits = probe.vis_rbits;
-      bp.s.vis_lbits = probe.vis_lbits;
-      bp.s.vis_max_disp = probe.vis_max_disp;
-      bp.s.vis_limit = probe.vis_limit;
-      if (lds > kLdsPerCu) throw ArgError("ef_construction / dim too large for the LDS budget");
-    }
-    const size_t lds = alaya_amd::build_lds_bytes(ix->stride, ef, bp.s.hash_log2, bp.s.vis_rbits != alaya_amd::kVisWide);
-    int per_cu = 0;
-    hip_check(alaya_amd::build_search_occupancy(bp, lds, &per_cu), "occupancy");
-    per_cu = std::max(1, per_cu);
-    const uint64_t grid_max = static_cast<uint64_t>(per_cu) * ix->num_cus;
-    prepare_spill(ix, bp.s, std::min<uint64_t>(grid_max, bmax), st);
-
-    hip_check(hipEventRecord(e0, st), "event");
-    uint64_t launches = 0;
-    for (const BuildStep &s : steps) {
-      bp.s.nq = s.cnt;
-      bp.s.ep = s.ep;
-      bp.pts = d_act.as<uint32_t>() + s.off;
-      bp.batch_first = s.first;
-      bp.level = s.level;
-      bp.max_level = s.max_level;
-      bp.refine = s.refine;
-      bp.Mmax = s.level == 0 ? R : M;
-      bp.edge_keys = k_in.as<uint64_t>();
-      bp.edge_d = dd_in.as<float>();
-      const int grid = static_cast<int>(std::min<uint64_t>(s.cnt, grid_max));
-      const int wide = static_cast<int>(std::min<uint64_t>(s.cnt, static_cast<uint64_t>(ix->num_cus) * 16));
-      hip_check(hipMemsetAsync(bp.s.work_counter, 0, 4, st), "memset");
-      hip_check(alaya_amd::launch_build_search(bp, grid, lds, st), "build search");
-      hip_check(alaya_amd::launch_build_select(bp, wide, st), "build select");
-      const uint64_t ne = static_cast<uint64_t>(s.cnt) * M;
-      size_t tb = tmp_bytes;
-      hip_check(alaya_amd::sort_edges(sort_tmp.ptr, &tb, k_in.as<uint64_t>(), k_out.as<uint64_t>(), dd_in.as<float>(),
-                                      dd_out.as<float>(), ne, st), "sort edges");
-      bp.edge_keys = k_out.as<uint64_t>();
-      bp.edge_d = dd_out.as<float>();
-      bp.n_edges = ne;
-      const int agrid = static_cast<int>(std::min<uint64_t>((ne + 63) / 64, static_cast<uint64_t>(ix->num_cus) * 16));
-      hip_check(alaya_amd::launch_build_apply(bp, agrid, st), "build apply");
-      launches += 4;
-    }
-    hip_check(hipEventRecord(e1, st), "event");
     HostGraph g;
     g.n = n;
     g.R = R;
-    g.l0.resize(n * R);
     g.has_overlay = true;
     g.upper_R = R;
     g.ep = ep;
     g.levels = lv;
     g.upper_off = off;
-    g.upper_edges.resize(n_upper);
-    hip_check(hipMemcpyAsync(g.l0.data(), ix->l0.ptr, n * R * 4, hipMemcpyDeviceToHost, st), "D2H");
-    if (n_upper)
-      hip_check(hipMemcpyAsync(g.upper_edges.data(), ix->upper_edges.ptr, n_upper * 4, hipMemcpyDeviceToHost, st), "D2H");
-    unsigned long long hc[8] = {0};
-    hip_check(hipMemcpyAsync(hc, cnt.ptr, sizeof(hc), hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "device build");
-    float ms = 0.f;
-    hip_check(hipEventElapsedTime(&ms, e0, e1), "event");
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    const BuildRun run = run_build_steps(ix, R, ef, max_batch, steps, act, false, false,
+                                         [&] { queue_graph_download(ix, g, n_upper); });
     ix->R = R;
     ix->upper_R = R;
     ix->ep = ep;
@@ -1984,18 +2032,155 @@ int alaya_index_build_graph(alaya_index *ix, uint32_t R, uint32_t ef_constructio
     ix->dedup = false;
     ix->graph_n = n;
     ix->has_graph = true;
-    if (stats) {
-      stats[0] = steps.empty() ? 0 : 1;
-      for (size_t i = 1; i < steps.size(); ++i) stats[0] += steps[i].first != steps[i - 1].first ? 1 : 0;
-      stats[1] = launches;
-      stats[2] = hc[0];
-      stats[3] = hc[1];
-      stats[4] = hc[2];
-      stats[5] = static_cast<uint64_t>(ms * 1000.0);
-      stats[6] = bmax;
-      stats[7] = static_cast<uint64_t>(maxl);
-    }
+    run.write(stats, maxl);
     if (out) *out = new alaya_graph{std::move(g)};
+  });
+}
+
+int alaya_build_batches(const uint32_t *levels, uint64_t n, uint64_t start, uint32_t ep, uint32_t batch_div,
+                        uint32_t max_batch, uint64_t *ends, uint64_t *n_batches) {
+  return guarded([&] {
+    if ((n && !levels) || !n_batches) throw ArgError("invalid arguments");
+    if (start == 0 || start > n || ep >= start) throw ArgError("start must be in 1..n and the entry point below it");
+    std::vector<uint32_t> act;
+    std::vector<uint64_t> e;
+    uint32_t fep = 0;
+    int fmax = 0;
+    build_schedule(levels, n, start, ep, batch_div ? batch_div : 16, max_batch ? max_batch : 65536, 0, act, &fep, &fmax,
+                   &e);
+    *n_batches = e.size();
+    if (ends) std::copy(e.begin(), e.end(), ends);
+  });
+}
+
+int alaya_index_extend_graph(alaya_index *ix, const float *rows, uint64_t count, uint32_t ef_construction,
+                             uint64_t seed, uint32_t batch_div, uint32_t max_batch, uint32_t refine,
+                             alaya_graph **out, uint64_t *stats) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (count && !rows)) throw ArgError("invalid arguments");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    scratch_drain(ix);
+    // every refusal comes before the first change to the index
+    if (!ix->base.ptr || ix->n == 0) throw ArgError("index has no base vectors");
+    if (!ix->has_graph || ix->graph_n != ix->n) throw ArgError("index has no graph over its rows");
+    if (!ix->has_overlay || ix->upper_R != ix->R)
+      throw ArgError("the device build extends HNSW graphs whose overlay lists are max_nbrs wide");
+    const uint32_t R = ix->R;
+    if (R < 2 || R > 64 || R % 2) throw ArgError("max_nbrs must be even and in 2..64 for the device build");
+    const uint64_t n0 = ix->n, n = n0 + count;
+    if (n >= (1ull << 31)) throw ArgError("ids must stay below 2^31 (LinearPool checked bit)");
+    if (ix->upd_graph && ix->upd_graph->n != n0) throw ArgError("the update mirror and the device index differ");
+    const uint32_t M = R / 2;
+    const uint32_t ef = std::max(ef_construction, M);
+    batch_div = batch_div ? batch_div : 16;
+    max_batch = max_batch ? max_batch : 65536;
+    hipStream_t st = ix->stream;
+
+    // the graph's own levels and offsets; the new rows take the tail of the draw for n rows (a
+    // sequential draw: its first n0 levels are the draw for n0 rows) and overlay slots past the end
+    std::vector<uint32_t> lv(n);
+    std::vector<uint64_t> off(n);
+    hip_check(hipMemcpyAsync(lv.data(), ix->levels.ptr, n0 * 4, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipMemcpyAsync(off.data(), ix->upper_off.ptr, n0 * 8, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "read levels");
+    uint64_t n_upper0 = 0;
+    for (uint64_t i = 0; i < n0; ++i)
+      if (lv[i]) n_upper0 = std::max(n_upper0, off[i] + static_cast<uint64_t>(lv[i]) * R);
+    if (n_upper0 * 4 > ix->upper_edges.bytes || ix->ep >= n0) throw ArgError("the installed graph is inconsistent");
+    uint64_t n_upper = n_upper0;
+    if (count) {
+      const std::vector<uint32_t> draw = alaya_amd::hnsw_levels(n, M, seed);
+      for (uint64_t i = n0; i < n; ++i) {
+        lv[i] = draw[i];
+        off[i] = n_upper;
+        n_upper += static_cast<uint64_t>(lv[i]) * R;
+      }
+    }
+    std::vector<uint32_t> act;
+    uint32_t ep = ix->ep;
+    int maxl = static_cast<int>(lv[ep]);
+    const std::vector<BuildStep> steps =
+        build_schedule(lv.data(), n, n0, ix->ep, batch_div, max_batch, refine, act, &ep, &maxl);
+
+    // removed rows: the bitmap travels with the build only when a bit of [0, n0) is clear
+    bool tombstones = false;
+    if (ix->has_valid) {
+      std::vector<uint32_t> w((n0 + 31) / 32);
+      hip_check(hipMemcpy(w.data(), ix->valid.ptr, w.size() * 4, hipMemcpyDeviceToHost), "read bitmap");
+      for (uint64_t i = 0; i < n0 && !tombstones; ++i) tombstones = !((w[i >> 5] >> (i & 31)) & 1u);
+    }
+
+    // grow every per-row buffer once, then write the rows, their bits, codes and empty graph slots
+    const size_t row = static_cast<size_t>(ix->stride) * 4;
+    grow_keep(ix, ix->base, n * row, n0 * row);
+    if (ix->has_valid) grow_keep(ix, ix->valid, (n + 31) / 32 * 4, (n0 + 31) / 32 * 4);
+    grow_keep(ix, ix->l0, n * R * 4, n0 * R * 4);
+    grow_keep(ix, ix->levels, n * 4, n0 * 4);
+    grow_keep(ix, ix->upper_off, n * 8, n0 * 8);
+    grow_keep(ix, ix->upper_edges, std::max<uint64_t>(n_upper, 1) * 4, n_upper0 * 4);
+    if (ix->has_sq8) grow_keep(ix, ix->codes, n * ix->code_stride, n0 * ix->code_stride);
+    ix->capacity = std::max(ix->capacity, n);
+    if (count) {
+      write_rows_locked(ix, n0, rows, count);  // ix->n = n; norms, tiles and screen copies follow
+      if (ix->has_valid) {
+        hip_check(alaya_amd::launch_set_valid_range(ix->valid.as<uint32_t>(), n0, count, st), "set valid");
+        ix->tiles_ready = false;
+      }
+      if (ix->has_sq8)
+        hip_check(alaya_amd::launch_sq8_encode_rows(ix->base.as<float>(), ix->stride, ix->dim, ix->sq_min.as<float>(),
+                                                    ix->sq_max.as<float>(), ix->codes.as<uint8_t>(), ix->code_stride,
+                                                    n0, count, st), "sq8 encode");
+      hip_check(hipMemsetAsync(ix->l0.as<uint32_t>() + n0 * R, 0xff, count * R * 4, st), "memset");
+      if (n_upper > n_upper0)
+        hip_check(hipMemsetAsync(ix->upper_edges.as<uint32_t>() + n_upper0, 0xff, (n_upper - n_upper0) * 4, st), "memset");
+      hip_check(hipMemcpyAsync(ix->levels.as<uint32_t>() + n0, lv.data() + n0, count * 4, hipMemcpyHostToDevice, st), "H2D");
+      hip_check(hipMemcpyAsync(ix->upper_off.as<uint64_t>() + n0, off.data() + n0, count * 8, hipMemcpyHostToDevice, st),
+                "H2D");
+    }
+    ix->graph_n = n;
+
+    HostGraph g;
+    g.n = n;
+    g.R = R;
+    g.has_overlay = true;
+    g.upper_R = R;
+    g.ep = ep;
+    g.levels = lv;
+    g.upper_off = off;
+    BuildRun run;
+    try {
+      run = run_build_steps(ix, R, ef, max_batch, steps, act, tombstones, ix->dedup,
+                            [&] { queue_graph_download(ix, g, n_upper); });
+    } catch (const ArgError &) {  // refused before its first launch (the LDS budget): the rows are not added
+      ix->n = n0;
+      ix->graph_n = n0;
+      throw;
+    }
+    ix->ep = ep;
+    if (ix->upd_graph) {  // the mirror follows; the record of pending removals (upd_ctx) stays
+      *ix->upd_graph = g;
+      alaya_amd::RowMirror &m = *ix->upd_rows;
+      m.rows.insert(m.rows.end(), rows, rows + count * ix->dim);
+      if (m.valid.size() < (ix->capacity + 7) / 8 + 1) m.valid.resize((ix->capacity + 7) / 8 + 1, 0);
+      for (uint64_t i = n0; i < n; ++i) m.valid[i >> 3] |= static_cast<uint8_t>(1u << (i & 7));
+    }
+    run.write(stats, maxl);
+    if (out) *out = new alaya_graph{std::move(g)};
+  });
+}
+
+int alaya_index_read_sq8(alaya_index *ix, uint64_t first, uint64_t count, uint8_t *codes) {
+  return guarded([&] {
+    if (!ix || (count && !codes)) throw ArgError("invalid arguments");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    if (!ix->has_sq8) throw ArgError("index has no SQ8 codes");
+    if (first + count > ix->n || (first + count) * ix->code_stride > ix->codes.bytes) throw ArgError("rows out of range");
+    if (!count) return;
+    hip_check(hipMemcpy2DAsync(codes, ix->dim, ix->codes.as<uint8_t>() + first * ix->code_stride, ix->code_stride,
+                               ix->dim, count, hipMemcpyDeviceToHost, ix->stream), "read codes");
+    hip_check(hipStreamSynchronize(ix->stream), "read codes");
   });
 }
 

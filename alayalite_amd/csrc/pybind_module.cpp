@@ -267,7 +267,9 @@ class PyIndexInterface : public LaunchControls {
       {
         py::gil_scoped_release nogil;
         check(alaya_index_set_base(ix_, rows_f32_.data(), n, dim_, dist_code(), nullptr));
-        check(alaya_index_build_graph(ix_, params_.max_nbrs_, ef_construction, 100, 0, 0, 2, &graph_, nullptr));
+        uint64_t st[8] = {0};
+        check(alaya_index_build_graph(ix_, params_.max_nbrs_, ef_construction, 100, 0, 0, 2, &graph_, st));
+        last_build_us_ = st[5];
       }
       if (params_.quantization_type_ == QuantizationType::SQ8) {
         train_sq8(num_threads);
@@ -425,6 +427,65 @@ class PyIndexInterface : public LaunchControls {
     }
     graph_dirty_ = true;
     return py::int_(id);
+  }
+
+  // --- extra (not in the reference binding): append rows in bulk by continuing the batched device build
+  // (alaya_index_extend_graph) with fit(builder="gpu")'s seed and schedule, whatever built the graph.
+  // Rows are checked and, for COS, normalised in place as fit does; an SQ8 index encodes them on the
+  // device with its fitted quantizer (values outside the fitted range clamp).  Returns the first new id.
+  uint64_t add(py::array vectors, uint32_t ef_construction) {
+    if (!graph_) throw std::runtime_error("Index is not init yet");
+    if (vectors.ndim() != 2) throw std::runtime_error("Array must be 2D");
+    check_dtype(vectors);
+    if (static_cast<uint32_t>(vectors.shape(1)) != dim_) throw std::runtime_error("vector dimension mismatch");
+    py::array arr = py::array::ensure(vectors, py::array::c_style);
+    const uint64_t m = arr.shape(0), n0 = n_;
+    if (n0 + m > params_.capacity_) throw std::runtime_error("The index is full, cannot insert more vectors");
+    if (m == 0) return n0;
+    if (params_.metric_ == MetricType::COS) normalize_in_place(arr, m);
+    std::vector<float> rows(m * dim_);
+    to_float(arr.data(), dtype_, m * dim_, rows.data());
+    const bool sq8 = params_.quantization_type_ == QuantizationType::SQ8;
+    std::vector<uint8_t> codes(sq8 ? m * dim_ : 0);
+    alaya_graph *g = nullptr;
+    {
+      py::gil_scoped_release nogil;
+      uint64_t st[8] = {0};
+      check(alaya_index_extend_graph(ix_, rows.data(), m, ef_construction, 100, 0, 0, 2, &g, st));
+      last_build_us_ = st[5];
+      if (sq8) check(alaya_index_read_sq8(ix_, n0, m, codes.data()));
+    }
+    alaya_graph_free(graph_);
+    graph_ = g;
+    graph_dirty_ = false;  // the returned graph is the device's, inserts included; the mirror followed
+    const size_t es = dtype_size(dtype_);
+    raw_.insert(raw_.end(), static_cast<const char *>(arr.data()), static_cast<const char *>(arr.data()) + m * dim_ * es);
+    rows_f32_.insert(rows_f32_.end(), rows.begin(), rows.end());
+    sq_codes_.insert(sq_codes_.end(), codes.begin(), codes.end());
+    n_ += m;
+    if (!valid_.empty()) {
+      valid_.resize((n_ + 7) / 8, 0);
+      for (uint64_t i = n0; i < n_; ++i) valid_[i / 8] |= static_cast<uint8_t>(1u << (i % 8));
+    }
+    return n0;
+  }
+
+  // the SQ8 codes the device searches, rows [0, n) x dim (tests, tools)
+  py::array sq8_codes() {
+    if (params_.quantization_type_ != QuantizationType::SQ8) throw std::runtime_error("not an SQ8 index");
+    py::array_t<uint8_t> out = out2d<uint8_t>(n_, dim_);
+    check(alaya_index_read_sq8(ix_, 0, n_, out.mutable_data()));
+    return out;
+  }
+  // device time of the last fit(builder="gpu") or add: the build steps alone (tools/add_sweep.py)
+  double last_build_device_ms() const { return static_cast<double>(last_build_us_) / 1000.0; }
+  py::tuple sq8_range() const {
+    py::array_t<float> mn(static_cast<py::ssize_t>(sq_min_.size())), mx(static_cast<py::ssize_t>(sq_max_.size()));
+    if (!sq_min_.empty()) {
+      std::memcpy(mn.mutable_data(), sq_min_.data(), sq_min_.size() * 4);
+      std::memcpy(mx.mutable_data(), sq_max_.data(), sq_max_.size() * 4);
+    }
+    return py::make_tuple(mn, mx);
   }
 
   // PyIndex::remove -> GraphUpdateJob::remove (index.hpp:234, graph_update_job.hpp:91-103)
@@ -779,6 +840,7 @@ class PyIndexInterface : public LaunchControls {
   std::vector<float> rows_f32_;    // float rows uploaded to HBM
   std::vector<uint8_t> valid_;     // empty = all valid
   uint64_t delete_cnt_ = 0;        // RawSpace::delete_cnt_
+  uint64_t last_build_us_ = 0;     // last_build_device_ms
   bool updates_enabled_ = false;   // the device index holds an update mirror (alaya_index_enable_updates)
   bool graph_dirty_ = false;       // graph_ predates inserts (sync_graph refreshes it)
   std::vector<uint32_t> last_counters_;
@@ -879,6 +941,35 @@ class DeviceIndex : public LaunchControls {
       py::gil_scoped_release nogil;
       check(alaya_index_build_graph(ix_, R, efc, seed, batch_div, max_batch, refine, &g, st));
     }
+    return py::make_tuple(std::make_shared<Graph>(g), build_stats(st));
+  }
+  // append rows by continuing the device build on the installed graph (alaya_index_extend_graph): the
+  // whole grown graph and the stats of this call's batches
+  py::tuple extend_graph(F32Array rows, uint32_t efc, uint64_t seed, uint32_t batch_div, uint32_t max_batch,
+                         uint32_t refine) {
+    uint64_t n = 0;
+    uint32_t dim = 0;
+    check(alaya_index_info(ix_, &n, &dim, nullptr, nullptr, nullptr));
+    if (rows.ndim() != 2 || static_cast<uint32_t>(rows.shape(1)) != dim)
+      throw py::value_error("rows must be 2D with the index's width");
+    alaya_graph *g = nullptr;
+    uint64_t st[8] = {0};
+    const float *ptr = rows.data();
+    const uint64_t count = rows.shape(0);
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_extend_graph(ix_, ptr, count, efc, seed, batch_div, max_batch, refine, &g, st));
+    }
+    return py::make_tuple(std::make_shared<Graph>(g), build_stats(st));
+  }
+  py::array read_sq8(uint64_t first, uint64_t count) {
+    uint32_t dim = 0;
+    check(alaya_index_info(ix_, nullptr, &dim, nullptr, nullptr, nullptr));
+    py::array_t<uint8_t> out = out2d<uint8_t>(count, dim);
+    check(alaya_index_read_sq8(ix_, first, count, out.mutable_data()));
+    return out;
+  }
+  static py::dict build_stats(const uint64_t *st) {
     py::dict stats;
     stats["batches"] = st[0];
     stats["launches"] = st[1];
@@ -888,7 +979,7 @@ class DeviceIndex : public LaunchControls {
     stats["device_ms"] = static_cast<double>(st[5]) / 1000.0;
     stats["max_batch"] = st[6];
     stats["max_level"] = st[7];
-    return py::make_tuple(std::make_shared<Graph>(g), stats);
+    return stats;
   }
   py::tuple search(F32Array q, uint32_t k, uint32_t ef) {
     const uint64_t nq = q.shape(0);
@@ -1173,6 +1264,10 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("get_data_by_id", &PyIndexInterface::get_data_by_id, py::arg("id"))
       .def("insert", &PyIndexInterface::insert, py::arg("insert_data"), py::arg("ef"))
       .def("remove", &PyIndexInterface::remove, py::arg("id"))
+      .def("add", &PyIndexInterface::add, py::arg("vectors"), py::arg("ef_construction"))
+      .def("sq8_codes", &PyIndexInterface::sq8_codes)
+      .def("sq8_range", &PyIndexInterface::sq8_range)
+      .def("last_build_device_ms", &PyIndexInterface::last_build_device_ms)
       .def("batch_search", &PyIndexInterface::batch_search, py::arg("queries"), py::arg("topk"),
            py::arg("ef"), py::arg("num_threads"))
       .def("batch_search_with_distance", &PyIndexInterface::batch_search_with_distance,
@@ -1220,6 +1315,9 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("set_graph", &DeviceIndex::set_graph)
       .def("build_graph", &DeviceIndex::build_graph, py::arg("R") = 32, py::arg("ef_construction") = 100,
            py::arg("seed") = 100, py::arg("batch_div") = 0, py::arg("max_batch") = 0, py::arg("refine") = 2)
+      .def("extend_graph", &DeviceIndex::extend_graph, py::arg("rows"), py::arg("ef_construction") = 100,
+           py::arg("seed") = 100, py::arg("batch_div") = 0, py::arg("max_batch") = 0, py::arg("refine") = 2)
+      .def("read_sq8", &DeviceIndex::read_sq8, py::arg("first"), py::arg("count"))
       .def("search", &DeviceIndex::search, py::arg("queries"), py::arg("k"), py::arg("ef"))
       .def("search_device", &DeviceIndex::search_device)
       .def("filtered_search", &DeviceIndex::filtered_search, py::arg("queries"), py::arg("k"), py::arg("ef"),
@@ -1272,6 +1370,16 @@ PYBIND11_MODULE(_alayalitepy, m) {
     return codes;
   }, py::arg("data"), py::arg("min"), py::arg("max"), py::arg("num_threads") = 1u);
   m.def("host_sq8_order", &host_sq8_order);
+  // the batch ends of the build schedule of rows [start, n) (alaya_build_batches; no device needed)
+  m.def("build_batches", [](U32Array levels, uint64_t start, uint32_t ep, uint32_t batch_div, uint32_t max_batch) {
+    if (levels.ndim() != 1) throw py::value_error("levels must be 1D");
+    const uint64_t n = levels.shape(0);
+    uint64_t nb = 0;
+    check(alaya_build_batches(levels.data(), n, start, ep, batch_div, max_batch, nullptr, &nb));
+    py::array_t<uint64_t> ends(static_cast<py::ssize_t>(nb));
+    check(alaya_build_batches(levels.data(), n, start, ep, batch_div, max_batch, ends.mutable_data(), &nb));
+    return ends;
+  }, py::arg("levels"), py::arg("start") = 1, py::arg("ep") = 0, py::arg("batch_div") = 0, py::arg("max_batch") = 0);
   m.def("build_info", [] { return std::string(alaya_build_info()); });
   m.def("screen_lower_bound", [](F32Array d_tilde, F32Array e_row, uint32_t dim) {
     if (d_tilde.size() != e_row.size()) throw std::invalid_argument("d_tilde and e_row differ in size");

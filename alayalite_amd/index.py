@@ -64,6 +64,32 @@ class Index:
             raise RuntimeError("The index is full, cannot insert more vectors")
         return ret
 
+    def add(self, vectors: VectorLikeBatch, ef_construction: int = 100) -> VectorLike:
+        """Append the rows of ``vectors`` (2-D, the index's width and dtype) in bulk and return their
+        ids, ``n0 .. n0 + m - 1`` in the index's id type.  The graph grows on the MI355X by continuing
+        the batched build of ``fit(builder="gpu")`` (same seed, schedule and refine passes) from the
+        graph the index holds, whatever built it and whatever ``insert`` / ``remove`` did to it; when
+        ``n0`` is a batch boundary of that build, ``fit(first n0) + add(rest)`` is ``fit(all)`` exactly.
+        No new row links to a removed row.  COS rows are normalised in place, as ``fit`` does.  An SQ8
+        index encodes the new rows with the quantizer fitted at ``fit``: it is not retrained, so values
+        outside a dimension's fitted range clamp.  ``m == 0`` is a no-op; past the index capacity the
+        call raises RuntimeError and adds nothing.  One call per block of rows: every call regrows the
+        device buffers and downloads the whole graph."""
+        _assert(self.__index is not None, "Index is not init yet")
+        vectors = np.asarray(vectors)
+        _assert(vectors.ndim == 2, "vectors must be a 2D array")
+        _assert(vectors.shape[1] == self.__dim,
+                "vectors dimension must match the dimension of the vectors used to fit the index."
+                f"fit data dimension: {self.__dim}, vectors dimension: {vectors.shape[1]}")
+        if self.__params.data_type != vectors.dtype:
+            raise ValueError(f"Data type mismatch: {self.__params.data_type} vs {vectors.dtype}")
+        n0, m = self.__index.get_data_num(), vectors.shape[0]
+        if n0 + m > self.__params.capacity:
+            raise RuntimeError("The index is full, cannot insert more vectors")
+        if m:
+            self.__index.add(vectors, ef_construction)
+        return np.arange(n0, n0 + m, dtype=self.__params.id_type)
+
     def remove(self, vector_id: int) -> None:
         _assert(self.__index is not None, "Index is not init yet")
         self.__index.remove(vector_id)

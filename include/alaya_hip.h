@@ -233,6 +233,40 @@ int alaya_index_filtered_search_sq8_device(alaya_index *ix, const float *d_queri
 int alaya_index_build_graph(alaya_index *ix, uint32_t R, uint32_t ef_construction, uint64_t seed,
                             uint32_t batch_div, uint32_t max_batch, uint32_t refine, alaya_graph **out,
                             uint64_t *stats);
+/* ---- bulk growth (Index.add) ----------------------------------------------------------------
+ * Appends `count` rows (ix->dim floats each, COS rows already normalised) to an index that has rows
+ * and an installed HNSW graph over them -- device-built, host-built, loaded, or changed by
+ * alaya_index_insert / alaya_index_remove -- by continuing the batched build above: the graph is the
+ * state after rows [0, n0), the new rows are inserted in label order, their levels are the tail of
+ * the draw for n0 + count rows from `seed`, the batch sizes follow from the rows inserted so far and
+ * the first batch starts from the graph's own entry point and max level.  So when n0 is a batch
+ * boundary of the schedule for all rows, build(n0 rows) + extend(the rest) is build(all rows) bit
+ * for bit (alaya_build_batches lists the boundaries).  Needs an overlay whose lists are R wide, R
+ * even in 2..64 and n0 + count < 2^31; anything else is ALAYA_ERR_ARG and leaves the index as it was.
+ * Every per-row device buffer grows once per call, so one large call beats many small ones.
+ *
+ * Removed rows (cleared validity bits): the build's searches measure them as a query does (FLT_MAX)
+ * and the neighbour selection drops them, so no new row links to a removed row on any level, no
+ * removed row receives an edge and the removed rows' own lists stay as they are.  Rows the update
+ * job rewrote may repeat ids; they are taken as they are.
+ * SQ8 indexes: the new rows' codes are encoded on the device with the quantizer the index was given
+ * (alaya_index_set_sq8's min / max, alaya_sq8_encode's arithmetic).  The quantizer is not retrained:
+ * a value outside the fitted range of its dimension clamps to code 0 or 255.  alaya_index_read_sq8
+ * copies codes of rows [first, first + count) back (dim bytes per row).
+ * The new rows are valid, the grown graph stays installed, a host copy of the whole graph is
+ * returned in *out (nullable), and an update mirror (alaya_index_enable_updates), if there is one,
+ * follows with its record of removals kept.  stats as alaya_index_build_graph's, for this call's
+ * batches alone. */
+int alaya_index_extend_graph(alaya_index *ix, const float *rows, uint64_t count, uint32_t ef_construction,
+                             uint64_t seed, uint32_t batch_div, uint32_t max_batch, uint32_t refine,
+                             alaya_graph **out, uint64_t *stats);
+int alaya_index_read_sq8(alaya_index *ix, uint64_t first, uint64_t count, uint8_t *codes);
+/* Host only: the batch ends of the schedule of rows [start, n) with the given levels, for a graph
+ * over rows [0, start) whose entry point is `ep` (a build from scratch: start = 1, ep = 0).  ends
+ * NULL: count only.  Every end is a row count at which alaya_index_extend_graph continues the
+ * schedule exactly. */
+int alaya_build_batches(const uint32_t *levels, uint64_t n, uint64_t start, uint32_t ep, uint32_t batch_div,
+                        uint32_t max_batch, uint64_t *ends, uint64_t *n_batches);
 /* ---- online updates (Index.insert / Index.remove) ------------------------------------------
  * Device-mirror primitives, for a host that keeps its own graph and update job (the reference's
  * GraphUpdateJob, include/executor/jobs/graph_update_job.hpp:49-137) and patches HBM after each

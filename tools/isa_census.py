@@ -171,13 +171,14 @@ def census(name: str, body: list[str]) -> dict:
 
 def normalise(body: list[str]) -> list[str]:
     """A kernel body without what differs between two compiles of one source: comments, debug
-    directives and the per-compile __hip_cuid_ symbol."""
+    directives, the per-compile __hip_cuid_ symbol and the function's ordinal in its block labels
+    (.LBB<ordinal>_<block>: kernels added to the file renumber the ones after them)."""
     out = []
     for ln in body:
         s = ln.split(";", 1)[0].strip()
         if not s or s.startswith((".file", ".loc", ".ident")) or "__hip_cuid_" in s:
             continue
-        out.append(s)
+        out.append(re.sub(r"\.LBB\d+_", ".LBB_", s))
     return out
 
 
@@ -216,8 +217,10 @@ def main() -> None:
     ap.add_argument("--extra", default="", help="extra hipcc flags (e.g. -DALAYA_...)")
     ap.add_argument("--compare", default=None, metavar="PATH",
                     help="another tree's search_kernels.hip: report identical / differs per kernel and exit")
+    ap.add_argument("--src", default=SRC, metavar="PATH",
+                    help="this tree's file to compile (with --compare: e.g. csrc/build_kernels.hip against the parent's)")
     args = ap.parse_args()
-    asm = compile_asm(SRC, args.extra.split())
+    asm = compile_asm(args.src, args.extra.split())
     if args.compare:
         raise SystemExit(0 if compare(asm, compile_asm(args.compare, args.extra.split())) else 1)
     rows = []
