@@ -134,6 +134,9 @@ struct alaya_index {
   DevBuf work, overflow, dirty, stab, q_buf, id_buf, dist_buf, cnt_buf, dlist_buf, dout_buf;
   DevBuf allow_buf, group_buf;  // the host filtered search's masks and per-query mask indices
   DevBuf through_buf;           // the host through search's rows stepped through per query
+  // range search: the append buffers of both entry points (nq x cap ids and distances, scratch between the search
+  // launch and the sort), and the host entry's radii and counts
+  DevBuf range_ids, range_d, range_radii, range_cnt;
   // exact filtered scan (alaya_index_flat_search_filtered*): the current mask's id list (n words), the
   // compaction's block sums and count, the partial lists of one scan launch (capped, see
   // alaya_amd::flat_filtered_plan) and the queries ordered by mask
@@ -366,9 +369,10 @@ bool helpers_requested(const alaya_index *ix, const SearchParams &p, uint64_t nq
 }
 
 // filter_k != 0: the filtered search -- its own kernel's registers, and a result pool of filter_k entries
-// in every wave's region (hop: the through search's kernel).
+// in every wave's region (hop: the through search's kernel).  range: the range search -- its own kernel's
+// registers and no result pool.
 uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchVariant &v, uint64_t nq, uint32_t ef,
-                      int W = 1, uint32_t filter_k = 0, bool hop = false) {
+                      int W = 1, uint32_t filter_k = 0, bool hop = false, bool range = false) {
   const uint32_t lbits = std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2)));
   const int mode = ix->visited_mode_override;  // 0 auto, 1 compact, 2 wide, 3 compact + short probes
   auto set_mode = [&](uint32_t l, bool compact) {
@@ -414,7 +418,8 @@ uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchV
   const bool stab = p.stab_log2 != 0;  // set by do_search (spill_table_log2)
   int vgpr_blocks = 0;
   const size_t probe_lds = shared + W * (wave_fixed + (stab ? 1024 : 4096));
-  hip_check(!filter_k ? alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks)
+  hip_check(range ? alaya_amd::range_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
+            : !filter_k ? alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks)
             : hop ? alaya_amd::filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
             : p.sq8_order ? alaya_amd::filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, probe_lds, &vgpr_blocks)
                           : alaya_amd::filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks),
@@ -761,10 +766,17 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
 //
 // hop: the through search (alaya_index_filtered_search_hop*, filtered_hop_search_kernel; f32 rows only) -- the same
 // plan with that kernel's occupancy; d_through (nullable) receives the rows stepped through per query.
+//
+// range: the search stage of the range search (alaya_index_range_search*, range_search_kernel; f32 rows only) -- the
+// same plan without a result pool (k = 0, d_ids / d_dists unused) and with that kernel's occupancy; d_allow may be
+// null (no mask).  The kernel fills range->counts and the append buffers; the caller launches the sort.
 void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef, const uint32_t *d_allow,
                         const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt,
-                        hipStream_t stream, bool sq8 = false, bool hop = false, uint32_t *d_through = nullptr) {
+                        hipStream_t stream, bool sq8 = false, bool hop = false, uint32_t *d_through = nullptr,
+                        const alaya_amd::RangeParams *range = nullptr) {
   using namespace alaya_amd;
+  if (range && (sq8 || ix->has_sq8))
+    throw ArgError("range search of an SQ8 index: alaya_index_range_search searches f32 rows only");
   if (hop && (sq8 || ix->has_sq8))
     throw ArgError("through search of an SQ8 index: alaya_index_filtered_search_hop searches f32 rows only");
   if (!ix->base.ptr) throw ArgError("index has no base vectors");
@@ -773,7 +785,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   if (!sq8 && ix->has_sq8)
     throw ArgError("filtered search of an SQ8 index: use alaya_index_filtered_search_sq8 (this call searches f32 rows only)");
   if (ef == 0) throw ArgError("ef must be >= 1");
-  if (k == 0 || k > 224) throw ArgError("filtered search: k must be in 1..224");
+  if (!range && (k == 0 || k > 224)) throw ArgError("filtered search: k must be in 1..224");
   if (nq == 0) return;
   if (ix->graph_n > ix->n) throw ArgError("graph has more nodes than base vectors");
   SearchParams p = graph_search_params(ix, d_q, nq, k, ef, d_ids, d_dists, d_cnt);
@@ -782,9 +794,9 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   const SearchVariant &plain = resolve_search_variant({ix->dim, p.ip, p.sq8_order, ix->generic, 0});
   int W = search_waves(p);
   while (W > 1 && static_cast<uint64_t>(W) > nq) W /= 2;
-  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k, hop);
+  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k, hop, range != nullptr);
   const size_t traversal_lds = search_wave_lds_bytes(ix->stride, ef, p.hash_log2, p.vis_rbits != kVisWide, p.sq8_order);
-  p.wave_lds = static_cast<uint32_t>(traversal_lds + filter_result_lds_bytes(k));
+  p.wave_lds = static_cast<uint32_t>(traversal_lds + (range ? 0 : filter_result_lds_bytes(k)));
   FilterParams f{};
   f.allow = d_allow;
   f.mask_of_query = d_mask_of_query;
@@ -792,9 +804,12 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   f.k = k;
   f.result_off = static_cast<uint32_t>(traversal_lds);
   const size_t lds = search_shared_lds_bytes(ix->stride, sq8) + static_cast<size_t>(W) * p.wave_lds;
-  if (lds > kLdsPerCu) throw ArgError("filtered search: k / ef / dim too large for the LDS budget");
+  if (lds > kLdsPerCu)
+    throw ArgError(range ? "range search: ef / dim too large for the LDS budget"
+                         : "filtered search: k / ef / dim too large for the LDS budget");
   int per_cu = 0;
-  hip_check(sq8 ? filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, lds, &per_cu)
+  hip_check(range ? range_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
+            : sq8 ? filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, lds, &per_cu)
             : hop ? filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
                 : filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu),
             "occupancy");
@@ -808,7 +823,8 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   const uint64_t searchers = static_cast<uint64_t>(grid) * W;
   prepare_spill(ix, p, searchers, stream);
   record_launch(ix, p, grid, W, lds, per_cu, searchers, stream);  // (no scout, helpers or screen: p has none set)
-  hip_check(sq8   ? launch_filtered_sq8_search(p, f, grid, W, lds, stream)
+  hip_check(range ? launch_range_search(p, f, *range, grid, W, lds, stream)
+            : sq8 ? launch_filtered_sq8_search(p, f, grid, W, lds, stream)
             : hop ? launch_filtered_hop_search(p, f, HopParams{d_through}, grid, W, lds, stream)
                   : launch_filtered_search(p, f, grid, W, lds, stream),
             "filtered search launch");
@@ -2290,6 +2306,96 @@ int alaya_index_filtered_search_hop(alaya_index *ix, const float *queries, uint6
                                     uint32_t *ids, float *dists, uint32_t *counters, uint32_t *n_through) {
   return filtered_search_host_call(ix, queries, nq, k, ef, allow_words, n_masks, mask_of_query, ids, dists, counters, true,
                                    n_through);
+}
+
+static void check_range_cap(uint32_t max_results) {
+  if (max_results == 0 || max_results > alaya_amd::kRangeMaxCap)
+    throw ArgError("range search: max_results must be in 1..4096");
+}
+
+// alaya_index_range_search_device / alaya_index_range_search: the search stage (do_filtered_search's range plan)
+// into the index's append buffers, then the sort into d_ids / d_dists.  The caller holds ix->mu.
+static void range_search_dev(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t ef, const float *d_radii,
+                             uint32_t max_results, const uint32_t *d_allow, const uint32_t *d_mask_of_query,
+                             uint32_t *d_counts, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt, hipStream_t s) {
+  check_range_cap(max_results);
+  if (ef == 0) throw ArgError("ef must be >= 1");
+  const size_t slots = static_cast<size_t>(nq) * max_results;
+  ix->range_ids.reserve(slots * 4);
+  ix->range_d.reserve(slots * 4);
+  alaya_amd::RangeParams r{};
+  r.radii = d_radii;
+  r.cap = max_results;
+  r.append_ids = ix->range_ids.as<uint32_t>();
+  r.append_dists = ix->range_d.as<float>();
+  r.counts = d_counts;
+  r.out_ids = d_ids;
+  r.out_dists = d_dists;
+  do_filtered_search(ix, d_q, nq, 0, ef, d_allow, d_mask_of_query, nullptr, nullptr, d_cnt, s, false, false, nullptr, &r);
+  if (nq == 0) return;
+  // diagnostics (ALAYA_RANGE_SORT=0, include/alaya_hip.h): the search stage alone, to time it; ids / dists are
+  // then left unwritten
+  if (const char *e = std::getenv("ALAYA_RANGE_SORT"))
+    if (std::atoi(e) == 0) return;
+  hip_check(alaya_amd::launch_range_sort(r, nq, s), "range sort launch");
+  scratch_release(ix, s);  // the sort read the append buffers
+}
+
+// the range entries' mask arguments: none at all (no mask), or what the filtered entries accept
+static void check_range_masks(uint64_t nq, const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                              bool host_indices) {
+  if (!allow_words && n_masks == 0) {
+    if (mask_of_query) throw ArgError("range search: mask_of_query without masks");
+    return;
+  }
+  if (!allow_words) throw ArgError("range search: n_masks without allow_words");
+  check_masks("range search", nq, n_masks, mask_of_query, host_indices);
+}
+
+int alaya_index_range_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t ef, const float *d_radii,
+                                    uint32_t max_results, const uint32_t *d_allow_words, uint32_t n_masks,
+                                    const uint32_t *d_mask_of_query, uint32_t *d_counts, uint32_t *d_ids, float *d_dists,
+                                    uint32_t *d_counters, void *stream) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (nq && (!d_queries || !d_radii || !d_counts || !d_ids || !d_dists))) throw ArgError("invalid arguments");
+    check_range_masks(nq, d_allow_words, n_masks, d_mask_of_query, false);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    range_search_dev(ix, d_queries, nq, ef, d_radii, max_results, d_allow_words, d_mask_of_query, d_counts, d_ids, d_dists,
+                     d_counters, static_cast<hipStream_t>(stream));
+  });
+}
+
+int alaya_index_range_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t ef, const float *radii,
+                             uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
+                             const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists,
+                             uint32_t *counters) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (nq && (!queries || !radii || !counts || !ids || !dists))) throw ArgError("invalid arguments");
+    check_range_masks(nq, allow_words, n_masks, mask_of_query, true);
+    for (uint64_t i = 0; i < nq; ++i)
+      if (radii[i] != radii[i]) throw ArgError("range search: a radius is NaN");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    check_range_cap(max_results);  // (before the result buffers are sized by it)
+    if (nq == 0) {
+      range_search_dev(ix, nullptr, 0, ef, nullptr, max_results, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       ix->stream);  // the index's own refusals
+      return;
+    }
+    const float *d_q = stage_queries(ix, queries, nq, max_results);
+    const uint32_t *d_allow = allow_words ? stage_masks(ix, allow_words, n_masks) : nullptr;
+    const uint32_t *d_groups = allow_words ? stage_mask_indices(ix, mask_of_query, nq) : nullptr;
+    ix->range_radii.reserve(nq * 4);
+    ix->range_cnt.reserve(nq * 4);
+    hip_check(hipMemcpyAsync(ix->range_radii.ptr, radii, nq * 4, hipMemcpyHostToDevice, ix->stream), "upload radii");
+    range_search_dev(ix, d_q, nq, ef, ix->range_radii.as<float>(), max_results, d_allow, d_groups,
+                     ix->range_cnt.as<uint32_t>(), ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(),
+                     ix->cnt_buf.as<uint32_t>(), ix->stream);
+    fetch_results(ix, nq, max_results, ids, dists, counters);
+    hip_check(hipMemcpyAsync(counts, ix->range_cnt.ptr, nq * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    stream_sync(ix, "range search");
+  });
 }
 
 int alaya_index_profile_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k,

@@ -94,6 +94,27 @@ Masks parse_masks(const U32Array &allow_words, const py::object &mask_of_query, 
   return m;
 }
 
+// The range calls' masks: allow_words None = no mask (mask_of_query must then be None too), else parse_masks.
+// `words` owns what the result's words point to.
+Masks parse_range_masks(const py::object &allow_words, U32Array &words, const py::object &mask_of_query, uint64_t n,
+                        uint64_t nq) {
+  if (allow_words.is_none()) {
+    if (!mask_of_query.is_none()) throw py::value_error("mask_of_query needs allow_words");
+    return Masks{};
+  }
+  words = U32Array(allow_words);
+  return parse_masks(words, mask_of_query, n, nq);
+}
+
+// The range calls' radius, a number or an array of shape (nq,), as nq f32 values.
+std::vector<float> parse_radii(const py::object &radius, uint64_t nq) {
+  const F32Array a(radius);
+  if (a.ndim() == 0) return std::vector<float>(nq, *a.data());
+  if (a.ndim() != 1 || static_cast<uint64_t>(a.shape(0)) != nq)
+    throw py::value_error("radius must be a number or hold one value per query");
+  return std::vector<float>(a.data(), a.data() + nq);
+}
+
 enum DType { kF32 = 0, kI8, kU8, kF64, kI32, kU32 };
 
 DType dtype_code(const py::dtype &dt) {
@@ -380,6 +401,36 @@ class PyIndexInterface : public LaunchControls {
                                              m.of_query, ids32.data(), dists.mutable_data()));
     }
     return py::make_tuple(widen_ids(ids32, nq, topk, true), dists);
+  }
+
+  // --- extra (not in the reference binding): every row the traversal of batch_search at `ef` measures within
+  // `radius` (a number or one per query) of the query (alaya_index_range_search; f32 indexes only).  Returns
+  // (counts[nq], ids[nq, max_results], dists[nq, max_results], counters[nq, 4]): row i holds its first
+  // min(counts[i], max_results) hits to arrive, by (distance, id), then empty slots as exact_search's.
+  // allow_words / mask_of_query as for filtered_search, or None for no mask.
+  py::object range_search(py::array queries, uint32_t ef, py::object radius, uint32_t max_results, py::object allow_words,
+                          py::object mask_of_query) {
+    if (!graph_) throw std::runtime_error("Index is not init yet");
+    if (params_.quantization_type_ != QuantizationType::NONE)
+      throw py::value_error("range_search searches f32 indexes only (no SQ8 codes)");
+    py::array q = prepare_queries(queries);
+    const uint64_t nq = q.shape(0);
+    U32Array words;
+    const Masks m = parse_range_masks(allow_words, words, mask_of_query, n_, nq);
+    const std::vector<float> radii = parse_radii(radius, nq);
+    if (max_results == 0 || max_results > 4096) throw py::value_error("max_results must be in 1..4096");
+    std::vector<uint32_t> ids32(nq * max_results);
+    py::array_t<float> dists = out2d<float>(nq, max_results);
+    py::array_t<uint32_t> counts(static_cast<py::ssize_t>(nq));
+    uint32_t *cp = counts.mutable_data();
+    float *dp = dists.mutable_data();
+    last_counters_.assign(nq * 4, 0);
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_range_search(ix_, static_cast<const float *>(q.data()), nq, ef, radii.data(), max_results, m.words,
+                                     m.n_masks, m.of_query, cp, ids32.data(), dp, last_counters_.data()));
+    }
+    return py::make_tuple(counts, widen_ids(ids32, nq, max_results, true), dists, last_counters());
   }
 
   uint64_t get_data_num() const { return n_; }
@@ -1042,6 +1093,35 @@ class DeviceIndex : public LaunchControls {
                                              n_masks, dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(ids),
                                              dptr<float>(dists), dptr<uint32_t>(counters), dptr<void>(stream)));
   }
+  // every row the traversal measures within `radius` (a number or one per query) of the query
+  // (alaya_index_range_search): (counts[nq], ids[nq, max_results], dists[nq, max_results], counters[nq, 4]);
+  // allow_words / mask_of_query as for filtered_search, or None for no mask
+  py::tuple range_search(F32Array q, uint32_t ef, py::object radius, uint32_t max_results, py::object allow_words,
+                         py::object mask_of_query) {
+    const uint64_t nq = q.shape(0);
+    U32Array words;
+    const Masks m = parse_range_masks(allow_words, words, mask_of_query, rows(), nq);
+    const std::vector<float> radii = parse_radii(radius, nq);
+    if (max_results == 0 || max_results > 4096) throw py::value_error("max_results must be in 1..4096");
+    Results r(nq, max_results);
+    py::array_t<uint32_t> counts(static_cast<py::ssize_t>(nq));
+    uint32_t *np = counts.mutable_data();
+    const float *qp = q.data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_range_search(ix_, qp, nq, ef, radii.data(), max_results, m.words, m.n_masks, m.of_query, np, r.ip,
+                                     r.dp, r.cp));
+    }
+    return py::make_tuple(counts, r.ids, r.d, r.c);
+  }
+  void range_search_device(uintptr_t q, uint64_t nq, uint32_t ef, uintptr_t radii, uint32_t max_results,
+                           uintptr_t allow_words, uint32_t n_masks, uintptr_t mask_of_query, uintptr_t counts, uintptr_t ids,
+                           uintptr_t dists, uintptr_t counters, uintptr_t stream) {
+    check(alaya_index_range_search_device(ix_, dptr<const float>(q), nq, ef, dptr<const float>(radii), max_results,
+                                          dptr<const uint32_t>(allow_words), n_masks, dptr<const uint32_t>(mask_of_query),
+                                          dptr<uint32_t>(counts), dptr<uint32_t>(ids), dptr<float>(dists),
+                                          dptr<uint32_t>(counters), dptr<void>(stream)));
+  }
   // the same over the index's SQ8 codes, reranked on the f32 rows (alaya_index_filtered_search_sq8); pool: the
   // candidate pool's capacity, 0 = min(224, max(k, ef)); rerank_queries: None = queries
   py::tuple filtered_search_sq8(F32Array q, uint32_t k, uint32_t ef, U32Array allow_words, py::object mask_of_query,
@@ -1282,6 +1362,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("filtered_search", &PyIndexInterface::filtered_search, py::arg("queries"), py::arg("topk"), py::arg("ef"),
            py::arg("allow_words"), py::arg("mask_of_query") = py::none(), py::arg("pool") = 0,
            py::arg("through") = false)
+      .def("range_search", &PyIndexInterface::range_search, py::arg("queries"), py::arg("ef"), py::arg("radius"),
+           py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none())
       .def("last_through", &PyIndexInterface::last_through)
       .def("get_data_dim", &PyIndexInterface::get_data_dim)
       .def("get_data_num", &PyIndexInterface::get_data_num)
@@ -1330,6 +1412,9 @@ PYBIND11_MODULE(_alayalitepy, m) {
            py::arg("allow_words"), py::arg("mask_of_query") = py::none(), py::arg("pool") = 0,
            py::arg("rerank_queries") = py::none())
       .def("filtered_search_sq8_device", &DeviceIndex::filtered_search_sq8_device)
+      .def("range_search", &DeviceIndex::range_search, py::arg("queries"), py::arg("ef"), py::arg("radius"),
+           py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none())
+      .def("range_search_device", &DeviceIndex::range_search_device)
       .def("shard_search_device", &DeviceIndex::shard_search_device)
       .def("distances", &DeviceIndex::distances)
       .def("set_hash_log2", &DeviceIndex::set_hash_log2)

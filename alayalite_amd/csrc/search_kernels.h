@@ -140,6 +140,21 @@ struct HopParams {
   uint32_t *n_through;  // nq: rows stepped through per query (nullable)
 };
 
+// The range search's own arguments (range_search_kernel's third argument; range_sort_kernel's only
+// one).  All pointers are device pointers.  The search kernel appends query i's hits, in arrival order,
+// to slots [i * cap, i * cap + min(counts[i], cap)) of append_ids / append_dists and leaves the other
+// slots unwritten; the sort kernel reads those and writes out_ids / out_dists.
+struct RangeParams {
+  const float *radii;    // nq: a hit has d <= radii[i]
+  uint32_t cap;          // stored rows per query (1 .. kRangeMaxCap)
+  uint32_t *append_ids;  // nq x cap
+  float *append_dists;   // nq x cap
+  uint32_t *counts;      // nq: hits per query, not capped
+  uint32_t *out_ids;     // nq x cap: the stored rows by (distance, id), then (kEmpty, FLT_MAX)
+  float *out_dists;      // nq x cap
+};
+constexpr uint32_t kRangeMaxCap = 4096;
+
 // PyIndex::rerank inputs (python/include/index.hpp:450-488).  Per query the kernel rescores
 // search_ids[0 .. n_take) (row stride n_src; kEmpty entries are skipped) plus `zeros` entries of id 0
 // -- the reference's res_pool slots [k, ef) that batch_search leaves zero (index.hpp:301) -- and
@@ -211,6 +226,14 @@ hipError_t launch_filtered_search(const SearchParams &p, const FilterParams &f, 
 hipError_t filtered_hop_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);
 hipError_t launch_filtered_hop_search(const SearchParams &p, const FilterParams &f, const HopParams &h, int grid, int waves,
                                       size_t lds, hipStream_t stream);
+// Range search (range_search_kernel; f32 rows): p is planned as the plain (mode 0) search of the shape,
+// with no result pool (p.k = 0: the kernel writes no result rows, only r.counts, the append buffers and
+// p.out_counters); f.allow == nullptr = no mask.  launch_range_sort (range_sort_kernel) then orders
+// every query's stored rows: one workgroup per query, 8 bytes of LDS per slot of the cap's power of two.
+hipError_t range_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);
+hipError_t launch_range_search(const SearchParams &p, const FilterParams &f, const RangeParams &r, int grid, int waves,
+                               size_t lds, hipStream_t stream);
+hipError_t launch_range_sort(const RangeParams &r, uint64_t nq, hipStream_t stream);
 // Filtered search of SQ8 codes (filtered_sq8_search_kernel): f.k = p.k = m, the candidate pool's capacity
 // (filter_result_lds_bytes(m) at the end of p.wave_lds); p is planned as the plain (mode 0) SQ8 search of
 // the shape and p.out_ids receives nq x m candidate ids, kEmpty in empty slots, for launch_rerank.

@@ -2192,4 +2192,212 @@ hipError_t filtered_hop_search_occupancy(uint32_t dim, bool generic, bool ip, in
                                                       lds);
 }
 
+// --------------------------------------------------------------------------------------------
+// Range search: the filtered search's traversal -- hnsw_search_kernel's plain searcher, f32 rows -- with
+// the result pool replaced by an append list cut at a radius.  Every (id, distance) the traversal hands
+// to pool.insert, in that order, whose row is valid, allowed by the query's mask (f.allow == nullptr: no
+// mask) and has d <= radius is a hit.  The wave counts every hit and stores the first r.cap of them, in
+// arrival order, in the query's region of the global append buffers; range_sort_kernel orders them.  The
+// traversal pool, the visited set, every pop and the four counters are those of the unfiltered search at
+// the same ef.  No LDS beyond the plain searcher's; p.k = 0, so query_end writes the counters only.
+// --------------------------------------------------------------------------------------------
+namespace {
+
+// The hits among the lanes with ok, appended in lane order behind the query's `count` earlier ones: one
+// ballot, each lane's slot from the popcount of the hits below it, stores while the slot is below the cap.
+__device__ __forceinline__ void range_offer(uint32_t &count, const RangeParams &r, uint64_t region, float radius, bool ok,
+                                            uint32_t id, float d) {
+  const bool hit = ok && d <= radius;
+  const uint64_t hm = ballot(hit);
+  if (hm == 0ull) return;
+  const uint32_t at = count + static_cast<uint32_t>(__popcll(hm & ((1ull << lane_id()) - 1ull)));
+  if (hit && at < r.cap) {
+    r.append_ids[region + at] = id;
+    r.append_dists[region + at] = d;
+  }
+  count += static_cast<uint32_t>(__popcll(hm));
+}
+
+template <bool kIP, int kChunks>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(search_min_waves<kChunks, 0, 0>() ? search_min_waves<kChunks, 0, 0>() : 1, 8)))
+    range_search_kernel(SearchParams p, FilterParams f, RangeParams r) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int kSpace = 0;
+  const int lane = lane_id();
+  const int wave = static_cast<int>(threadIdx.x >> 6);
+  const int W = static_cast<int>(blockDim.x >> 6);
+  const Lds L = carve_lds<kSpace>(p, smem, wave);
+  const uint64_t bit_words = (p.n + 31) / 32;
+  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * W + wave;
+  uint32_t *slot_bits = p.overflow_bits + slot * bit_words;
+  uint32_t *slot_dirty = p.dirty_words + slot * p.dirty_cap;
+  constexpr bool kRegMerge = kChunks > 0 && kChunks <= 8;  // as the plain kernel's traversal merge
+  const bool masked = f.allow != nullptr;                  // (uniform over the launch)
+
+  for (;;) {
+    uint32_t qi = 0;
+    if (lane == 0) qi = atomicAdd(p.work_counter, 1u);
+    qi = read_lane(qi, 0);
+    if (qi >= p.nq) break;
+    const uint32_t *mask =
+        masked ? f.allow + static_cast<uint64_t>(f.mask_of_query != nullptr ? f.mask_of_query[qi] : 0u) * f.mask_words
+               : nullptr;
+    const float radius = r.radii[qi];
+    const uint64_t region = static_cast<uint64_t>(qi) * r.cap;
+    uint32_t count = 0;  // the query's hits so far (wave-uniform)
+    Visited vs;
+    PoolState ps;
+    uint32_t n_dist = 0, n_expand = 0, n_dist_up = 0, n_hops_up = 0;
+    query_begin<kIP, kChunks, kSpace>(p, L, qi, slot_bits, slot_dirty, nullptr, vs, ps, n_dist_up, n_hops_up,
+                                      [&](bool has, uint32_t id, float d) {
+                                        bool ok = has;
+                                        if (has) {
+                                          if (masked) ok = ((mask[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                          if (p.valid != nullptr) ok = ok && ((p.valid[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                        }
+                                        range_offer(count, r, region, radius, ok, id, d);
+                                      });
+
+    // ---- best-first expansion: the plain searcher's loop ------------------------------------
+    uint32_t pred = kEmpty, pred_v = kEmpty;  // adjacency prefetch of the predicted next pop
+    while (ps.cur < ps.size) {
+      const uint32_t u = pool_pop(ps, L);
+      ++n_expand;
+      uint32_t v = u == pred ? pred_v : adjacency_row(p, static_cast<int>(p.R), u);
+      const int cnt = adjacency_count(static_cast<int>(p.R), v);
+      bool act = lane < cnt;
+      if (p.dedup_edges) {  // graphs with repeated ids in a row: keep the first occurrence only
+        for (int j = 0; j < cnt; ++j) {
+          const uint32_t vj = read_lane(v, j);
+          if (j < lane && vj == v) act = false;
+        }
+      }
+      if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin(vs);
+      const bool fresh = visit(vs, v, act);
+      const uint64_t fm = ballot(fresh);
+      const int nf = __popcll(fm);
+      pred = ps.cur < ps.size ? (L.pi[ps.cur] & kIdMask) : kEmpty;
+      if (pred != kEmpty) pred_v = adjacency_row(p, static_cast<int>(p.R), pred, pred_v);
+      if (nf == 0) continue;
+      // compact fresh ids in adjacency order
+      if (fresh) L.cid[__popcll(fm & ((1ull << lane) - 1ull))] = v;
+      wave_sync();
+      // each candidate's allow word (and validity word) goes out ahead of the row gather, as in the
+      // filtered kernel
+      const bool has = lane < nf;
+      const uint32_t cid = has ? L.cid[lane] : 0u;
+      uint32_t aw = 0xffffffffu, vw = 0xffffffffu;
+      if (has) {
+        if (masked) aw = mask[cid >> 5];
+        if (p.valid != nullptr) vw = p.valid[cid >> 5];
+      }
+      space_distances<kIP, kChunks, kSpace>(p, L, L.cid, nf, L.cd);
+      n_dist += nf;
+      const float cd = has ? L.cd[lane] : 0.f;
+      wave_sync();
+      pool_merge<kRegMerge>(ps, L, has, cid, cd, [&](uint32_t nx) {
+        if (nx != pred) {
+          pred = nx;
+          pred_v = adjacency_row(p, static_cast<int>(p.R), nx, pred_v);
+        }
+      });
+      range_offer(count, r, region, radius, has && (((aw & vw) >> (cid & 31)) & 1u) != 0u, cid, cd);
+    }
+
+    query_end(p, L, ps, qi, n_dist, n_expand, n_dist_up, n_hops_up);  // p.k = 0: the four counters
+    if (lane == 0) r.counts[qi] = count;
+    visit_end(vs);
+    wave_sync();
+  }
+}
+
+__device__ __forceinline__ uint32_t range_pow2(uint32_t n) {
+  uint32_t p2 = 1;
+  while (p2 < n) p2 <<= 1;
+  return p2;
+}
+
+// One workgroup per query: the query's min(count, cap) stored rows into LDS, padded to a power of two
+// with (FLT_MAX, kEmpty), a bitonic sort on (distance, id) under float comparison -- the float itself is
+// the key, so -0.0 ties with +0.0, the id decides, and the measured bits come back out -- then the
+// sorted rows and the empty tail to the outputs.  Hits are never NaN (d <= radius held), and a pad sorts
+// behind every hit: no row has id kEmpty.
+__global__ void __launch_bounds__(256) range_sort_kernel(RangeParams r) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float *sd = reinterpret_cast<float *>(smem);
+  uint32_t *si = reinterpret_cast<uint32_t *>(smem) + range_pow2(r.cap);
+  const uint64_t region = static_cast<uint64_t>(blockIdx.x) * r.cap;
+  const uint32_t n = min(r.counts[blockIdx.x], r.cap);
+  const uint32_t n2 = range_pow2(n);  // <= range_pow2(r.cap): the launch's LDS
+  for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) {
+    sd[i] = i < n ? r.append_dists[region + i] : FLT_MAX;
+    si[i] = i < n ? r.append_ids[region + i] : kEmpty;
+  }
+  __syncthreads();
+  for (uint32_t k = 2; k <= n2; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) {
+        const uint32_t o = i ^ j;
+        if (o > i) {
+          const float da = sd[i], db = sd[o];
+          const uint32_t ia = si[i], ib = si[o];
+          const bool b_first = db < da || (db == da && ib < ia);
+          const bool a_first = da < db || (da == db && ia < ib);
+          if ((i & k) == 0u ? b_first : a_first) {
+            sd[i] = db;
+            sd[o] = da;
+            si[i] = ib;
+            si[o] = ia;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (uint32_t i = threadIdx.x; i < r.cap; i += blockDim.x) {
+    r.out_ids[region + i] = i < n ? si[i] : kEmpty;
+    r.out_dists[region + i] = i < n ? sd[i] : FLT_MAX;
+  }
+}
+}  // namespace
+
+// The range kernels: the filtered kernels' set.
+template <int... kChunks>
+static const void *range_symbol_of(int chunks, bool ip) {
+  const void *sym = nullptr;
+  ((chunks == kChunks ? (sym = ip ? reinterpret_cast<const void *>(&range_search_kernel<true, kChunks>)
+                                  : reinterpret_cast<const void *>(&range_search_kernel<false, kChunks>),
+                         0)
+                      : 0),
+   ...);
+  return sym;
+}
+
+static const void *range_kernel_symbol(uint32_t dim, bool generic, bool ip) {
+  const void *sym = range_symbol_of<4, 8, 16, 24, 30, 32>(search_chunks(dim, generic), ip);
+  return sym != nullptr ? sym : range_symbol_of<0>(0, ip);
+}
+
+hipError_t launch_range_search(const SearchParams &p, const FilterParams &f, const RangeParams &r, int grid, int waves,
+                               size_t lds, hipStream_t stream) {
+  SearchParams arg = p;
+  FilterParams farg = f;
+  RangeParams rarg = r;
+  void *args[] = {&arg, &farg, &rarg};
+  return hipLaunchKernel(range_kernel_symbol(p.dim, p.generic, p.ip), dim3(grid), dim3(64 * waves), args, lds, stream);
+}
+
+hipError_t range_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, range_kernel_symbol(dim, generic, ip), 64 * waves, lds);
+}
+
+hipError_t launch_range_sort(const RangeParams &r, uint64_t nq, hipStream_t stream) {
+  if (nq == 0) return hipSuccess;
+  uint32_t p2 = 1;
+  while (p2 < r.cap) p2 <<= 1;
+  hipLaunchKernelGGL(range_sort_kernel, dim3(static_cast<uint32_t>(nq)), dim3(256), static_cast<size_t>(p2) * 8, stream, r);
+  return hipGetLastError();
+}
+
 }  // namespace alaya_amd

@@ -10,7 +10,7 @@ import numpy as np
 from ._native import PyIndexInterface as _PyIndexInterface
 from .common import VectorLike, VectorLikeBatch, _assert
 from .schema import IndexParams, load_schema
-from .utils import pack_allow
+from .utils import pack_allow, range_csr
 
 
 class Index:
@@ -102,6 +102,22 @@ class Index:
                 "query dimension must match the dimension of the vectors used to fit the index."
                 f"fit data dimension: {self.__dim}, query dimension: {got}")
 
+    def _masks(self, allow, groups, nq: int):
+        """``allow`` and ``groups`` of the masked searches, checked, as (mask words, uint32 groups or None)."""
+        allow = np.asarray(allow)
+        _assert(allow.ndim in (1, 2), "allow must have shape (n,) or (G, n)")
+        words = pack_allow(allow, self.get_data_num())
+        if groups is None:
+            _assert(words.shape[0] == 1, "groups is required with more than one mask")
+        else:
+            groups = np.asarray(groups)
+            _assert(groups.shape == (nq,), "groups must have shape (nq,)")
+            _assert(np.issubdtype(groups.dtype, np.integer), "groups must be integers")
+            _assert(groups.size == 0 or (groups.min() >= 0 and groups.max() < words.shape[0]),
+                    "groups must be below the number of masks")
+            groups = np.ascontiguousarray(groups, np.uint32)
+        return words, groups
+
     def search(self, query: VectorLike, topk: int, ef_search: int = 100) -> VectorLike:
         self._check_queries(query, 1, "query")
         return self.__index.search(query, topk, ef_search)
@@ -146,18 +162,7 @@ class Index:
         if allow is None:
             _assert(groups is None, "groups needs allow")
             return self.__index.exact_search(queries, topk)
-        allow = np.asarray(allow)
-        _assert(allow.ndim in (1, 2), "allow must have shape (n,) or (G, n)")
-        words = pack_allow(allow, self.get_data_num())
-        if groups is None:
-            _assert(words.shape[0] == 1, "groups is required with more than one mask")
-        else:
-            groups = np.asarray(groups)
-            _assert(groups.shape == (queries.shape[0],), "groups must have shape (nq,)")
-            _assert(np.issubdtype(groups.dtype, np.integer), "groups must be integers")
-            _assert(groups.size == 0 or (groups.min() >= 0 and groups.max() < words.shape[0]),
-                    "groups must be below the number of masks")
-            groups = np.ascontiguousarray(groups, np.uint32)
+        words, groups = self._masks(allow, groups, queries.shape[0])
         return self.__index.exact_search_filtered(queries, topk, words, groups)
 
     def get_data_num(self) -> int:
@@ -205,19 +210,56 @@ class Index:
             _assert((self.__params.quantization_type or "none").lower() == "sq8", "rerank_pool applies to SQ8 indexes only")
             pool = int(rerank_pool)
             _assert(topk <= pool <= 224, "rerank_pool must be in topk..224")
-        allow = np.asarray(allow)
-        _assert(allow.ndim in (1, 2), "allow must have shape (n,) or (G, n)")
-        words = pack_allow(allow, self.get_data_num())
-        if groups is None:
-            _assert(words.shape[0] == 1, "groups is required with more than one mask")
-        else:
-            groups = np.asarray(groups)
-            _assert(groups.shape == (queries.shape[0],), "groups must have shape (nq,)")
-            _assert(np.issubdtype(groups.dtype, np.integer), "groups must be integers")
-            _assert(groups.size == 0 or (groups.min() >= 0 and groups.max() < words.shape[0]),
-                    "groups must be below the number of masks")
-            groups = np.ascontiguousarray(groups, np.uint32)
+        words, groups = self._masks(allow, groups, queries.shape[0])
         return self.__index.filtered_search(queries, topk, ef_search, words, groups, pool, through)
+
+    def range_search(self, queries: VectorLikeBatch, radius, ef_search: int = 100, max_results: int = 1024,
+                     allow=None, groups=None, _chunk=None):
+        """Every row within distance ``radius`` of each query, among the rows the graph traversal measures.
+        The traversal is ``batch_search``'s at ``ef_search``; the radius does not steer it.  Every distance it
+        computes for a valid row (and, with ``allow`` / ``groups`` as in ``filtered_search``, an allowed one)
+        that is ``<= radius`` is a hit -- all of them, not only the ``ef_search`` rows the traversal keeps.
+        The distance is the index's own: squared L2, ``-(q.b)`` for IP, the same on normalised rows and
+        queries for COS, so ``radius=-0.8`` on a COS index means cosine >= 0.8.  ``radius`` is a number or
+        an array of shape (nq,), not NaN.
+
+        Returns ``(lims, ids, dists, counts)``: ``lims`` is int64 of length nq + 1 and query i's rows are
+        ``ids[lims[i]:lims[i + 1]]`` (the index's id type) with ``dists`` beside them, ordered by
+        (distance, id).  ``counts[i]`` (uint32) is the number of hits, not capped, and
+        ``lims[i + 1] - lims[i] == min(counts[i], max_results)``.  ``counts[i] > max_results`` means the
+        list is truncated: it then holds the first ``max_results`` hits the traversal met, NOT the nearest
+        ones -- raise ``max_results`` (1..4096) or lower the radius.  A removed row is never returned.
+        float32 graph search only: an SQ8 index is refused."""
+        self._check_queries(queries, 2, "queries")
+        _assert((self.__params.quantization_type or "none").lower() != "sq8",
+                "range_search searches f32 indexes only: this index has SQ8 codes")
+        _assert(1 <= max_results <= 4096, "max_results must be in 1..4096")
+        _assert(ef_search >= 1, "ef_search must be >= 1")
+        nq = queries.shape[0]
+        radii = np.asarray(radius, np.float32)
+        _assert(radii.shape in ((), (nq,)), "radius must be a number or have shape (nq,)")
+        _assert(not np.isnan(radii).any(), "radius must not be NaN")
+        radii = np.ascontiguousarray(np.broadcast_to(radii, (nq,)))
+        words = None
+        if allow is None:
+            _assert(groups is None, "groups needs allow")
+        else:
+            words, groups = self._masks(allow, groups, nq)
+        # chunks of queries: at most 2^26 padded result slots per call
+        step = max(1, (1 << 26) // max_results) if _chunk is None else int(_chunk)
+        parts = []
+        for lo in range(0, nq, step):
+            hi = min(nq, lo + step)
+            counts, ids, dists, _ = self.__index.range_search(queries[lo:hi], ef_search, radii[lo:hi], max_results, words,
+                                                              None if groups is None else groups[lo:hi])
+            parts.append((counts,) + range_csr(counts, ids, dists, max_results)[1:])
+        if not parts:
+            return (np.zeros(1, np.int64), np.zeros(0, self.__params.id_type), np.zeros(0, np.float32),
+                    np.zeros(0, np.uint32))
+        counts = np.concatenate([p[0] for p in parts])
+        lims = np.zeros(nq + 1, np.int64)
+        np.cumsum(np.minimum(counts.astype(np.int64), max_results), out=lims[1:])
+        return lims, np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts]), counts
 
     def save(self, url) -> dict:
         os.makedirs(url, exist_ok=True)

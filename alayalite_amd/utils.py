@@ -6,7 +6,7 @@ import hashlib
 
 import numpy as np
 
-__all__ = ["load_fvecs", "load_ivecs", "calc_recall", "calc_gt", "calc_gt_device", "md5", "pack_allow"]
+__all__ = ["load_fvecs", "load_ivecs", "calc_recall", "calc_gt", "calc_gt_device", "md5", "pack_allow", "range_csr"]
 
 
 def _load_vecs(file_path, dtype):
@@ -98,6 +98,24 @@ def pack_allow(allow, n):
     bits[:, :n] = a != 0
     packed = np.packbits(bits, axis=1, bitorder="little")
     return np.ascontiguousarray(packed).view("<u4").astype(np.uint32, copy=False).reshape(a.shape[0], words)
+
+
+def range_csr(counts, ids, dists, max_results):
+    """The padded result of a ``range_search`` -- counts (nq,), ids and dists (nq, max_results) -- as the
+    CSR form ``Index.range_search`` returns: (lims, ids, dists) with lims int64 of length nq + 1 and
+    query i's rows at ``[lims[i]:lims[i + 1]]``, ``min(counts[i], max_results)`` of them, in the
+    padded form's order.  ``counts[i] > max_results`` marks a truncated list."""
+    counts = np.asarray(counts)
+    ids, dists = np.asarray(ids), np.asarray(dists)
+    nq = counts.shape[0]
+    if counts.ndim != 1 or ids.shape != (nq, max_results) or dists.shape != (nq, max_results):
+        raise ValueError(f"counts must have shape (nq,) and ids, dists (nq, {max_results}); "
+                         f"got {counts.shape}, {ids.shape}, {dists.shape}")
+    kept = np.minimum(counts.astype(np.int64), max_results)
+    lims = np.zeros(nq + 1, np.int64)
+    np.cumsum(kept, out=lims[1:])
+    take = np.arange(max_results)[None, :] < kept[:, None]
+    return lims, ids[take], dists[take]
 
 
 def md5(arr, chunk_size=1024 * 1024):

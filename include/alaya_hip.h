@@ -216,6 +216,38 @@ int alaya_index_filtered_search_sq8_device(alaya_index *ix, const float *d_queri
                                            const uint32_t *d_allow_words, uint32_t n_masks,
                                            const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists,
                                            uint32_t *d_counters, void *stream);
+/* Range search: every row the graph traversal measures within a radius of the query (f32 rows; an index with
+ * SQ8 codes is refused).  For query i with radius r_i = radii[i] and cap C = max_results, 1 <= C <= 4096:
+ *   1. Traversal: alaya_index_batch_search's at the same ef -- the same overlay descent, pool of capacity ef,
+ *      visited set and pops -- so the four counters are equal, as for alaya_index_filtered_search.  The radius
+ *      does not steer it: it neither stops early nor expands past what ef gives.
+ *   2. Hits: the subsequence, in arrival order, of the (id, d) the traversal hands to its pool (the entry offers
+ *      included) whose row is valid, is allowed by the query's mask when masks are given, and has d <= r_i as
+ *      an f32 comparison (inclusive).  A removed row never qualifies, whatever the radius.  d is the index's
+ *      distance: squared L2, or -(q.b) for IP and COS (a radius of -0.8 on normalised rows = cosine >= 0.8).
+ *   3. counts[i] = the number of hits, not capped.
+ *   4. The first min(counts[i], C) hits to arrive are stored and returned in row i of ids / dists (nq x C),
+ *      ordered by (distance, id) under float comparison -- -0.0 ties with +0.0 and the id decides -- with the
+ *      measured distance bits; the remaining slots hold (0xffffffff, FLT_MAX).
+ *   5. counts[i] > C means the list is truncated: the stored rows are the first C to arrive, NOT the C nearest.
+ *      A caller that needs them all raises max_results or lowers the radius.
+ *   6. A graph without overlay whose entry-point list repeats an id offers it twice, and it stays twice.
+ * allow_words / n_masks / mask_of_query as for alaya_index_filtered_search; allow_words == NULL with
+ * n_masks == 0 (and mask_of_query == NULL) means no mask.  counters (nullable): nq x 4.  max_results outside
+ * 1..4096, ef == 0, a NaN radius (host entry only) and a mask shape the filtered entries refuse are argument
+ * errors.  ALAYA_FILTER_GRID as for alaya_index_filtered_search.  Environment ALAYA_RANGE_SORT=0 (diagnostics,
+ * read per launch) runs the search stage alone, to time it: ids and dists are then left unwritten. */
+int alaya_index_range_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t ef, const float *radii,
+                             uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
+                             const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists,
+                             uint32_t *counters);
+/* Same on device buffers, asynchronous on `stream`: it never waits on the stream, so d_radii (nq floats) is not
+ * read here and a NaN radius simply matches nothing; the indices of d_mask_of_query are not checked.  The
+ * append list between the two kernels is the index's own scratch. */
+int alaya_index_range_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t ef,
+                                    const float *d_radii, uint32_t max_results, const uint32_t *d_allow_words,
+                                    uint32_t n_masks, const uint32_t *d_mask_of_query, uint32_t *d_counts,
+                                    uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream);
 /* ---- device graph construction (Index.fit on the MI355X) ------------------------------------
  * Replaces HNSWBuilder::build_graph (include/index/graph/hnsw/hnsw_builder.hpp:98-194) over hnswlib
  * add_point (include/index/graph/hnsw/hnswlib.hpp:652-751), from the index's own rows
