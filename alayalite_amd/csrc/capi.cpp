@@ -137,6 +137,7 @@ struct alaya_index {
   // range search: the append buffers of both entry points (nq x cap ids and distances, scratch between the search
   // launch and the sort), and the host entry's radii and counts
   DevBuf range_ids, range_d, range_radii, range_cnt;
+  DevBuf range_frontier, range_more;  // radius mode: nq x max_frontier frontier ids (scratch), the host entry's nq x 2 `more`
   // exact filtered scan (alaya_index_flat_search_filtered*): the current mask's id list (n words), the
   // compaction's block sums and count, the partial lists of one scan launch (capped, see
   // alaya_amd::flat_filtered_plan) and the queries ordered by mask
@@ -370,9 +371,9 @@ bool helpers_requested(const alaya_index *ix, const SearchParams &p, uint64_t nq
 
 // filter_k != 0: the filtered search -- its own kernel's registers, and a result pool of filter_k entries
 // in every wave's region (hop: the through search's kernel).  range: the range search -- its own kernel's
-// registers and no result pool.
+// registers and no result pool (more: its radius mode's kernel).
 uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchVariant &v, uint64_t nq, uint32_t ef,
-                      int W = 1, uint32_t filter_k = 0, bool hop = false, bool range = false) {
+                      int W = 1, uint32_t filter_k = 0, bool hop = false, bool range = false, bool more = false) {
   const uint32_t lbits = std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2)));
   const int mode = ix->visited_mode_override;  // 0 auto, 1 compact, 2 wide, 3 compact + short probes
   auto set_mode = [&](uint32_t l, bool compact) {
@@ -418,7 +419,8 @@ uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchV
   const bool stab = p.stab_log2 != 0;  // set by do_search (spill_table_log2)
   int vgpr_blocks = 0;
   const size_t probe_lds = shared + W * (wave_fixed + (stab ? 1024 : 4096));
-  hip_check(range ? alaya_amd::range_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
+  hip_check(more    ? alaya_amd::range_more_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
+            : range ? alaya_amd::range_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
             : !filter_k ? alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks)
             : hop ? alaya_amd::filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
             : p.sq8_order ? alaya_amd::filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, probe_lds, &vgpr_blocks)
@@ -769,11 +771,12 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
 //
 // range: the search stage of the range search (alaya_index_range_search*, range_search_kernel; f32 rows only) -- the
 // same plan without a result pool (k = 0, d_ids / d_dists unused) and with that kernel's occupancy; d_allow may be
-// null (no mask).  The kernel fills range->counts and the append buffers; the caller launches the sort.
+// null (no mask).  The kernel fills range->counts and the append buffers; the caller launches the sort.  more: the
+// radius mode (alaya_index_range_search_radius*, range_more_search_kernel) -- the same plan with that kernel's occupancy.
 void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef, const uint32_t *d_allow,
                         const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt,
                         hipStream_t stream, bool sq8 = false, bool hop = false, uint32_t *d_through = nullptr,
-                        const alaya_amd::RangeParams *range = nullptr) {
+                        const alaya_amd::RangeParams *range = nullptr, const alaya_amd::RangeMoreParams *more = nullptr) {
   using namespace alaya_amd;
   if (range && (sq8 || ix->has_sq8))
     throw ArgError("range search of an SQ8 index: alaya_index_range_search searches f32 rows only");
@@ -794,7 +797,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   const SearchVariant &plain = resolve_search_variant({ix->dim, p.ip, p.sq8_order, ix->generic, 0});
   int W = search_waves(p);
   while (W > 1 && static_cast<uint64_t>(W) > nq) W /= 2;
-  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k, hop, range != nullptr);
+  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k, hop, range != nullptr, more != nullptr);
   const size_t traversal_lds = search_wave_lds_bytes(ix->stride, ef, p.hash_log2, p.vis_rbits != kVisWide, p.sq8_order);
   p.wave_lds = static_cast<uint32_t>(traversal_lds + (range ? 0 : filter_result_lds_bytes(k)));
   FilterParams f{};
@@ -808,7 +811,8 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
     throw ArgError(range ? "range search: ef / dim too large for the LDS budget"
                          : "filtered search: k / ef / dim too large for the LDS budget");
   int per_cu = 0;
-  hip_check(range ? range_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
+  hip_check(more    ? range_more_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
+            : range ? range_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
             : sq8 ? filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, lds, &per_cu)
             : hop ? filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
                 : filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu),
@@ -823,7 +827,8 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   const uint64_t searchers = static_cast<uint64_t>(grid) * W;
   prepare_spill(ix, p, searchers, stream);
   record_launch(ix, p, grid, W, lds, per_cu, searchers, stream);  // (no scout, helpers or screen: p has none set)
-  hip_check(range ? launch_range_search(p, f, *range, grid, W, lds, stream)
+  hip_check(more    ? launch_range_more_search(p, f, *range, *more, grid, W, lds, stream)
+            : range ? launch_range_search(p, f, *range, grid, W, lds, stream)
             : sq8 ? launch_filtered_sq8_search(p, f, grid, W, lds, stream)
             : hop ? launch_filtered_hop_search(p, f, HopParams{d_through}, grid, W, lds, stream)
                   : launch_filtered_search(p, f, grid, W, lds, stream),
@@ -2317,9 +2322,18 @@ static void check_range_cap(uint32_t max_results) {
 // into the index's append buffers, then the sort into d_ids / d_dists.  The caller holds ix->mu.
 static void range_search_dev(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t ef, const float *d_radii,
                              uint32_t max_results, const uint32_t *d_allow, const uint32_t *d_mask_of_query,
-                             uint32_t *d_counts, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt, hipStream_t s) {
+                             uint32_t *d_counts, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt, hipStream_t s,
+                             uint32_t max_frontier = 0, uint32_t *d_more = nullptr) {
   check_range_cap(max_results);
+  const bool radius_mode = max_frontier != 0;  // (the radius entries refuse 0 themselves)
   if (ef == 0) throw ArgError("ef must be >= 1");
+  alaya_amd::RangeMoreParams m{};
+  if (radius_mode) {
+    ix->range_frontier.reserve(static_cast<size_t>(nq) * max_frontier * 4);
+    m.frontier_ids = ix->range_frontier.as<uint32_t>();
+    m.cap = max_frontier;
+    m.more = d_more;
+  }
   const size_t slots = static_cast<size_t>(nq) * max_results;
   ix->range_ids.reserve(slots * 4);
   ix->range_d.reserve(slots * 4);
@@ -2331,7 +2345,8 @@ static void range_search_dev(alaya_index *ix, const float *d_q, uint64_t nq, uin
   r.counts = d_counts;
   r.out_ids = d_ids;
   r.out_dists = d_dists;
-  do_filtered_search(ix, d_q, nq, 0, ef, d_allow, d_mask_of_query, nullptr, nullptr, d_cnt, s, false, false, nullptr, &r);
+  do_filtered_search(ix, d_q, nq, 0, ef, d_allow, d_mask_of_query, nullptr, nullptr, d_cnt, s, false, false, nullptr, &r,
+                     radius_mode ? &m : nullptr);
   if (nq == 0) return;
   // diagnostics (ALAYA_RANGE_SORT=0, include/alaya_hip.h): the search stage alone, to time it; ids / dists are
   // then left unwritten
@@ -2352,24 +2367,32 @@ static void check_range_masks(uint64_t nq, const uint32_t *allow_words, uint32_t
   check_masks("range search", nq, n_masks, mask_of_query, host_indices);
 }
 
-int alaya_index_range_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t ef, const float *d_radii,
-                                    uint32_t max_results, const uint32_t *d_allow_words, uint32_t n_masks,
-                                    const uint32_t *d_mask_of_query, uint32_t *d_counts, uint32_t *d_ids, float *d_dists,
-                                    uint32_t *d_counters, void *stream) {
+static void check_range_frontier(bool radius_mode, uint32_t max_frontier) {
+  if (radius_mode && (max_frontier == 0 || max_frontier > alaya_amd::kRangeMaxFrontier))
+    throw ArgError("range search: max_frontier must be in 1..16384");
+}
+
+// The device entries of both modes (radius_mode: alaya_index_range_search_radius_device, else max_frontier = 0).
+static int range_device_call(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t ef, const float *d_radii,
+                             uint32_t max_results, const uint32_t *d_allow_words, uint32_t n_masks,
+                             const uint32_t *d_mask_of_query, uint32_t *d_counts, uint32_t *d_ids, float *d_dists,
+                             uint32_t *d_counters, void *stream, bool radius_mode, uint32_t max_frontier, uint32_t *d_more) {
   return guarded_scratch(ix, [&] {
     if (!ix || (nq && (!d_queries || !d_radii || !d_counts || !d_ids || !d_dists))) throw ArgError("invalid arguments");
     check_range_masks(nq, d_allow_words, n_masks, d_mask_of_query, false);
+    check_range_frontier(radius_mode, max_frontier);
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     range_search_dev(ix, d_queries, nq, ef, d_radii, max_results, d_allow_words, d_mask_of_query, d_counts, d_ids, d_dists,
-                     d_counters, static_cast<hipStream_t>(stream));
+                     d_counters, static_cast<hipStream_t>(stream), max_frontier, d_more);
   });
 }
 
-int alaya_index_range_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t ef, const float *radii,
-                             uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
-                             const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists,
-                             uint32_t *counters) {
+// The host entries of both modes; more (radius mode, nullable): nq x 2.
+static int range_host_call(alaya_index *ix, const float *queries, uint64_t nq, uint32_t ef, const float *radii,
+                           uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
+                           const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists, uint32_t *counters,
+                           bool radius_mode, uint32_t max_frontier, uint32_t *more) {
   return guarded_scratch(ix, [&] {
     if (!ix || (nq && (!queries || !radii || !counts || !ids || !dists))) throw ArgError("invalid arguments");
     check_range_masks(nq, allow_words, n_masks, mask_of_query, true);
@@ -2378,9 +2401,10 @@ int alaya_index_range_search(alaya_index *ix, const float *queries, uint64_t nq,
     std::lock_guard<std::mutex> lk(ix->mu);
     set_device(ix);
     check_range_cap(max_results);  // (before the result buffers are sized by it)
+    check_range_frontier(radius_mode, max_frontier);
     if (nq == 0) {
       range_search_dev(ix, nullptr, 0, ef, nullptr, max_results, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       ix->stream);  // the index's own refusals
+                       ix->stream, max_frontier);  // the index's own refusals
       return;
     }
     const float *d_q = stage_queries(ix, queries, nq, max_results);
@@ -2388,14 +2412,50 @@ int alaya_index_range_search(alaya_index *ix, const float *queries, uint64_t nq,
     const uint32_t *d_groups = allow_words ? stage_mask_indices(ix, mask_of_query, nq) : nullptr;
     ix->range_radii.reserve(nq * 4);
     ix->range_cnt.reserve(nq * 4);
+    const bool more_out = radius_mode && more;
+    if (more_out) ix->range_more.reserve(nq * 8);
     hip_check(hipMemcpyAsync(ix->range_radii.ptr, radii, nq * 4, hipMemcpyHostToDevice, ix->stream), "upload radii");
     range_search_dev(ix, d_q, nq, ef, ix->range_radii.as<float>(), max_results, d_allow, d_groups,
                      ix->range_cnt.as<uint32_t>(), ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(),
-                     ix->cnt_buf.as<uint32_t>(), ix->stream);
+                     ix->cnt_buf.as<uint32_t>(), ix->stream, max_frontier, more_out ? ix->range_more.as<uint32_t>() : nullptr);
     fetch_results(ix, nq, max_results, ids, dists, counters);
     hip_check(hipMemcpyAsync(counts, ix->range_cnt.ptr, nq * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    if (more_out) hip_check(hipMemcpyAsync(more, ix->range_more.ptr, nq * 8, hipMemcpyDeviceToHost, ix->stream), "D2H");
     stream_sync(ix, "range search");
   });
+}
+
+int alaya_index_range_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t ef, const float *d_radii,
+                                    uint32_t max_results, const uint32_t *d_allow_words, uint32_t n_masks,
+                                    const uint32_t *d_mask_of_query, uint32_t *d_counts, uint32_t *d_ids, float *d_dists,
+                                    uint32_t *d_counters, void *stream) {
+  return range_device_call(ix, d_queries, nq, ef, d_radii, max_results, d_allow_words, n_masks, d_mask_of_query, d_counts,
+                           d_ids, d_dists, d_counters, stream, false, 0, nullptr);
+}
+
+int alaya_index_range_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t ef, const float *radii,
+                             uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
+                             const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists,
+                             uint32_t *counters) {
+  return range_host_call(ix, queries, nq, ef, radii, max_results, allow_words, n_masks, mask_of_query, counts, ids, dists,
+                         counters, false, 0, nullptr);
+}
+
+int alaya_index_range_search_radius_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t ef,
+                                           const float *d_radii, uint32_t max_results, const uint32_t *d_allow_words,
+                                           uint32_t n_masks, const uint32_t *d_mask_of_query, uint32_t *d_counts,
+                                           uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream,
+                                           uint32_t max_frontier, uint32_t *d_more) {
+  return range_device_call(ix, d_queries, nq, ef, d_radii, max_results, d_allow_words, n_masks, d_mask_of_query, d_counts,
+                           d_ids, d_dists, d_counters, stream, true, max_frontier, d_more);
+}
+
+int alaya_index_range_search_radius(alaya_index *ix, const float *queries, uint64_t nq, uint32_t ef, const float *radii,
+                                    uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
+                                    const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists,
+                                    uint32_t *counters, uint32_t max_frontier, uint32_t *more) {
+  return range_host_call(ix, queries, nq, ef, radii, max_results, allow_words, n_masks, mask_of_query, counts, ids, dists,
+                         counters, true, max_frontier, more);
 }
 
 int alaya_index_profile_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k,

@@ -407,9 +407,11 @@ class PyIndexInterface : public LaunchControls {
   // `radius` (a number or one per query) of the query (alaya_index_range_search; f32 indexes only).  Returns
   // (counts[nq], ids[nq, max_results], dists[nq, max_results], counters[nq, 4]): row i holds its first
   // min(counts[i], max_results) hits to arrive, by (distance, id), then empty slots as exact_search's.
-  // allow_words / mask_of_query as for filtered_search, or None for no mask.
+  // allow_words / mask_of_query as for filtered_search, or None for no mask.  radius_mode: the traversal then
+  // keeps expanding the in-radius rows it measured (alaya_index_range_search_radius; max_frontier 1..16384 of them
+  // per query), and last_range_more() holds (frontier, more_dist) per query.
   py::object range_search(py::array queries, uint32_t ef, py::object radius, uint32_t max_results, py::object allow_words,
-                          py::object mask_of_query) {
+                          py::object mask_of_query, bool radius_mode, uint32_t max_frontier, bool more_append) {
     if (!graph_) throw std::runtime_error("Index is not init yet");
     if (params_.quantization_type_ != QuantizationType::NONE)
       throw py::value_error("range_search searches f32 indexes only (no SQ8 codes)");
@@ -419,13 +421,25 @@ class PyIndexInterface : public LaunchControls {
     const Masks m = parse_range_masks(allow_words, words, mask_of_query, n_, nq);
     const std::vector<float> radii = parse_radii(radius, nq);
     if (max_results == 0 || max_results > 4096) throw py::value_error("max_results must be in 1..4096");
+    if (radius_mode && (max_frontier == 0 || max_frontier > 16384))
+      throw py::value_error("max_frontier must be in 1..16384");
     std::vector<uint32_t> ids32(nq * max_results);
     py::array_t<float> dists = out2d<float>(nq, max_results);
     py::array_t<uint32_t> counts(static_cast<py::ssize_t>(nq));
     uint32_t *cp = counts.mutable_data();
     float *dp = dists.mutable_data();
     last_counters_.assign(nq * 4, 0);
-    {
+    if (radius_mode) {
+      // more_append: a later chunk of one Index.range_search call, whose rows go behind the earlier chunks'
+      const size_t at = more_append ? last_range_more_.size() : 0;
+      last_range_more_.resize(at);
+      last_range_more_.resize(at + nq * 2, 0);
+      uint32_t *mp = last_range_more_.data() + at;
+      py::gil_scoped_release nogil;
+      check(alaya_index_range_search_radius(ix_, static_cast<const float *>(q.data()), nq, ef, radii.data(), max_results,
+                                            m.words, m.n_masks, m.of_query, cp, ids32.data(), dp, last_counters_.data(),
+                                            max_frontier, mp));
+    } else {
       py::gil_scoped_release nogil;
       check(alaya_index_range_search(ix_, static_cast<const float *>(q.data()), nq, ef, radii.data(), max_results, m.words,
                                      m.n_masks, m.of_query, cp, ids32.data(), dp, last_counters_.data()));
@@ -585,6 +599,12 @@ class PyIndexInterface : public LaunchControls {
 
   // --- extra (not in the reference binding): device counters of the last search ---
   // rows stepped through per query of the last filtered_search(..., through=True); empty after any other
+  // (frontier, more_dist) per query of the last radius-mode range_search: shape (nq, 2)
+  py::array last_range_more() const {
+    py::array_t<uint32_t> out = out2d<uint32_t>(last_range_more_.size() / 2, 2);
+    if (!last_range_more_.empty()) std::memcpy(out.mutable_data(), last_range_more_.data(), last_range_more_.size() * 4);
+    return out;
+  }
   py::array last_through() const {
     py::array_t<uint32_t> out(static_cast<py::ssize_t>(last_through_.size()));
     if (!last_through_.empty()) std::memcpy(out.mutable_data(), last_through_.data(), last_through_.size() * 4);
@@ -896,6 +916,7 @@ class PyIndexInterface : public LaunchControls {
   bool graph_dirty_ = false;       // graph_ predates inserts (sync_graph refreshes it)
   std::vector<uint32_t> last_counters_;
   std::vector<uint32_t> last_through_;
+  std::vector<uint32_t> last_range_more_;
   int rerank_mode_ = 1;
   std::vector<float> raw_queries_;   // SQ8 + COS: the un-normalised queries the SQ8 search encodes
   std::vector<uint8_t> sq_codes_;
@@ -1113,6 +1134,38 @@ class DeviceIndex : public LaunchControls {
                                      r.dp, r.cp));
     }
     return py::make_tuple(counts, r.ids, r.d, r.c);
+  }
+  // the radius mode (alaya_index_range_search_radius): the same and more[nq, 2] = (frontier, more_dist)
+  py::tuple range_search_radius(F32Array q, uint32_t ef, py::object radius, uint32_t max_results, uint32_t max_frontier,
+                                py::object allow_words, py::object mask_of_query) {
+    const uint64_t nq = q.shape(0);
+    U32Array words;
+    const Masks m = parse_range_masks(allow_words, words, mask_of_query, rows(), nq);
+    const std::vector<float> radii = parse_radii(radius, nq);
+    if (max_results == 0 || max_results > 4096) throw py::value_error("max_results must be in 1..4096");
+    if (max_frontier == 0 || max_frontier > 16384) throw py::value_error("max_frontier must be in 1..16384");
+    Results r(nq, max_results);
+    py::array_t<uint32_t> counts(static_cast<py::ssize_t>(nq));
+    py::array_t<uint32_t> more = out2d<uint32_t>(nq, 2);
+    uint32_t *np = counts.mutable_data();
+    uint32_t *mp = more.mutable_data();
+    const float *qp = q.data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_range_search_radius(ix_, qp, nq, ef, radii.data(), max_results, m.words, m.n_masks, m.of_query, np,
+                                            r.ip, r.dp, r.cp, max_frontier, mp));
+    }
+    return py::make_tuple(counts, r.ids, r.d, r.c, more);
+  }
+  void range_search_radius_device(uintptr_t q, uint64_t nq, uint32_t ef, uintptr_t radii, uint32_t max_results,
+                                  uintptr_t allow_words, uint32_t n_masks, uintptr_t mask_of_query, uintptr_t counts,
+                                  uintptr_t ids, uintptr_t dists, uintptr_t counters, uintptr_t stream, uint32_t max_frontier,
+                                  uintptr_t more) {
+    check(alaya_index_range_search_radius_device(ix_, dptr<const float>(q), nq, ef, dptr<const float>(radii), max_results,
+                                                 dptr<const uint32_t>(allow_words), n_masks,
+                                                 dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(counts),
+                                                 dptr<uint32_t>(ids), dptr<float>(dists), dptr<uint32_t>(counters),
+                                                 dptr<void>(stream), max_frontier, dptr<uint32_t>(more)));
   }
   void range_search_device(uintptr_t q, uint64_t nq, uint32_t ef, uintptr_t radii, uint32_t max_results,
                            uintptr_t allow_words, uint32_t n_masks, uintptr_t mask_of_query, uintptr_t counts, uintptr_t ids,
@@ -1363,7 +1416,9 @@ PYBIND11_MODULE(_alayalitepy, m) {
            py::arg("allow_words"), py::arg("mask_of_query") = py::none(), py::arg("pool") = 0,
            py::arg("through") = false)
       .def("range_search", &PyIndexInterface::range_search, py::arg("queries"), py::arg("ef"), py::arg("radius"),
-           py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none())
+           py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none(),
+           py::arg("radius_mode") = false, py::arg("max_frontier") = 4096u, py::arg("more_append") = false)
+      .def("last_range_more", &PyIndexInterface::last_range_more)
       .def("last_through", &PyIndexInterface::last_through)
       .def("get_data_dim", &PyIndexInterface::get_data_dim)
       .def("get_data_num", &PyIndexInterface::get_data_num)
@@ -1415,6 +1470,10 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("range_search", &DeviceIndex::range_search, py::arg("queries"), py::arg("ef"), py::arg("radius"),
            py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none())
       .def("range_search_device", &DeviceIndex::range_search_device)
+      .def("range_search_radius", &DeviceIndex::range_search_radius, py::arg("queries"), py::arg("ef"), py::arg("radius"),
+           py::arg("max_results"), py::arg("max_frontier") = 4096u, py::arg("allow_words") = py::none(),
+           py::arg("mask_of_query") = py::none())
+      .def("range_search_radius_device", &DeviceIndex::range_search_radius_device)
       .def("shard_search_device", &DeviceIndex::shard_search_device)
       .def("distances", &DeviceIndex::distances)
       .def("set_hash_log2", &DeviceIndex::set_hash_log2)

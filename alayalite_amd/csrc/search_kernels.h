@@ -155,6 +155,16 @@ struct RangeParams {
 };
 constexpr uint32_t kRangeMaxCap = 4096;
 
+// What the radius-mode range search (range_more_search_kernel) takes beyond range_search_kernel's
+// arguments: its fourth argument.  The kernel stores the first min(frontier count, cap) rows that join
+// query i's frontier in slots [i * cap, ...) of frontier_ids, and reads them back itself.
+struct RangeMoreParams {
+  uint32_t *frontier_ids;  // nq x cap
+  uint32_t cap;            // stored frontier rows per query (1 .. kRangeMaxFrontier)
+  uint32_t *more;          // nq x 2 (rows that joined the frontier, not capped; distances of phase 2), nullable
+};
+constexpr uint32_t kRangeMaxFrontier = 16384;
+
 // PyIndex::rerank inputs (python/include/index.hpp:450-488).  Per query the kernel rescores
 // search_ids[0 .. n_take) (row stride n_src; kEmpty entries are skipped) plus `zeros` entries of id 0
 // -- the reference's res_pool slots [k, ef) that batch_search leaves zero (index.hpp:301) -- and
@@ -234,6 +244,11 @@ hipError_t range_search_occupancy(uint32_t dim, bool generic, bool ip, int waves
 hipError_t launch_range_search(const SearchParams &p, const FilterParams &f, const RangeParams &r, int grid, int waves,
                                size_t lds, hipStream_t stream);
 hipError_t launch_range_sort(const RangeParams &r, uint64_t nq, hipStream_t stream);
+// The radius-mode range search (range_more_search_kernel): range_search_kernel's plan and arguments, its own
+// kernel's resident workgroups per CU, and its launch; launch_range_sort follows as above.
+hipError_t range_more_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);
+hipError_t launch_range_more_search(const SearchParams &p, const FilterParams &f, const RangeParams &r,
+                                    const RangeMoreParams &m, int grid, int waves, size_t lds, hipStream_t stream);
 // Filtered search of SQ8 codes (filtered_sq8_search_kernel): f.k = p.k = m, the candidate pool's capacity
 // (filter_result_lds_bytes(m) at the end of p.wave_lds); p is planned as the plain (mode 0) SQ8 search of
 // the shape and p.out_ids receives nq x m candidate ids, kEmpty in empty slots, for launch_rerank.

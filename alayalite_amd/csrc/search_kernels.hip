@@ -2312,6 +2312,193 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// --------------------------------------------------------------------------------------------
+// Range search, radius mode: range_search_kernel's traversal (phase 1, pop for pop), then a flood fill of
+// the in-radius region it reached (phase 2).  Every (id, d) either phase measures whose row is valid and
+// has d <= radius joins the query's frontier, in arrival order, whatever the allow mask says: the first
+// m.cap of them are stored in the query's region of the global frontier buffer.  When the traversal pool
+// has no unchecked entry left the stored frontier rows are expanded in that order: visit, distances,
+// offers -- hits to the append list by phase 1's rule, in-radius rows to the frontier -- and nothing goes
+// into the pool, so there is no merge.  The wave reads the frontier back 64 entries at a time, lane j
+// taking entry cursor + j, with plain loads through the pointer it stored them by; the next row to
+// expand is known exactly, so its adjacency row is issued before the distance pass.
+// --------------------------------------------------------------------------------------------
+// The in-radius rows among the lanes with `valid` join the frontier behind its `fcount` earlier ones, and
+// the allowed ones among them the append list, as range_offer.  Without a mask the frontier's ballot is
+// the hit ballot.
+__device__ __forceinline__ void range_more_offer(uint32_t &count, uint32_t &fcount, const RangeParams &r,
+                                                 const RangeMoreParams &m, uint64_t region, uint32_t *fr, float radius,
+                                                 bool masked, bool valid, bool allowed, uint32_t id, float d) {
+  const bool in = valid && d <= radius;
+  const uint64_t im = ballot(in);
+  if (im == 0ull) return;
+  const uint64_t below = (1ull << lane_id()) - 1ull;
+  const uint32_t fat = fcount + static_cast<uint32_t>(__popcll(im & below));
+  if (in && fat < m.cap) fr[fat] = id;
+  fcount += static_cast<uint32_t>(__popcll(im));
+  bool hit = in;
+  uint64_t hm = im;
+  if (masked) {
+    hit = in && allowed;
+    hm = ballot(hit);
+    if (hm == 0ull) return;
+  }
+  const uint32_t at = count + static_cast<uint32_t>(__popcll(hm & below));
+  if (hit && at < r.cap) {
+    r.append_ids[region + at] = id;
+    r.append_dists[region + at] = d;
+  }
+  count += static_cast<uint32_t>(__popcll(hm));
+}
+
+template <bool kIP, int kChunks>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(search_min_waves<kChunks, 0, 0>() ? search_min_waves<kChunks, 0, 0>() : 1, 8)))
+    range_more_search_kernel(SearchParams p, FilterParams f, RangeParams r, RangeMoreParams m) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int kSpace = 0;
+  const int lane = lane_id();
+  const int wave = static_cast<int>(threadIdx.x >> 6);
+  const int W = static_cast<int>(blockDim.x >> 6);
+  const Lds L = carve_lds<kSpace>(p, smem, wave);
+  const uint64_t bit_words = (p.n + 31) / 32;
+  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * W + wave;
+  uint32_t *slot_bits = p.overflow_bits + slot * bit_words;
+  uint32_t *slot_dirty = p.dirty_words + slot * p.dirty_cap;
+  constexpr bool kRegMerge = kChunks > 0 && kChunks <= 8;  // as the plain kernel's traversal merge
+  const bool masked = f.allow != nullptr;                  // (uniform over the launch)
+  const int R = static_cast<int>(p.R);
+
+  for (;;) {
+    uint32_t qi = 0;
+    if (lane == 0) qi = atomicAdd(p.work_counter, 1u);
+    qi = read_lane(qi, 0);
+    if (qi >= p.nq) break;
+    const uint32_t *mask =
+        masked ? f.allow + static_cast<uint64_t>(f.mask_of_query != nullptr ? f.mask_of_query[qi] : 0u) * f.mask_words
+               : nullptr;
+    const float radius = r.radii[qi];
+    const uint64_t region = static_cast<uint64_t>(qi) * r.cap;
+    uint32_t *fr = m.frontier_ids + static_cast<uint64_t>(qi) * m.cap;
+    uint32_t count = 0;   // the query's hits so far (wave-uniform)
+    uint32_t fcount = 0;  // the rows that joined its frontier so far (wave-uniform)
+    Visited vs;
+    PoolState ps;
+    uint32_t n_dist = 0, n_expand = 0, n_dist_up = 0, n_hops_up = 0;
+    query_begin<kIP, kChunks, kSpace>(p, L, qi, slot_bits, slot_dirty, nullptr, vs, ps, n_dist_up, n_hops_up,
+                                      [&](bool has, uint32_t id, float d) {
+                                        bool valid = has, allowed = true;
+                                        if (has) {
+                                          if (masked) allowed = ((mask[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                          if (p.valid != nullptr) valid = ((p.valid[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                        }
+                                        range_more_offer(count, fcount, r, m, region, fr, radius, masked, valid, allowed, id,
+                                                         d);
+                                      });
+
+    // ---- phase 1: range_search_kernel's loop ---------------------------------------------------
+    uint32_t pred = kEmpty, pred_v = kEmpty;  // adjacency prefetch of the predicted next pop
+    while (ps.cur < ps.size) {
+      const uint32_t u = pool_pop(ps, L);
+      ++n_expand;
+      uint32_t v = u == pred ? pred_v : adjacency_row(p, R, u);
+      const int cnt = adjacency_count(R, v);
+      bool act = lane < cnt;
+      if (p.dedup_edges) {  // graphs with repeated ids in a row: keep the first occurrence only
+        for (int j = 0; j < cnt; ++j) {
+          const uint32_t vj = read_lane(v, j);
+          if (j < lane && vj == v) act = false;
+        }
+      }
+      if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin(vs);
+      const bool fresh = visit(vs, v, act);
+      const uint64_t fm = ballot(fresh);
+      const int nf = __popcll(fm);
+      pred = ps.cur < ps.size ? (L.pi[ps.cur] & kIdMask) : kEmpty;
+      if (pred != kEmpty) pred_v = adjacency_row(p, R, pred, pred_v);
+      if (nf == 0) continue;
+      // compact fresh ids in adjacency order
+      if (fresh) L.cid[__popcll(fm & ((1ull << lane) - 1ull))] = v;
+      wave_sync();
+      const bool has = lane < nf;
+      const uint32_t cid = has ? L.cid[lane] : 0u;
+      uint32_t aw = 0xffffffffu, vw = 0xffffffffu;
+      if (has) {
+        if (masked) aw = mask[cid >> 5];
+        if (p.valid != nullptr) vw = p.valid[cid >> 5];
+      }
+      space_distances<kIP, kChunks, kSpace>(p, L, L.cid, nf, L.cd);
+      n_dist += nf;
+      const float cd = has ? L.cd[lane] : 0.f;
+      wave_sync();
+      pool_merge<kRegMerge>(ps, L, has, cid, cd, [&](uint32_t nx) {
+        if (nx != pred) {
+          pred = nx;
+          pred_v = adjacency_row(p, R, nx, pred_v);
+        }
+      });
+      range_more_offer(count, fcount, r, m, region, fr, radius, masked, has && ((vw >> (cid & 31)) & 1u) != 0u,
+                       ((aw >> (cid & 31)) & 1u) != 0u, cid, cd);
+    }
+    query_end(p, L, ps, qi, n_dist, n_expand, n_dist_up, n_hops_up);  // p.k = 0: phase 1's four counters
+
+    // ---- phase 2: the stored frontier rows, in arrival order -----------------------------------
+    uint32_t cursor = 0, more = 0;
+    for (;;) {
+      const uint32_t stored = min(fcount, m.cap);
+      if (cursor >= stored) break;
+      // a window of the frontier: entries appended while it is walked lie past it
+      const int wn = static_cast<int>(min(64u, stored - cursor));
+      const uint32_t w = lane < wn ? fr[cursor + static_cast<uint32_t>(lane)] : kEmpty;
+      uint32_t next_v = adjacency_row(p, R, read_lane(w, 0));
+      for (int j = 0; j < wn; ++j) {
+        const uint32_t v = next_v;
+        const int cnt = adjacency_count(R, v);
+        bool act = lane < cnt;
+        if (p.dedup_edges) {
+          for (int e = 0; e < cnt; ++e) {
+            const uint32_t ve = read_lane(v, e);
+            if (e < lane && ve == v) act = false;
+          }
+        }
+        if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin(vs);
+        const bool fresh = visit(vs, v, act);
+        const uint64_t fm = ballot(fresh);
+        const int nf = __popcll(fm);
+        // the window's next row, ahead of the distance pass
+        if (j + 1 < wn) next_v = adjacency_row(p, R, read_lane(w, j + 1), next_v);
+        if (nf == 0) continue;
+        if (fresh) L.cid[__popcll(fm & ((1ull << lane) - 1ull))] = v;
+        wave_sync();
+        const bool has = lane < nf;
+        const uint32_t cid = has ? L.cid[lane] : 0u;
+        uint32_t aw = 0xffffffffu, vw = 0xffffffffu;
+        if (has) {
+          if (masked) aw = mask[cid >> 5];
+          if (p.valid != nullptr) vw = p.valid[cid >> 5];
+        }
+        space_distances<kIP, kChunks, kSpace>(p, L, L.cid, nf, L.cd);
+        more += nf;
+        const float cd = has ? L.cd[lane] : 0.f;
+        wave_sync();
+        range_more_offer(count, fcount, r, m, region, fr, radius, masked, has && ((vw >> (cid & 31)) & 1u) != 0u,
+                         ((aw >> (cid & 31)) & 1u) != 0u, cid, cd);
+      }
+      cursor += static_cast<uint32_t>(wn);
+    }
+
+    if (lane == 0) {
+      r.counts[qi] = count;
+      if (m.more != nullptr) {
+        m.more[static_cast<uint64_t>(qi) * 2] = fcount;
+        m.more[static_cast<uint64_t>(qi) * 2 + 1] = more;
+      }
+    }
+    visit_end(vs);
+    wave_sync();
+  }
+}
+
 __device__ __forceinline__ uint32_t range_pow2(uint32_t n) {
   uint32_t p2 = 1;
   while (p2 < n) p2 <<= 1;
@@ -2390,6 +2577,38 @@ hipError_t launch_range_search(const SearchParams &p, const FilterParams &f, con
 
 hipError_t range_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, range_kernel_symbol(dim, generic, ip), 64 * waves, lds);
+}
+
+// The radius-mode range kernels: the same set.
+template <int... kChunks>
+static const void *range_more_symbol_of(int chunks, bool ip) {
+  const void *sym = nullptr;
+  ((chunks == kChunks ? (sym = ip ? reinterpret_cast<const void *>(&range_more_search_kernel<true, kChunks>)
+                                  : reinterpret_cast<const void *>(&range_more_search_kernel<false, kChunks>),
+                         0)
+                      : 0),
+   ...);
+  return sym;
+}
+
+static const void *range_more_kernel_symbol(uint32_t dim, bool generic, bool ip) {
+  const void *sym = range_more_symbol_of<4, 8, 16, 24, 30, 32>(search_chunks(dim, generic), ip);
+  return sym != nullptr ? sym : range_more_symbol_of<0>(0, ip);
+}
+
+hipError_t launch_range_more_search(const SearchParams &p, const FilterParams &f, const RangeParams &r,
+                                    const RangeMoreParams &m, int grid, int waves, size_t lds, hipStream_t stream) {
+  SearchParams arg = p;
+  FilterParams farg = f;
+  RangeParams rarg = r;
+  RangeMoreParams marg = m;
+  void *args[] = {&arg, &farg, &rarg, &marg};
+  return hipLaunchKernel(range_more_kernel_symbol(p.dim, p.generic, p.ip), dim3(grid), dim3(64 * waves), args, lds, stream);
+}
+
+hipError_t range_more_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, range_more_kernel_symbol(dim, generic, ip), 64 * waves,
+                                                      lds);
 }
 
 hipError_t launch_range_sort(const RangeParams &r, uint64_t nq, hipStream_t stream) {

@@ -214,7 +214,7 @@ class Index:
         return self.__index.filtered_search(queries, topk, ef_search, words, groups, pool, through)
 
     def range_search(self, queries: VectorLikeBatch, radius, ef_search: int = 100, max_results: int = 1024,
-                     allow=None, groups=None, _chunk=None):
+                     allow=None, groups=None, _chunk=None, expand="fixed", max_frontier: int = 4096):
         """Every row within distance ``radius`` of each query, among the rows the graph traversal measures.
         The traversal is ``batch_search``'s at ``ef_search``; the radius does not steer it.  Every distance it
         computes for a valid row (and, with ``allow`` / ``groups`` as in ``filtered_search``, an allowed one)
@@ -229,8 +229,27 @@ class Index:
         ``lims[i + 1] - lims[i] == min(counts[i], max_results)``.  ``counts[i] > max_results`` means the
         list is truncated: it then holds the first ``max_results`` hits the traversal met, NOT the nearest
         ones -- raise ``max_results`` (1..4096) or lower the radius.  A removed row is never returned.
-        float32 graph search only: an SQ8 index is refused."""
+        float32 graph search only: an SQ8 index is refused.
+
+        ``expand="radius"`` lets the radius steer the search.  The traversal above runs first, unchanged;
+        ``ef_search`` now only says where the flood fill starts.  Then every valid row measured within the
+        radius -- allowed or not -- is expanded in the order it turned up: its unvisited neighbours are
+        measured, the ones within the radius are hits (if allowed) and are expanded in their turn, until no
+        new row within the radius turns up.  The result is the in-radius region of the graph that the
+        traversal reached, so a small ``ef_search`` suffices where ``expand="fixed"`` needs a guess that
+        grows with the radius ("Round 20").  At most ``max_frontier`` (1..16384) rows
+        per query are expanded this way, the first to turn up.  ``native().last_range_more()`` is a uint32
+        array of shape (nq, 2) for the last call: column 0 the rows within the radius that turned up,
+        column 1 the distances the continuation computed.  There are now two truncations:
+        ``counts[i] > max_results`` as above, and ``last_range_more()[i, 0] > max_frontier`` -- rows past
+        the first ``max_frontier`` were counted and returned but not expanded, so rows behind them may be
+        missing.  A huge radius makes the continuation read up to ``max_frontier`` adjacency rows and
+        measure up to ``max_frontier x R`` rows per query: it is the radius that bounds the work.
+        ``expand="fixed"`` (the default) is the call without the keyword, bit for bit."""
         self._check_queries(queries, 2, "queries")
+        _assert(expand in ("fixed", "radius"), "expand must be 'fixed' or 'radius'")
+        radius_mode = expand == "radius"
+        _assert(1 <= max_frontier <= 16384, "max_frontier must be in 1..16384")
         _assert((self.__params.quantization_type or "none").lower() != "sq8",
                 "range_search searches f32 indexes only: this index has SQ8 codes")
         _assert(1 <= max_results <= 4096, "max_results must be in 1..4096")
@@ -245,13 +264,19 @@ class Index:
             _assert(groups is None, "groups needs allow")
         else:
             words, groups = self._masks(allow, groups, nq)
-        # chunks of queries: at most 2^26 padded result slots per call
-        step = max(1, (1 << 26) // max_results) if _chunk is None else int(_chunk)
+        # chunks of queries: at most 2^26 padded result (and frontier) slots per call
+        widest = max(max_results, max_frontier) if radius_mode else max_results
+        step = max(1, (1 << 26) // widest) if _chunk is None else int(_chunk)
         parts = []
         for lo in range(0, nq, step):
             hi = min(nq, lo + step)
-            counts, ids, dists, _ = self.__index.range_search(queries[lo:hi], ef_search, radii[lo:hi], max_results, words,
-                                                              None if groups is None else groups[lo:hi])
+            if radius_mode:
+                counts, ids, dists, _ = self.__index.range_search(queries[lo:hi], ef_search, radii[lo:hi], max_results,
+                                                                  words, None if groups is None else groups[lo:hi], True,
+                                                                  max_frontier, lo > 0)
+            else:
+                counts, ids, dists, _ = self.__index.range_search(queries[lo:hi], ef_search, radii[lo:hi], max_results,
+                                                                  words, None if groups is None else groups[lo:hi])
             parts.append((counts,) + range_csr(counts, ids, dists, max_results)[1:])
         if not parts:
             return (np.zeros(1, np.int64), np.zeros(0, self.__params.id_type), np.zeros(0, np.float32),

@@ -248,6 +248,48 @@ int alaya_index_range_search_device(alaya_index *ix, const float *d_queries, uin
                                     const float *d_radii, uint32_t max_results, const uint32_t *d_allow_words,
                                     uint32_t n_masks, const uint32_t *d_mask_of_query, uint32_t *d_counts,
                                     uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream);
+/* Range search, radius mode: the range search above, which then keeps expanding while rows within the radius
+ * turn up -- a flood fill of the in-radius region the traversal reached.  ef says where the fill starts.  For
+ * query i with radius r_i, result cap C = max_results (1..4096) and frontier cap F = max_frontier (1..16384):
+ *   1. Phase 1 is alaya_index_range_search, unchanged: alaya_index_batch_search's traversal at ef on the f32
+ *      rows, the same pops, the same four counters, the same hit rule (valid, allowed when masks are given,
+ *      d <= r_i as an f32 comparison, arrival order).
+ *   2. The frontier: every (id, d) that phase 1 or phase 2 computes, entry offers included, joins the query's
+ *      frontier in arrival order when its row is valid and d <= r_i.  The allow mask does not matter here: a
+ *      disallowed in-radius row is not a hit but is continued through.  frontier[i] counts the rows that
+ *      joined and is not capped; the first F to arrive are stored.  A removed row never joins; a repeated
+ *      entry point joins twice and stays twice.
+ *   3. Phase 2: when the traversal pool has no unchecked entry left, the stored frontier rows are expanded in
+ *      arrival order, whether or not phase 1 had already popped them.  For each, the level-0 row is read
+ *      (repeated ids dropped as in phase 1); neighbours not yet visited are marked visited, measured in
+ *      adjacency order and offered: hits follow rule 1, the frontier rule 2.  Nothing is inserted into the
+ *      traversal pool.  Phase 2 ends when the cursor reaches the end of the stored frontier, so it expands
+ *      min(frontier[i], F) rows; more_dist[i] counts the distances it computed.
+ *   4. counts, the stored min(counts, C) first hits and their order by (distance, id) are rules 3-6 of
+ *      alaya_index_range_search, applied to the hit stream of both phases.  The four counters stay phase 1's,
+ *      so they still equal alaya_index_batch_search's.
+ *   5. frontier[i] > F means the continuation was cut: in-radius rows past the first F were counted and
+ *      returned as hits, but not expanded.
+ *   6. (An implementation may skip the adjacency read of a frontier row it can prove phase 1 expanded: such a
+ *      row yields no fresh neighbour, so hits, frontier and more_dist are the same either way.  This one reads
+ *      every row.)
+ * With no truncation (counts <= C, frontier <= F), no mask and no removed rows the returned set contains phase
+ * 1's hits and is closed: every level-0 neighbour of a returned row that lies within the radius is returned too.
+ * With a radius below every measured distance phase 2 does nothing.  A radius that takes in most of the index
+ * makes phase 2 read up to F adjacency rows and measure up to F x R rows per query.
+ * more (nullable): nq x 2, (frontier[i], more_dist[i]).  The arguments, refusals and environment switches are
+ * alaya_index_range_search's; max_frontier outside 1..16384 is an argument error as well. */
+int alaya_index_range_search_radius(alaya_index *ix, const float *queries, uint64_t nq, uint32_t ef, const float *radii,
+                                    uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
+                                    const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists,
+                                    uint32_t *counters, uint32_t max_frontier, uint32_t *more);
+/* Same on device buffers, asynchronous on `stream`, as alaya_index_range_search_device; the frontier (nq x
+ * max_frontier ids) is the index's own scratch beside the append list. */
+int alaya_index_range_search_radius_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t ef,
+                                           const float *d_radii, uint32_t max_results, const uint32_t *d_allow_words,
+                                           uint32_t n_masks, const uint32_t *d_mask_of_query, uint32_t *d_counts,
+                                           uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream,
+                                           uint32_t max_frontier, uint32_t *d_more);
 /* ---- device graph construction (Index.fit on the MI355X) ------------------------------------
  * Replaces HNSWBuilder::build_graph (include/index/graph/hnsw/hnsw_builder.hpp:98-194) over hnswlib
  * add_point (include/index/graph/hnsw/hnswlib.hpp:652-751), from the index's own rows
