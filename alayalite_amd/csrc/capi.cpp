@@ -137,6 +137,7 @@ struct alaya_index {
   // range search: the append buffers of both entry points (nq x cap ids and distances, scratch between the search
   // launch and the sort), and the host entry's radii and counts
   DevBuf range_ids, range_d, range_radii, range_cnt;
+  DevBuf range_cradii, range_cand;    // SQ8 range search, host entry: the code radii and the candidate counts
   DevBuf range_frontier, range_more;  // radius mode: nq x max_frontier frontier ids (scratch), the host entry's nq x 2 `more`
   // exact filtered scan (alaya_index_flat_search_filtered*): the current mask's id list (n words), the
   // compaction's block sums and count, the partial lists of one scan launch (capped, see
@@ -420,6 +421,8 @@ uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchV
   int vgpr_blocks = 0;
   const size_t probe_lds = shared + W * (wave_fixed + (stab ? 1024 : 4096));
   hip_check(more    ? alaya_amd::range_more_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
+            : range && p.sq8_order
+                ? alaya_amd::range_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, probe_lds, &vgpr_blocks)
             : range ? alaya_amd::range_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
             : !filter_k ? alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks)
             : hop ? alaya_amd::filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
@@ -773,12 +776,15 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
 // same plan without a result pool (k = 0, d_ids / d_dists unused) and with that kernel's occupancy; d_allow may be
 // null (no mask).  The kernel fills range->counts and the append buffers; the caller launches the sort.  more: the
 // radius mode (alaya_index_range_search_radius*, range_more_search_kernel) -- the same plan with that kernel's occupancy.
+// range with sq8: the search stage of the range search of SQ8 codes (alaya_index_range_search_sq8*,
+// range_sq8_search_kernel) -- the plain mode-0 SQ8 plan of the shape, as the sq8 case, without a result pool and with
+// that kernel's occupancy; range->radii are the code radii and range->counts receives the candidate counts.
 void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t ef, const uint32_t *d_allow,
                         const uint32_t *d_mask_of_query, uint32_t *d_ids, float *d_dists, uint32_t *d_cnt,
                         hipStream_t stream, bool sq8 = false, bool hop = false, uint32_t *d_through = nullptr,
                         const alaya_amd::RangeParams *range = nullptr, const alaya_amd::RangeMoreParams *more = nullptr) {
   using namespace alaya_amd;
-  if (range && (sq8 || ix->has_sq8))
+  if (range && !sq8 && ix->has_sq8)
     throw ArgError("range search of an SQ8 index: alaya_index_range_search searches f32 rows only");
   if (hop && (sq8 || ix->has_sq8))
     throw ArgError("through search of an SQ8 index: alaya_index_filtered_search_hop searches f32 rows only");
@@ -812,6 +818,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
                          : "filtered search: k / ef / dim too large for the LDS budget");
   int per_cu = 0;
   hip_check(more    ? range_more_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
+            : range && sq8 ? range_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, lds, &per_cu)
             : range ? range_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
             : sq8 ? filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, lds, &per_cu)
             : hop ? filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
@@ -828,6 +835,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   prepare_spill(ix, p, searchers, stream);
   record_launch(ix, p, grid, W, lds, per_cu, searchers, stream);  // (no scout, helpers or screen: p has none set)
   hip_check(more    ? launch_range_more_search(p, f, *range, *more, grid, W, lds, stream)
+            : range && sq8 ? launch_range_sq8_search(p, f, *range, grid, W, lds, stream)
             : range ? launch_range_search(p, f, *range, grid, W, lds, stream)
             : sq8 ? launch_filtered_sq8_search(p, f, grid, W, lds, stream)
             : hop ? launch_filtered_hop_search(p, f, HopParams{d_through}, grid, W, lds, stream)
@@ -2456,6 +2464,100 @@ int alaya_index_range_search_radius(alaya_index *ix, const float *queries, uint6
                                     uint32_t *counters, uint32_t max_frontier, uint32_t *more) {
   return range_host_call(ix, queries, nq, ef, radii, max_results, allow_words, n_masks, mask_of_query, counts, ids, dists,
                          counters, true, max_frontier, more);
+}
+
+// alaya_index_range_search_sq8_device / alaya_index_range_search_sq8: the search stage (do_filtered_search's range plan
+// on the SQ8 space) appends the candidates within the code radii to the index's append buffers and counts them in
+// d_cand; the rerank measures the stored ones on the f32 rows against d_rq, pads the ones past the exact radius and
+// adds the hits to d_counts (zeroed here, on the stream); the sort orders them into d_ids / d_dists.  The caller
+// holds ix->mu.
+static void range_sq8_dev(alaya_index *ix, const float *d_q, const float *d_rq, uint64_t nq, uint32_t ef,
+                          const float *d_radii, const float *d_code_radii, uint32_t max_results, const uint32_t *d_allow,
+                          const uint32_t *d_mask_of_query, uint32_t *d_counts, uint32_t *d_cand, uint32_t *d_ids,
+                          float *d_dists, uint32_t *d_cnt, hipStream_t s) {
+  if (!ix->has_sq8) throw ArgError("index has no SQ8 codes");
+  check_range_cap(max_results);
+  if (ef == 0) throw ArgError("ef must be >= 1");
+  const size_t slots = static_cast<size_t>(nq) * max_results;
+  ix->range_ids.reserve(slots * 4);
+  ix->range_d.reserve(slots * 4);
+  alaya_amd::RangeParams r{};
+  r.radii = d_code_radii;
+  r.cap = max_results;
+  r.append_ids = ix->range_ids.as<uint32_t>();
+  r.append_dists = ix->range_d.as<float>();
+  r.counts = d_cand;
+  r.out_ids = d_ids;
+  r.out_dists = d_dists;
+  do_filtered_search(ix, d_q, nq, 0, ef, d_allow, d_mask_of_query, nullptr, nullptr, d_cnt, s, true, false, nullptr, &r);
+  if (nq == 0) return;
+  hip_check(hipMemsetAsync(d_counts, 0, nq * 4, s), "hipMemsetAsync");
+  // diagnostics (ALAYA_RANGE_SORT, include/alaya_hip.h), to time the stages: 0 = the search stage alone, counts stay
+  // zero; 2 = the search and the rerank without the sort; ids / dists are then left unwritten
+  const char *stages = std::getenv("ALAYA_RANGE_SORT");
+  if (stages && std::atoi(stages) == 0) return;
+  SearchParams p = base_params(ix);
+  p.queries = d_rq ? d_rq : d_q;
+  p.nq = nq;
+  p.q_stride = ix->dim;
+  r.radii = d_radii;
+  hip_check(alaya_amd::launch_range_rerank(p, r, d_counts, s), "range rerank launch");
+  if (!(stages && std::atoi(stages) == 2)) hip_check(alaya_amd::launch_range_sort(r, nq, s), "range sort launch");
+  scratch_release(ix, s);  // the rerank and the sort read the append buffers
+}
+
+int alaya_index_range_search_sq8_device(alaya_index *ix, const float *d_queries, const float *d_rerank_queries, uint64_t nq,
+                                        uint32_t ef, const float *d_radii, const float *d_code_radii, uint32_t max_results,
+                                        const uint32_t *d_allow_words, uint32_t n_masks, const uint32_t *d_mask_of_query,
+                                        uint32_t *d_counts, uint32_t *d_cand, uint32_t *d_ids, float *d_dists,
+                                        uint32_t *d_counters, void *stream) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (nq && (!d_queries || !d_radii || !d_code_radii || !d_counts || !d_cand || !d_ids || !d_dists)))
+      throw ArgError("invalid arguments");
+    check_range_masks(nq, d_allow_words, n_masks, d_mask_of_query, false);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    range_sq8_dev(ix, d_queries, d_rerank_queries, nq, ef, d_radii, d_code_radii, max_results, d_allow_words,
+                  d_mask_of_query, d_counts, d_cand, d_ids, d_dists, d_counters, static_cast<hipStream_t>(stream));
+  });
+}
+
+int alaya_index_range_search_sq8(alaya_index *ix, const float *queries, const float *rerank_queries, uint64_t nq, uint32_t ef,
+                                 const float *radii, const float *code_radii, uint32_t max_results,
+                                 const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                 uint32_t *counts, uint32_t *cand, uint32_t *ids, float *dists, uint32_t *counters) {
+  return guarded_scratch(ix, [&] {
+    if (!ix || (nq && (!queries || !radii || !code_radii || !counts || !cand || !ids || !dists)))
+      throw ArgError("invalid arguments");
+    check_range_masks(nq, allow_words, n_masks, mask_of_query, true);
+    for (uint64_t i = 0; i < nq; ++i)
+      if (radii[i] != radii[i] || code_radii[i] != code_radii[i]) throw ArgError("range search: a radius is NaN");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    check_range_cap(max_results);  // (before the result buffers are sized by it)
+    if (nq == 0) {
+      range_sq8_dev(ix, nullptr, nullptr, 0, ef, nullptr, nullptr, max_results, nullptr, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, ix->stream);  // the index's own refusals
+      return;
+    }
+    const float *d_q = stage_queries(ix, queries, nq, max_results);
+    const float *d_rq = stage_rerank_queries(ix, rerank_queries, queries, nq);
+    const uint32_t *d_allow = allow_words ? stage_masks(ix, allow_words, n_masks) : nullptr;
+    const uint32_t *d_groups = allow_words ? stage_mask_indices(ix, mask_of_query, nq) : nullptr;
+    ix->range_radii.reserve(nq * 4);
+    ix->range_cradii.reserve(nq * 4);
+    ix->range_cnt.reserve(nq * 4);
+    ix->range_cand.reserve(nq * 4);
+    hip_check(hipMemcpyAsync(ix->range_radii.ptr, radii, nq * 4, hipMemcpyHostToDevice, ix->stream), "upload radii");
+    hip_check(hipMemcpyAsync(ix->range_cradii.ptr, code_radii, nq * 4, hipMemcpyHostToDevice, ix->stream), "upload radii");
+    range_sq8_dev(ix, d_q, d_rq, nq, ef, ix->range_radii.as<float>(), ix->range_cradii.as<float>(), max_results, d_allow,
+                  d_groups, ix->range_cnt.as<uint32_t>(), ix->range_cand.as<uint32_t>(), ix->id_buf.as<uint32_t>(),
+                  ix->dist_buf.as<float>(), ix->cnt_buf.as<uint32_t>(), ix->stream);
+    fetch_results(ix, nq, max_results, ids, dists, counters);
+    hip_check(hipMemcpyAsync(counts, ix->range_cnt.ptr, nq * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    hip_check(hipMemcpyAsync(cand, ix->range_cand.ptr, nq * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    stream_sync(ix, "range sq8 search");
+  });
 }
 
 int alaya_index_profile_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k,

@@ -447,6 +447,45 @@ class PyIndexInterface : public LaunchControls {
     return py::make_tuple(counts, widen_ids(ids32, nq, max_results, true), dists, last_counters());
   }
 
+  // --- extra (not in the reference binding): range_search on an SQ8 index (alaya_index_range_search_sq8).  The
+  // traversal of batch_search at `ef` runs on the codes; the valid, allowed rows it measures within `code_radius`
+  // by code distance are candidates, the first max_results of them are measured exactly and those within `radius`
+  // are the hits.  Returns range_search's tuple with counts the hits; last_range_candidates() holds the candidate
+  // counts (cand_append: behind an earlier chunk's of one Index.range_search call).  The query forms are
+  // filtered_search's on an SQ8 index.
+  py::object range_search_sq8(py::array queries, uint32_t ef, py::object radius, py::object code_radius,
+                              uint32_t max_results, py::object allow_words, py::object mask_of_query, bool cand_append) {
+    if (!graph_) throw std::runtime_error("Index is not init yet");
+    if (params_.quantization_type_ != QuantizationType::SQ8)
+      throw py::value_error("range_search_sq8 searches SQ8 indexes only");
+    py::array q = prepare_queries(queries);
+    const uint64_t nq = q.shape(0);
+    U32Array words;
+    const Masks m = parse_range_masks(allow_words, words, mask_of_query, n_, nq);
+    const std::vector<float> radii = parse_radii(radius, nq);
+    const std::vector<float> code_radii = parse_radii(code_radius, nq);
+    if (max_results == 0 || max_results > 4096) throw py::value_error("max_results must be in 1..4096");
+    std::vector<uint32_t> ids32(nq * max_results);
+    py::array_t<float> dists = out2d<float>(nq, max_results);
+    py::array_t<uint32_t> counts(static_cast<py::ssize_t>(nq));
+    uint32_t *cp = counts.mutable_data();
+    float *dp = dists.mutable_data();
+    last_counters_.assign(nq * 4, 0);
+    std::vector<uint32_t> cand(nq, 0);  // joins last_range_cand_ only once the call has succeeded
+    uint32_t *np = cand.data();
+    const float *qp = static_cast<const float *>(q.data());
+    // the traversal encodes the query as given, the rerank's f32 distance takes the normalised one (run())
+    const float *sq = raw_queries_.empty() ? qp : raw_queries_.data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_range_search_sq8(ix_, sq, qp, nq, ef, radii.data(), code_radii.data(), max_results, m.words,
+                                         m.n_masks, m.of_query, cp, np, ids32.data(), dp, last_counters_.data()));
+    }
+    if (!cand_append) last_range_cand_.clear();
+    last_range_cand_.insert(last_range_cand_.end(), cand.begin(), cand.end());
+    return py::make_tuple(counts, widen_ids(ids32, nq, max_results, true), dists, last_counters());
+  }
+
   uint64_t get_data_num() const { return n_; }
 
   py::array get_data_by_id(uint32_t id) {
@@ -599,6 +638,12 @@ class PyIndexInterface : public LaunchControls {
 
   // --- extra (not in the reference binding): device counters of the last search ---
   // rows stepped through per query of the last filtered_search(..., through=True); empty after any other
+  // candidates per query of the last range_search_sq8: shape (nq,)
+  py::array last_range_candidates() const {
+    py::array_t<uint32_t> out(static_cast<py::ssize_t>(last_range_cand_.size()));
+    if (!last_range_cand_.empty()) std::memcpy(out.mutable_data(), last_range_cand_.data(), last_range_cand_.size() * 4);
+    return out;
+  }
   // (frontier, more_dist) per query of the last radius-mode range_search: shape (nq, 2)
   py::array last_range_more() const {
     py::array_t<uint32_t> out = out2d<uint32_t>(last_range_more_.size() / 2, 2);
@@ -917,6 +962,7 @@ class PyIndexInterface : public LaunchControls {
   std::vector<uint32_t> last_counters_;
   std::vector<uint32_t> last_through_;
   std::vector<uint32_t> last_range_more_;
+  std::vector<uint32_t> last_range_cand_;  // candidate counts of the last range_search_sq8 (chunks concatenated)
   int rerank_mode_ = 1;
   std::vector<float> raw_queries_;   // SQ8 + COS: the un-normalised queries the SQ8 search encodes
   std::vector<uint8_t> sq_codes_;
@@ -1175,6 +1221,50 @@ class DeviceIndex : public LaunchControls {
                                           dptr<uint32_t>(counts), dptr<uint32_t>(ids), dptr<float>(dists),
                                           dptr<uint32_t>(counters), dptr<void>(stream)));
   }
+  // range search of the index's SQ8 codes, the stored candidates measured on the f32 rows
+  // (alaya_index_range_search_sq8): (counts[nq] = hits, ids[nq, max_results], dists[nq, max_results], counters[nq, 4],
+  // cand[nq] = candidates within code_radius, not capped); radius / code_radius: a number or one per query;
+  // allow_words / groups as range_search's masks; rerank_queries: None = queries
+  py::tuple range_search_sq8(F32Array q, uint32_t ef, py::object radius, py::object code_radius, uint32_t max_results,
+                             py::object allow_words, py::object mask_of_query, py::object rerank_queries) {
+    const uint64_t nq = q.shape(0);
+    U32Array words;
+    const Masks m = parse_range_masks(allow_words, words, mask_of_query, rows(), nq);
+    const std::vector<float> radii = parse_radii(radius, nq);
+    const std::vector<float> code_radii = parse_radii(code_radius, nq);
+    if (max_results == 0 || max_results > 4096) throw py::value_error("max_results must be in 1..4096");
+    F32Array rq;
+    const float *rqp = nullptr;
+    if (!rerank_queries.is_none()) {
+      rq = F32Array(rerank_queries);
+      if (rq.ndim() != 2 || rq.shape(0) != q.shape(0) || rq.shape(1) != q.shape(1))
+        throw py::value_error("rerank_queries must have the queries' shape");
+      rqp = rq.data();
+    }
+    Results r(nq, max_results);
+    py::array_t<uint32_t> counts(static_cast<py::ssize_t>(nq));
+    py::array_t<uint32_t> cand(static_cast<py::ssize_t>(nq));
+    uint32_t *np = counts.mutable_data();
+    uint32_t *cdp = cand.mutable_data();
+    const float *qp = q.data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_range_search_sq8(ix_, qp, rqp, nq, ef, radii.data(), code_radii.data(), max_results, m.words,
+                                         m.n_masks, m.of_query, np, cdp, r.ip, r.dp, r.cp));
+    }
+    return py::make_tuple(counts, r.ids, r.d, r.c, cand);
+  }
+  void range_search_sq8_device(uintptr_t q, uintptr_t rq, uint64_t nq, uint32_t ef, uintptr_t radii, uintptr_t code_radii,
+                               uint32_t max_results, uintptr_t allow_words, uint32_t n_masks, uintptr_t mask_of_query,
+                               uintptr_t counts, uintptr_t cand, uintptr_t ids, uintptr_t dists, uintptr_t counters,
+                               uintptr_t stream) {
+    check(alaya_index_range_search_sq8_device(ix_, dptr<const float>(q), dptr<const float>(rq), nq, ef,
+                                              dptr<const float>(radii), dptr<const float>(code_radii), max_results,
+                                              dptr<const uint32_t>(allow_words), n_masks,
+                                              dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(counts),
+                                              dptr<uint32_t>(cand), dptr<uint32_t>(ids), dptr<float>(dists),
+                                              dptr<uint32_t>(counters), dptr<void>(stream)));
+  }
   // the same over the index's SQ8 codes, reranked on the f32 rows (alaya_index_filtered_search_sq8); pool: the
   // candidate pool's capacity, 0 = min(224, max(k, ef)); rerank_queries: None = queries
   py::tuple filtered_search_sq8(F32Array q, uint32_t k, uint32_t ef, U32Array allow_words, py::object mask_of_query,
@@ -1418,6 +1508,10 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("range_search", &PyIndexInterface::range_search, py::arg("queries"), py::arg("ef"), py::arg("radius"),
            py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none(),
            py::arg("radius_mode") = false, py::arg("max_frontier") = 4096u, py::arg("more_append") = false)
+      .def("range_search_sq8", &PyIndexInterface::range_search_sq8, py::arg("queries"), py::arg("ef"), py::arg("radius"),
+           py::arg("code_radius"), py::arg("max_results"), py::arg("allow_words") = py::none(),
+           py::arg("mask_of_query") = py::none(), py::arg("cand_append") = false)
+      .def("last_range_candidates", &PyIndexInterface::last_range_candidates)
       .def("last_range_more", &PyIndexInterface::last_range_more)
       .def("last_through", &PyIndexInterface::last_through)
       .def("get_data_dim", &PyIndexInterface::get_data_dim)
@@ -1470,6 +1564,10 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("range_search", &DeviceIndex::range_search, py::arg("queries"), py::arg("ef"), py::arg("radius"),
            py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none())
       .def("range_search_device", &DeviceIndex::range_search_device)
+      .def("range_search_sq8", &DeviceIndex::range_search_sq8, py::arg("queries"), py::arg("ef"), py::arg("radius"),
+           py::arg("code_radius"), py::arg("max_results"), py::arg("allow_words") = py::none(),
+           py::arg("groups") = py::none(), py::arg("rerank_queries") = py::none())
+      .def("range_search_sq8_device", &DeviceIndex::range_search_sq8_device)
       .def("range_search_radius", &DeviceIndex::range_search_radius, py::arg("queries"), py::arg("ef"), py::arg("radius"),
            py::arg("max_results"), py::arg("max_frontier") = 4096u, py::arg("allow_words") = py::none(),
            py::arg("mask_of_query") = py::none())

@@ -256,6 +256,17 @@ hipError_t filtered_sq8_search_occupancy(uint32_t dim, int sq8_order, bool ip, i
                                          int *blocks_per_cu);
 hipError_t launch_filtered_sq8_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
                                       hipStream_t stream);
+// Range search of SQ8 codes (range_sq8_search_kernel): p is planned as the plain (mode 0) SQ8 search of the
+// shape with no result pool (p.k = 0); r.radii are the code radii, r.counts receives the candidate counts
+// and the append buffers the first r.cap (id, code distance) candidates per query; f.allow == nullptr = no
+// mask.  launch_range_rerank (range_rerank_kernel) then takes p.base / p.queries as the f32 rows and the
+// rerank queries, r.radii as the exact radii and r.counts as those candidate counts: it overwrites the
+// stored code distances with exact ones, turns a candidate past its radius into the sort's pad and adds the
+// hits to hits[i], which the caller zeroes on the stream first.  launch_range_sort follows with the same r.
+hipError_t range_sq8_search_occupancy(uint32_t dim, int sq8_order, bool ip, int waves, size_t lds, int *blocks_per_cu);
+hipError_t launch_range_sq8_search(const SearchParams &p, const FilterParams &f, const RangeParams &r, int grid, int waves,
+                                   size_t lds, hipStream_t stream);
+hipError_t launch_range_rerank(const SearchParams &p, const RangeParams &r, uint32_t *hits, hipStream_t stream);
 // out[q * n + i] = dist(queries[q], base[ids[i]]) for q < nq (bit-exact device distance)
 hipError_t launch_row_distances(const SearchParams &p, const uint32_t *ids, uint32_t n,
                                 uint32_t nq, float *out, hipStream_t stream);

@@ -2547,6 +2547,170 @@ __global__ void __launch_bounds__(256) range_sort_kernel(RangeParams r) {
     r.out_dists[region + i] = i < n ? sd[i] : FLT_MAX;
   }
 }
+
+// --------------------------------------------------------------------------------------------
+// Range search of SQ8 codes: filtered_sq8_search_kernel's traversal, pop for pop -- the query encoded to
+// codes, code-to-code distances without a validity test, the spill levels and their prefetch -- with the
+// candidate pool replaced by range_search_kernel's append list, cut at the query's code radius
+// (r.radii[i]).  Every (id, code distance) the traversal hands to pool.insert, in that order, whose row is
+// valid, allowed by the query's mask (f.allow == nullptr: no mask) and has d_code <= the code radius is a
+// candidate: r.counts[i] counts them all, the first r.cap are stored in arrival order.
+// range_rerank_kernel then measures the stored ones exactly.  No LDS beyond the plain SQ8 searcher's
+// (carve_lds is unchanged, p.k = 0: query_end writes the counters only).
+// --------------------------------------------------------------------------------------------
+
+// range_offer under candidate_offer's discipline: the validity bitmap is read last, and only when some allowed
+// lane is within the code radius, so no validity word is live across the distance pass.
+__device__ __forceinline__ void range_sq8_offer(const SearchParams &p, uint32_t &count, const RangeParams &r, uint64_t region,
+                                                float radius, bool allowed, uint32_t id, float d) {
+  bool ok = allowed && d <= radius;
+  if (ballot(ok) == 0ull) return;
+  if (p.valid != nullptr && ok) ok = ((p.valid[id >> 5] >> (id & 31)) & 1u) != 0u;
+  range_offer(count, r, region, radius, ok, id, d);
+}
+
+template <bool kIP, int kChunks, int kSpace>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(search_min_waves<kChunks, kSpace, 0>() ? search_min_waves<kChunks, kSpace, 0>() : 1, 8)))
+    range_sq8_search_kernel(SearchParams p, FilterParams f, RangeParams r) {
+  static_assert(space_sq8<kSpace>(), "SQ8 codes");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr bool kTab = space_tab<kSpace>();
+  const int lane = lane_id();
+  const int wave = static_cast<int>(threadIdx.x >> 6);
+  const int W = static_cast<int>(blockDim.x >> 6);
+  const Lds L = carve_lds<kSpace>(p, smem, wave);
+  fill_shared<kSpace>(p, L);  // the workgroup's only barrier: every wave passes it, with or without a query
+  const uint64_t bit_words = (p.n + 31) / 32;
+  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * W + wave;
+  uint32_t *slot_bits = p.overflow_bits + slot * bit_words;
+  uint32_t *slot_dirty = p.dirty_words + slot * p.dirty_cap;
+  uint16_t *slot_stab = (kTab && p.spill_table) ? p.spill_table + (slot << p.stab_log2) : nullptr;
+  const bool masked = f.allow != nullptr;  // (uniform over the launch)
+
+  for (;;) {
+    uint32_t qi = 0;
+    if (lane == 0) qi = atomicAdd(p.work_counter, 1u);
+    qi = read_lane(qi, 0);
+    if (qi >= p.nq) break;
+    const uint32_t *mask =
+        masked ? f.allow + static_cast<uint64_t>(f.mask_of_query != nullptr ? f.mask_of_query[qi] : 0u) * f.mask_words
+               : nullptr;
+    // the query's state across the loop, all wave-uniform: the code radius, the region base, the count
+    const float radius = r.radii[qi];
+    const uint64_t region = static_cast<uint64_t>(qi) * r.cap;
+    uint32_t count = 0;
+    Visited vs;
+    PoolState ps;
+    uint32_t n_dist = 0, n_expand = 0, n_dist_up = 0, n_hops_up = 0;
+    query_begin<kIP, kChunks, kSpace>(p, L, qi, slot_bits, slot_dirty, slot_stab, vs, ps, n_dist_up, n_hops_up,
+                                      [&](bool has, uint32_t id, float d) {
+                                        bool allowed = has;
+                                        if (has && masked) allowed = ((mask[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                        range_sq8_offer(p, count, r, region, radius, allowed, id, d);
+                                      });
+
+    // ---- best-first expansion: the plain SQ8 searcher's loop ----------------------------------
+    uint32_t pred = kEmpty, pred_v = kEmpty;  // adjacency prefetch of the predicted next pop
+    uint32_t pre_u = kEmpty;                  // second-level state read one expansion ahead (spill_prefetch)
+    uint64_t pre_lo = 0ull, pre_hi = 0ull;
+    while (ps.cur < ps.size) {
+      const uint32_t u = pool_pop(ps, L);
+      ++n_expand;
+      uint32_t v = u == pred ? pred_v : adjacency_row(p, static_cast<int>(p.R), u);
+      const int cnt = adjacency_count(static_cast<int>(p.R), v);
+      bool act = lane < cnt;
+      if (p.dedup_edges) {  // graphs with repeated ids in a row: keep the first occurrence only
+        for (int j = 0; j < cnt; ++j) {
+          const uint32_t vj = read_lane(v, j);
+          if (j < lane && vj == v) act = false;
+        }
+      }
+      if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin<kTab>(vs);
+      const bool fresh = visit<kTab>(vs, v, act, u == pre_u, pre_lo, pre_hi);
+      // the pred_v load below issues after this visit's spill-table stores and bitset atomics: the
+      // second-level prefetch's wait for pred_v is its wait for them (as in hnsw_search_kernel)
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" ::: "memory");
+      pre_u = kEmpty;  // consumed: the prefetched state describes the table only up to this visit's stores
+      pre_lo = pre_hi = 0ull;
+      const uint64_t fm = ballot(fresh);
+      const int nf = __popcll(fm);
+      pred = ps.cur < ps.size ? (L.pi[ps.cur] & kIdMask) : kEmpty;
+      if (pred != kEmpty) pred_v = adjacency_row(p, static_cast<int>(p.R), pred, pred_v);
+      if (nf == 0) continue;
+      // compact fresh ids in adjacency order
+      if (fresh) L.cid[__popcll(fm & ((1ull << lane) - 1ull))] = v;
+      wave_sync();
+      // each candidate's allow word goes out ahead of the code rows, by the lane that will hold the
+      // candidate at the merge; it is used only after the distances, so its latency is the rows'
+      const bool has = lane < nf;
+      uint32_t aw = 0xffffffffu;
+      if (has && masked) aw = mask[L.cid[lane] >> 5];
+      space_distances<kIP, kChunks, kSpace>(p, L, L.cid, nf, L.cd, [&]() {
+        // the predicted next expansion's second-level state, behind this expansion's first row pass
+        if (vs.spilled && pred != kEmpty && !(p.spill_flags & 1u)) {
+          spill_prefetch(vs, pred_v, lane < static_cast<int>(p.R), pre_lo, pre_hi);
+          pre_u = pred;
+        }
+      });
+      n_dist += nf;
+      const uint32_t cid = has ? L.cid[lane] : 0u;
+      const float cd = has ? L.cd[lane] : 0.f;
+      wave_sync();
+      pool_merge(ps, L, has, cid, cd, [&](uint32_t nx) {
+        if (nx != pred) {
+          pred = nx;
+          pred_v = adjacency_row(p, static_cast<int>(p.R), nx, pred_v);
+        }
+      });
+      range_sq8_offer(p, count, r, region, radius, has && ((aw >> (cid & 31)) & 1u) != 0u, cid, cd);
+    }
+
+    query_end(p, L, ps, qi, n_dist, n_expand, n_dist_up, n_hops_up);  // p.k = 0: the four counters
+    if (lane == 0) r.counts[qi] = count;
+    visit_end(vs);
+    wave_sync();
+  }
+}
+
+// The rerank of the range search of SQ8 codes.  One wave per (query, block of 64 stored candidates): a block
+// past the query's min(r.counts[i], r.cap) stored candidates ends at once, so a query with few candidates costs
+// one short block and a small batch with long lists still fills the CUs.  The wave stages the rerank query
+// (p.queries) in LDS once, measures its candidates on their f32 rows eight at a time -- row_distance_kernel's
+// passes: the arithmetic of rerank_kernel -- and writes the exact distance over the code distance in the append
+// list.  A candidate with d_exact > r.radii[i] (the exact radius here; NaN compares false) becomes the sort's pad
+// (FLT_MAX, kEmpty); the survivors are added to hits[i], zeroed before the launch: one popcount of a ballot and
+// one atomic per wave.  range_sort_kernel then runs as it is, with r.counts the candidate counts: the pads sort
+// behind every hit and come out as the empty tail.
+template <bool kIP>
+__global__ void __launch_bounds__(64) range_rerank_kernel(SearchParams p, RangeParams r, uint32_t *hits) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float *q = reinterpret_cast<float *>(smem);
+  uint32_t *lid = reinterpret_cast<uint32_t *>(smem + static_cast<size_t>(p.stride) * 4);
+  float *ld = reinterpret_cast<float *>(lid + 64);
+  const int lane = lane_id();
+  const uint64_t qi = blockIdx.x;
+  const uint32_t n = min(r.counts[qi], r.cap);
+  const uint32_t b = blockIdx.y * 64u;
+  if (b >= n) return;  // (uniform over the wave)
+  const uint32_t cnt = min(64u, n - b);
+  const uint64_t at = qi * r.cap + b + static_cast<uint32_t>(lane);
+  const bool has = static_cast<uint32_t>(lane) < cnt;
+  if (has) lid[lane] = r.append_ids[at];
+  const float *qsrc = p.queries + qi * p.q_stride;
+  for (uint32_t e = lane; e < p.stride; e += 64) q[e] = e < p.dim ? qsrc[e] : 0.f;
+  wave_sync();
+  for (uint32_t c = 0; c < cnt; c += 8) row_distances<kIP, 0>(p, q, lid + c, static_cast<int>(min(8u, cnt - c)), ld + c);
+  const float d = has ? ld[lane] : 0.f;
+  const bool hit = has && d <= r.radii[qi];
+  if (has) {
+    r.append_dists[at] = hit ? d : FLT_MAX;
+    if (!hit) r.append_ids[at] = kEmpty;
+  }
+  const uint64_t hm = ballot(hit);
+  if (lane == 0 && hm != 0ull) atomicAdd(hits + qi, static_cast<uint32_t>(__popcll(hm)));
+}
 }  // namespace
 
 // The range kernels: the filtered kernels' set.
@@ -2616,6 +2780,53 @@ hipError_t launch_range_sort(const RangeParams &r, uint64_t nq, hipStream_t stre
   uint32_t p2 = 1;
   while (p2 < r.cap) p2 <<= 1;
   hipLaunchKernelGGL(range_sort_kernel, dim3(static_cast<uint32_t>(nq)), dim3(256), static_cast<size_t>(p2) * 8, stream, r);
+  return hipGetLastError();
+}
+
+// The range kernels of SQ8 codes: the filtered SQ8 kernels' set.
+template <int kSpace, int... kChunks>
+static const void *range_sq8_symbol_of(int chunks, bool ip) {
+  const void *sym = nullptr;
+  ((chunks == kChunks ? (sym = ip ? reinterpret_cast<const void *>(&range_sq8_search_kernel<true, kChunks, kSpace>)
+                                  : reinterpret_cast<const void *>(&range_sq8_search_kernel<false, kChunks, kSpace>),
+                         0)
+                      : 0),
+   ...);
+  return sym;
+}
+
+static const void *range_sq8_kernel_symbol(uint32_t dim, int sq8_order, bool ip) {
+  const int chunks = search_chunks(dim, false);
+  const void *sym = sq8_order == 2 ? range_sq8_symbol_of<2, 4, 24, 30>(chunks, ip)
+                                   : range_sq8_symbol_of<1, 4, 24, 30>(chunks, ip);
+  if (sym != nullptr) return sym;
+  return sq8_order == 2 ? range_sq8_symbol_of<2, 0>(0, ip) : range_sq8_symbol_of<1, 0>(0, ip);
+}
+
+hipError_t launch_range_sq8_search(const SearchParams &p, const FilterParams &f, const RangeParams &r, int grid, int waves,
+                                   size_t lds, hipStream_t stream) {
+  SearchParams arg = p;
+  FilterParams farg = f;
+  RangeParams rarg = r;
+  void *args[] = {&arg, &farg, &rarg};
+  return hipLaunchKernel(range_sq8_kernel_symbol(p.dim, p.sq8_order, p.ip), dim3(grid), dim3(64 * waves), args, lds,
+                         stream);
+}
+
+hipError_t range_sq8_search_occupancy(uint32_t dim, int sq8_order, bool ip, int waves, size_t lds, int *blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, range_sq8_kernel_symbol(dim, sq8_order, ip), 64 * waves,
+                                                      lds);
+}
+
+hipError_t launch_range_rerank(const SearchParams &p, const RangeParams &r, uint32_t *hits, hipStream_t stream) {
+  if (p.nq == 0) return hipSuccess;
+  const size_t lds = static_cast<size_t>(p.stride) * 4 + 128 * 4;
+  const dim3 grid(static_cast<uint32_t>(p.nq), (r.cap + 63) / 64);
+  if (p.ip) {
+    hipLaunchKernelGGL(range_rerank_kernel<true>, grid, dim3(64), lds, stream, p, r, hits);
+  } else {
+    hipLaunchKernelGGL(range_rerank_kernel<false>, grid, dim3(64), lds, stream, p, r, hits);
+  }
   return hipGetLastError();
 }
 

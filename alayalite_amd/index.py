@@ -214,7 +214,7 @@ class Index:
         return self.__index.filtered_search(queries, topk, ef_search, words, groups, pool, through)
 
     def range_search(self, queries: VectorLikeBatch, radius, ef_search: int = 100, max_results: int = 1024,
-                     allow=None, groups=None, _chunk=None, expand="fixed", max_frontier: int = 4096):
+                     allow=None, groups=None, _chunk=None, expand="fixed", max_frontier: int = 4096, slack=None):
         """Every row within distance ``radius`` of each query, among the rows the graph traversal measures.
         The traversal is ``batch_search``'s at ``ef_search``; the radius does not steer it.  Every distance it
         computes for a valid row (and, with ``allow`` / ``groups`` as in ``filtered_search``, an allowed one)
@@ -229,7 +229,21 @@ class Index:
         ``lims[i + 1] - lims[i] == min(counts[i], max_results)``.  ``counts[i] > max_results`` means the
         list is truncated: it then holds the first ``max_results`` hits the traversal met, NOT the nearest
         ones -- raise ``max_results`` (1..4096) or lower the radius.  A removed row is never returned.
-        float32 graph search only: an SQ8 index is refused.
+        On a float32 index ``slack`` must stay None.
+
+        An SQ8 index needs ``slack``: a number or an array of shape (nq,), >= 0, not NaN.  Its traversal
+        measures code distances, as its ``batch_search`` does, and those differ from the exact ones in both
+        directions.  So a valid, allowed row the traversal measures is a *candidate* when its code distance is
+        ``<= float32(radius) + float32(slack)``; the first ``max_results`` candidates to turn up are measured
+        exactly on their float32 rows, and those with exact distance ``<= radius`` are the hits, returned with
+        their exact distances.  Here ``counts[i]`` is the number of hits returned, so
+        ``lims[i + 1] - lims[i] == counts[i]``, and truncation shows elsewhere:
+        ``native().last_range_candidates()[i] > max_results`` (uint32, shape (nq,), the candidates of the last
+        call) means candidates past the first ``max_results`` were never measured exactly.  ``slack=0`` misses
+        rows whose code distance overstates the exact one; a larger slack admits them at the price of more
+        candidates to rerank; ``slack=np.inf`` makes every valid, allowed measured row a candidate.  No bound on
+        the code error is assumed: the slack is the caller's choice ("Round 21").
+        ``expand="radius"`` is refused on an SQ8 index.
 
         ``expand="radius"`` lets the radius steer the search.  The traversal above runs first, unchanged;
         ``ef_search`` now only says where the flood fill starts.  Then every valid row measured within the
@@ -250,15 +264,26 @@ class Index:
         _assert(expand in ("fixed", "radius"), "expand must be 'fixed' or 'radius'")
         radius_mode = expand == "radius"
         _assert(1 <= max_frontier <= 16384, "max_frontier must be in 1..16384")
-        _assert((self.__params.quantization_type or "none").lower() != "sq8",
-                "range_search searches f32 indexes only: this index has SQ8 codes")
+        sq8 = (self.__params.quantization_type or "none").lower() == "sq8"
+        _assert(not (sq8 and radius_mode), "expand='radius' searches f32 indexes only: this index has SQ8 codes")
+        _assert(not sq8 or slack is not None,
+                "range_search of an index with SQ8 codes measures code distances: pass slack= (0 or more)")
+        _assert(sq8 or slack is None, "slack applies to SQ8 indexes only")
         _assert(1 <= max_results <= 4096, "max_results must be in 1..4096")
         _assert(ef_search >= 1, "ef_search must be >= 1")
         nq = queries.shape[0]
+        if sq8:
+            slacks = np.asarray(slack, np.float32)
+            _assert(slacks.shape in ((), (nq,)), "slack must be a number or have shape (nq,)")
+            _assert(not np.isnan(slacks).any() and (slacks >= 0).all(), "slack must be >= 0 and not NaN")
         radii = np.asarray(radius, np.float32)
         _assert(radii.shape in ((), (nq,)), "radius must be a number or have shape (nq,)")
         _assert(not np.isnan(radii).any(), "radius must not be NaN")
         radii = np.ascontiguousarray(np.broadcast_to(radii, (nq,)))
+        if sq8:
+            with np.errstate(invalid="ignore"):  # (-inf + inf: refused below)
+                code_radii = np.ascontiguousarray(radii + np.broadcast_to(slacks, (nq,)), np.float32)
+            _assert(not np.isnan(code_radii).any(), "radius + slack must not be NaN")
         words = None
         if allow is None:
             _assert(groups is None, "groups needs allow")
@@ -270,7 +295,11 @@ class Index:
         parts = []
         for lo in range(0, nq, step):
             hi = min(nq, lo + step)
-            if radius_mode:
+            if sq8:
+                counts, ids, dists, _ = self.__index.range_search_sq8(queries[lo:hi], ef_search, radii[lo:hi],
+                                                                      code_radii[lo:hi], max_results, words,
+                                                                      None if groups is None else groups[lo:hi], lo > 0)
+            elif radius_mode:
                 counts, ids, dists, _ = self.__index.range_search(queries[lo:hi], ef_search, radii[lo:hi], max_results,
                                                                   words, None if groups is None else groups[lo:hi], True,
                                                                   max_frontier, lo > 0)

@@ -355,6 +355,24 @@ class ShardedIndex:
         shard_search(self.index, self.lo, self.sq8 is not None, q_dev, k, ef, ids_dev, dists_dev, counters_dev,
                      stream, rq_dev)
 
+    def _shard_masks(self, allow, groups, nq: int, device):
+        """This shard's columns of a global mask as device words (``shard_allow_words``), and the checked
+        per-query mask indices on the device, None without ``groups``.  The caller keeps both alive until its
+        search has run."""
+        import torch
+
+        words = torch.from_numpy(shard_allow_words(allow, self.lo, self.hi).view(np.int32)).to(device)
+        if groups is None:
+            if words.shape[0] != 1:
+                raise ValueError("groups is required with more than one mask")
+            return words, None
+        g = np.ascontiguousarray(np.asarray(groups))
+        if g.shape != (nq,) or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("groups must be integers of shape (nq,)")
+        if g.size and (g.min() < 0 or g.max() >= words.shape[0]):
+            raise ValueError("groups must be below the number of masks")
+        return words, torch.from_numpy(g.astype(np.int32)).to(device)
+
     def filtered_search(self, q_dev, k: int, ef: int, allow, stream, groups=None, group=None, rerank_pool=None,
                         rq_dev=None):
         """The k nearest rows of the whole base among those a mask allows, merged over the shards.
@@ -370,19 +388,8 @@ class ShardedIndex:
         nq = q_dev.shape[0]
         if self.sq8 is None and rerank_pool is not None:
             raise ValueError("rerank_pool applies to SQ8 shards only")
-        words = torch.from_numpy(shard_allow_words(allow, self.lo, self.hi).view(np.int32)).to(q_dev.device)
-        if groups is None:
-            if words.shape[0] != 1:
-                raise ValueError("groups is required with more than one mask")
-            gptr = 0
-        else:
-            g = np.ascontiguousarray(np.asarray(groups))
-            if g.shape != (nq,) or not np.issubdtype(g.dtype, np.integer):
-                raise ValueError("groups must be integers of shape (nq,)")
-            if g.size and (g.min() < 0 or g.max() >= words.shape[0]):
-                raise ValueError("groups must be below the number of masks")
-            g_dev = torch.from_numpy(g.astype(np.int32)).to(q_dev.device)
-            gptr = g_dev.data_ptr()
+        words, g_dev = self._shard_masks(allow, groups, nq, q_dev.device)
+        gptr = 0 if g_dev is None else g_dev.data_ptr()
         ids = torch.empty((nq, k), dtype=torch.int32, device=q_dev.device)
         d = torch.empty((nq, k), dtype=torch.float32, device=q_dev.device)
         c = torch.empty((nq, 4), dtype=torch.int32, device=q_dev.device)
@@ -400,6 +407,86 @@ class ShardedIndex:
         torch.cuda.synchronize(q_dev.device)
         self.last_local = (ids, d, c)  # this shard's own answer (tests, diagnostics)
         return exchange_and_merge(ids, d, self.lo, k, group)
+
+    def range_search(self, q_dev, radius, ef: int, max_results: int, stream, allow=None, groups=None, group=None,
+                     slack=None, rq_dev=None):
+        """Every row of the whole base within ``radius`` of each query, among the rows the shards' traversals
+        measure, merged over the shards: ``(ids, dists, counts, truncated)`` as device tensors.  Each rank
+        runs ``Index.range_search``'s search on its own shard under its columns of the global mask (``allow`` /
+        ``groups`` as in ``filtered_search``, or no mask) -- f32 shards ``range_search_device``, SQ8 shards
+        ``range_search_sq8_device`` on the shard's own SQ8 space with code radius ``float32(radius) +
+        float32(slack)`` (``slack`` >= 0, a number or (nq,): required there, refused on f32 shards).  Local ids
+        become global and ``exchange_and_merge`` keeps the first ``max_results`` rows of the union by
+        (distance, global id) in ``ids`` / ``dists`` (nq x max_results; empty slots sort last).
+
+        ``counts[i]`` (int64) is the sum of the shards' counts.  ``truncated[i]`` (bool) is true when a shard
+        dropped rows -- its count (f32) or its candidates (SQ8) exceeded ``max_results`` -- or when the rows
+        the shards returned together exceed ``max_results``; when it is false the row holds the whole union
+        and its first ``counts[i]`` slots are filled.  One batch at a time, synchronised around the shard
+        search; ``last_local`` keeps this shard's own ``(ids, dists, counters, counts, candidates or None)``.
+        ``group``: the process group of the exchange; ``rq_dev``: SQ8 rerank queries, None = q_dev.  As every
+        merged search here (``exchange_and_merge``), it needs an initialised process group, also for one shard."""
+        import torch
+        import torch.distributed as dist
+
+        nq, dev, cap = q_dev.shape[0], q_dev.device, int(max_results)
+        if not 1 <= cap <= 4096:
+            raise ValueError("max_results must be in 1..4096")
+        if self.sq8 is None and slack is not None:
+            raise ValueError("slack applies to SQ8 shards only")
+        if self.sq8 is not None and slack is None:
+            raise ValueError("range_search of SQ8 shards measures code distances: pass slack= (0 or more)")
+        radii = np.asarray(radius, np.float32)
+        if radii.shape not in ((), (nq,)) or np.isnan(radii).any():
+            raise ValueError("radius must be a number or have shape (nq,), not NaN")
+        radii = np.ascontiguousarray(np.broadcast_to(radii, (nq,)))
+        r_dev = torch.from_numpy(radii).to(dev)
+        if self.sq8 is not None:
+            slacks = np.asarray(slack, np.float32)
+            if slacks.shape not in ((), (nq,)) or np.isnan(slacks).any() or (slacks < 0).any():
+                raise ValueError("slack must be a number or have shape (nq,), >= 0 and not NaN")
+            with np.errstate(invalid="ignore"):
+                code_radii = np.ascontiguousarray(radii + np.broadcast_to(slacks, (nq,)), np.float32)
+            if np.isnan(code_radii).any():
+                raise ValueError("radius + slack must not be NaN")
+            cr_dev = torch.from_numpy(code_radii).to(dev)
+        if allow is None:
+            if groups is not None:
+                raise ValueError("groups needs allow")
+            wptr, n_masks, gptr = 0, 0, 0
+        else:
+            words, g_dev = self._shard_masks(allow, groups, nq, dev)
+            wptr, n_masks, gptr = words.data_ptr(), words.shape[0], 0 if g_dev is None else g_dev.data_ptr()
+        ids = torch.empty((nq, cap), dtype=torch.int32, device=dev)
+        d = torch.empty((nq, cap), dtype=torch.float32, device=dev)
+        c = torch.empty((nq, 4), dtype=torch.int32, device=dev)
+        counts = torch.empty((nq,), dtype=torch.int32, device=dev)
+        cand = torch.empty((nq,), dtype=torch.int32, device=dev) if self.sq8 is not None else None
+        # (uploads on torch's current stream, the search on `stream`: as in filtered_search)
+        torch.cuda.synchronize(dev)
+        if self.sq8 is not None:
+            self.index.range_search_sq8_device(q_dev.data_ptr(), 0 if rq_dev is None else rq_dev.data_ptr(), nq, ef,
+                                               r_dev.data_ptr(), cr_dev.data_ptr(), cap, wptr, n_masks, gptr,
+                                               counts.data_ptr(), cand.data_ptr(), ids.data_ptr(), d.data_ptr(),
+                                               c.data_ptr(), stream)
+        else:
+            self.index.range_search_device(q_dev.data_ptr(), nq, ef, r_dev.data_ptr(), cap, wptr, n_masks, gptr,
+                                           counts.data_ptr(), ids.data_ptr(), d.data_ptr(), c.data_ptr(), stream)
+        torch.cuda.synchronize(dev)
+        self.last_local = (ids, d, c, counts, cand)  # this shard's own answer (tests, diagnostics)
+        merged_ids, merged_d = exchange_and_merge(ids, d, self.lo, cap, group)
+        # per shard: (its count, the rows it returned, whether it dropped any)
+        n_s = counts.to(torch.int64) & 0xFFFFFFFF
+        offered = n_s if cand is None else cand.to(torch.int64) & 0xFFFFFFFF
+        mine = torch.stack([n_s, torch.clamp(n_s, max=cap), (offered > cap).to(torch.int64)], 1)
+        world = dist.get_world_size(group)
+        if world > 1:
+            if dist.get_backend(group) == "gloo" and dev.type != "cpu":  # gloo gathers host tensors
+                mine = mine.cpu()
+            parts = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine, group=group)
+            mine = torch.stack(parts).sum(0).to(dev)
+        return merged_ids, merged_d, mine[:, 0], (mine[:, 2] > 0) | (mine[:, 1] > cap)
 
     def search(self, q_dev, k: int, ef: int, stream, group=None):
         import torch

@@ -290,6 +290,47 @@ int alaya_index_range_search_radius_device(alaya_index *ix, const float *d_queri
                                            uint32_t n_masks, const uint32_t *d_mask_of_query, uint32_t *d_counts,
                                            uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream,
                                            uint32_t max_frontier, uint32_t *d_more);
+/* Range search of an index with SQ8 codes: the traversal runs on the codes, the stored candidates are measured
+ * exactly.  For query i with radius r_i = radii[i], code radius c_i = code_radii[i] and cap C = max_results,
+ * 1 <= C <= 4096:
+ *   1. Traversal: alaya_index_batch_search_sq8's at the same ef -- the query encoded to codes, code-to-code
+ *      distances with no validity test, the same overlay descent, pool of ef entries, visited levels and pops --
+ *      so the four counters are equal, as for alaya_index_filtered_search_sq8.  Neither radius steers it.
+ *   2. Candidates: the subsequence, in arrival order, of the (id, d_code) the traversal hands to its pool (the
+ *      entry offers included) whose row is valid, is allowed by the query's mask when masks are given, and has
+ *      d_code <= c_i as an f32 comparison (inclusive).  cand[i] = their number, not capped; the first
+ *      min(cand[i], C) are stored.
+ *   3. Rerank: every stored candidate is measured exactly -- the raw-space f32 distance of the rerank query
+ *      (rerank_queries, NULL = queries) to the row's f32 row, the arithmetic of alaya_index_batch_search_sq8's
+ *      rerank.  A stored candidate with d_exact <= r_i (inclusive f32 comparison) is a hit; counts[i] = the number
+ *      of hits, so counts[i] <= min(cand[i], C).
+ *   4. Row i of ids / dists (nq x C) holds the hits by (exact distance, id) under float comparison, with the
+ *      exact distance bits; the remaining slots hold (0xffffffff, FLT_MAX).
+ *   5. cand[i] > C means the list is truncated: candidates past the first C to arrive were never reranked.  The
+ *      reranked ones are the first C to arrive, NOT the C nearest, as for alaya_index_range_search.
+ *   6. A repeated entry point is a candidate twice, and stays twice.
+ *   7. Code and exact distances disagree in both directions, so c_i is the caller's: c_i above r_i admits rows
+ *      whose code distance overstates the exact one (the rerank cut removes the rest); c_i = +inf makes every
+ *      valid, allowed measured row a candidate.  COS: the Index layer passes the query as given to the
+ *      traversal and the normalised one to the rerank, as for alaya_index_filtered_search_sq8.
+ * Masks, counters and ALAYA_FILTER_GRID as for alaya_index_range_search.  An index without SQ8 codes, max_results
+ * outside 1..4096, ef == 0, a NaN in radii or code_radii (host entry only), a mask shape the filtered entries
+ * refuse and a shape whose LDS does not fit are argument errors.  Environment ALAYA_RANGE_SORT=0 (diagnostics,
+ * read per launch) runs the search stage alone, to time it: cand and counters are written, counts are zero, ids
+ * and dists are left unwritten; ALAYA_RANGE_SORT=2 runs the search and the rerank without the sort: counts are
+ * written too.  alaya_index_range_search[_radius][_device] go on refusing an SQ8 index. */
+int alaya_index_range_search_sq8(alaya_index *ix, const float *queries, const float *rerank_queries, uint64_t nq,
+                                 uint32_t ef, const float *radii, const float *code_radii, uint32_t max_results,
+                                 const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
+                                 uint32_t *counts, uint32_t *cand, uint32_t *ids, float *dists, uint32_t *counters);
+/* Same on device buffers, asynchronous on `stream`: it never waits on the stream, so neither radius array is
+ * read here and a NaN simply matches nothing; the indices of d_mask_of_query are not checked.  d_counts is zeroed
+ * on the stream before the rerank adds to it; the append list is the index's own scratch. */
+int alaya_index_range_search_sq8_device(alaya_index *ix, const float *d_queries, const float *d_rerank_queries,
+                                        uint64_t nq, uint32_t ef, const float *d_radii, const float *d_code_radii,
+                                        uint32_t max_results, const uint32_t *d_allow_words, uint32_t n_masks,
+                                        const uint32_t *d_mask_of_query, uint32_t *d_counts, uint32_t *d_cand,
+                                        uint32_t *d_ids, float *d_dists, uint32_t *d_counters, void *stream);
 /* ---- device graph construction (Index.fit on the MI355X) ------------------------------------
  * Replaces HNSWBuilder::build_graph (include/index/graph/hnsw/hnsw_builder.hpp:98-194) over hnswlib
  * add_point (include/index/graph/hnsw/hnswlib.hpp:652-751), from the index's own rows

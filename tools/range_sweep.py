@@ -1,6 +1,6 @@
 """Range search on a GIST-shaped device-built index: recall, counts and the two launches' times per radius.
 
-usage: python tools/range_sweep.py [--n 1000000] [--nq 1000] [--dim 960] [--ef 387] [--reps 10] [--rounds 5] [--out FILE]
+usage: python tools/range_sweep.py [--leg fixed|radius|sq8] [--n 1000000] [--nq 1000] [--dim 960] [--ef 387] [--reps 10] [--rounds 5] [--out FILE]
 
 Radii: per query, the exact m-th neighbour distance of the flat search's top 224 (exact_search's answer), for
 m in 1, 10, 50, 200, at max_results 1024 -- so the ground truth, the rows of that answer with d <= r, is exact;
@@ -17,7 +17,11 @@ kernel the other two are built from -- --rounds rounds of --reps launches each a
 the spread (max - min) / median of each.  One JSON line per measurement; --out appends them to a file.
 
 --leg radius measures expand="radius" against expand="fixed" instead (radius_leg below): the same index,
-queries and radii, [--small-ef 64] [--sweep-efs 500,700,...] [--small-sweep-efs 64,72,...] [--max-frontier 4096]."""
+queries and radii, [--small-ef 64] [--sweep-efs 500,700,...] [--small-sweep-efs 64,72,...] [--max-frontier 4096].
+
+--leg sq8 measures range search on an SQ8 index (sq8_leg below): filter_sweep.py --leg sq8's index -- config 5's
+shape, 768-d IP text-like rows, SQ8 codes, device-built graph; --n 1000000 --dim 768 --ef 200 are this leg's
+defaults."""
 import argparse
 import json
 import os
@@ -127,21 +131,179 @@ def radius_leg(args, dev, torch, st, qd, gt_ids, gt_d, cnt, counts, emit, timed,
                   median_ms=med, spread=(max(v) - min(v)) / med, ms=sorted(v)))
 
 
+def sq8_leg(args):
+    """--leg sq8.  The radius is each query's exact m-th neighbour distance (flat search), m = 10, 50, 200, at
+    max_results 1024.  Per m: the quantiles (0.5, 0.9, 0.99, max) of d_code - d_exact over the rows inside the
+    radius that the traversal measured (the hits of a call with slack inf at max_results 4096; d_code from the
+    oracle's code distance of the encoded query and row), then one run per slack -- 0, each quantile, inf --
+    with range recall against the exact in-radius set, hits and candidates (mean, max), truncated queries, and
+    the search launch (ALAYA_RANGE_SORT=0), the search and rerank (ALAYA_RANGE_SORT=2) and the whole call, every
+    launch alternated in this process, medians of --rounds rounds with spreads; the rerank and the sort are the
+    differences of those medians (the rerank consumes the search's list, so it cannot be launched alone).
+    Then the search stage against search_sq8_device(rerank = 0), the plain mode-0 kernel (ALAYA_HELPERS=0), on
+    the same grid: with a code radius that admits nothing, and at m = 200 with the 0.99 slack."""
+    import torch
+
+    import oracle
+    from alayalite_amd import _native
+    from workloads.datasets import text_like
+
+    ext = _native._ext
+    oracle.build()
+    st = torch.cuda.current_stream()
+    n, nq, ef, cap = args.n, args.nq, args.ef, 1024
+    base, queries = text_like(n, nq, dim=args.dim)
+    print(f"rows {base.shape}", file=sys.stderr, flush=True)
+    dev = ext.DeviceIndex(0)
+    dev.set_base(base, 1)
+    dev.build_graph(32, 100, 100, 0, 0, 2)
+    print("graph built", file=sys.stderr, flush=True)
+    mn, mx = ext.sq8_train(base)
+    codes = ext.sq8_encode(base, mn, mx, 16)
+    order = int(ext.host_sq8_order())
+    dev.set_sq8(codes, mn, mx, order)
+    qcodes = ext.sq8_encode(queries, mn, mx, 16)
+    gt_ids, gt_d, _ = dev.flat_search(queries, GT)
+    print("ground truth ready", file=sys.stderr, flush=True)
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim, ef=ef, metric="ip", sq8_order=order)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    ids = torch.empty((nq, 4096), dtype=torch.int32, device="cuda")
+    d = torch.empty((nq, 4096), dtype=torch.float32, device="cuda")
+    cnt = torch.empty((nq, 4), dtype=torch.int32, device="cuda")
+    counts = torch.empty((nq,), dtype=torch.int32, device="cuda")
+    cand = torch.empty((nq,), dtype=torch.int32, device="cuda")
+    k_ids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+
+    def timed(run):
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(args.reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    def env(name, value):
+        if value is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = value
+
+    def ranged(r_t, c_t, width):
+        dev.range_search_sq8_device(qd.data_ptr(), 0, nq, ef, r_t.data_ptr(), c_t.data_ptr(), width, 0, 0, 0,
+                                    counts.data_ptr(), cand.data_ptr(), ids.data_ptr(), d.data_ptr(), cnt.data_ptr(),
+                                    st.cuda_stream)
+
+    def rows_of(t, width):
+        """The nq x width result the last call wrote at the front of a (nq, 4096) buffer."""
+        return t.reshape(-1)[:nq * width].reshape(nq, width).cpu().numpy()
+
+    def plain():
+        dev.search_sq8_device(qd.data_ptr(), 0, nq, K, ef, 0, k_ids.data_ptr(), 0, cnt.data_ptr(), st.cuda_stream)
+
+    def stat(v):
+        med = float(np.median(v))
+        return dict(median_ms=med, spread=(max(v) - min(v)) / med, ms=sorted(v))
+
+    runs = []  # (m, slack name, radii tensor, code radii tensor)
+    inf_t = torch.full((nq,), float("inf"), dtype=torch.float32, device="cuda")
+    for m in (10, 50, 200):
+        radii = np.ascontiguousarray(gt_d[:, m - 1])
+        r_t = torch.from_numpy(radii).cuda()
+        keep = gt_d[:, GT - 1] > radii  # the ground truth is complete
+        truth = [set(int(v) for v in gt_ids[i][gt_d[i] <= radii[i]]) for i in range(nq)]
+        # the measured rows inside the radius, and how far their code distances sit above the exact ones
+        ranged(r_t, inf_t, 4096)
+        torch.cuda.synchronize()
+        c, cd = counts.cpu().numpy().view(np.uint32), cand.cpu().numpy().view(np.uint32)
+        got_i, got_d = rows_of(ids, 4096).view(np.uint32), rows_of(d, 4096)
+        gaps = []
+        for i in np.flatnonzero(cd <= 4096):
+            for v, e in zip(got_i[i][:c[i]], got_d[i][:c[i]]):
+                gaps.append(float(np.float32(oracle.sq8_dist(1, qcodes[i], codes[v], mn, mx, order))) - float(e))
+        gaps = np.array(gaps)
+        qs = {"q50": float(np.quantile(gaps, 0.5)), "q90": float(np.quantile(gaps, 0.9)),
+              "q99": float(np.quantile(gaps, 0.99)), "max": float(gaps.max())}
+        emit(dict(leg="gap", m=m, rows=len(gaps), queries_left_out=int((cd > 4096).sum()), min=float(gaps.min()), **qs))
+        slacks = [("0", 0.0)] + [(k, max(v, 0.0)) for k, v in qs.items()] + [("inf", float("inf"))]
+        for name, slack in slacks:
+            c_t = torch.from_numpy((radii + np.float32(slack)).astype(np.float32)).cuda()
+            ranged(r_t, c_t, cap)
+            torch.cuda.synchronize()
+            c, cd = counts.cpu().numpy().view(np.uint32), cand.cpu().numpy().view(np.uint32)
+            got_i = rows_of(ids, cap).view(np.uint32)
+            found = want = 0
+            for i in np.flatnonzero(keep):
+                want += len(truth[i])
+                found += len(truth[i] & set(int(v) for v in got_i[i][:c[i]]))
+            emit(dict(leg="answer", m=m, slack=name, slack_value=slack, max_results=cap, recall=found / float(want or 1),
+                      truth_rows=want, left_out=int((~keep).sum()), mean_hits=float(c.mean()), max_hits=int(c.max()),
+                      mean_cand=float(cd.mean()), max_cand=int(cd.max()), truncated=int((cd > cap).sum()),
+                      stored=int(np.minimum(cd, cap).sum()), n_dist=float(cnt.cpu().numpy()[:, 0].mean()),
+                      plan={k: int(v) for k, v in dev.last_plan().items()}))
+            runs.append((m, name, r_t, c_t))
+    none_t = torch.full((nq,), -FLT_MAX, dtype=torch.float32, device="cuda")  # admits no candidate
+    q99_200 = next(r for r in runs if r[0] == 200 and r[1] == "q99")
+
+    env("ALAYA_HELPERS", "0")
+    ms = {(m, name, stage): [] for m, name, _, _ in runs for stage in ("search", "rerank+", "all")}
+    ab = {"plain": [], "range, no candidate": [], "range, m=200 q99": []}
+    for _ in range(args.rounds):
+        ab["plain"].append(timed(plain))
+        plan_plain = dev.last_plan()
+        env("ALAYA_RANGE_SORT", "0")
+        ab["range, no candidate"].append(timed(lambda: ranged(none_t, none_t, cap)))
+        plan_range = dev.last_plan()
+        ab["range, m=200 q99"].append(timed(lambda: ranged(q99_200[2], q99_200[3], cap)))
+        for m, name, r_t, c_t in runs:
+            env("ALAYA_RANGE_SORT", "0")
+            ms[(m, name, "search")].append(timed(lambda: ranged(r_t, c_t, cap)))
+            env("ALAYA_RANGE_SORT", "2")
+            ms[(m, name, "rerank+")].append(timed(lambda: ranged(r_t, c_t, cap)))
+            env("ALAYA_RANGE_SORT", None)
+            ms[(m, name, "all")].append(timed(lambda: ranged(r_t, c_t, cap)))
+    for m, name, _, _ in runs:
+        s, r, a = (ms[(m, name, k)] for k in ("search", "rerank+", "all"))
+        # the rerank and the sort are differences of launches timed one after the other in the same round
+        emit(dict(leg="time", m=m, slack=name, search=stat(s), search_rerank=stat(r), total=stat(a),
+                  rerank_ms=float(np.median(r) - np.median(s)), sort_ms=float(np.median(a) - np.median(r)),
+                  rerank_rounds=[y - x for x, y in zip(s, r)], sort_rounds=[y - x for x, y in zip(r, a)]))
+    p = stat(ab["plain"])
+    for what in ("range, no candidate", "range, m=200 q99"):
+        v = stat(ab[what])
+        emit(dict(leg="ab", what=what, plain=p, range_search=v, ratio=v["median_ms"] / p["median_ms"],
+                  plain_plan={k: int(x) for k, x in plan_plain.items()}, range_plan={k: int(x) for k, x in plan_range.items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1000000)
     ap.add_argument("--nq", type=int, default=1000)
-    ap.add_argument("--dim", type=int, default=960)
-    ap.add_argument("--ef", type=int, default=387)
+    ap.add_argument("--dim", type=int, default=0, help="0 = 960 (768 for the sq8 leg)")
+    ap.add_argument("--ef", type=int, default=0, help="0 = 387 (200 for the sq8 leg)")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", choices=("fixed", "radius"), default="fixed")
+    ap.add_argument("--leg", choices=("fixed", "radius", "sq8"), default="fixed")
     ap.add_argument("--small-ef", type=int, default=64)
     ap.add_argument("--sweep-efs", default="500,700,1000,1400,2000,2800,4000")
     ap.add_argument("--small-sweep-efs", default="64,72,80,96,112,128,160,200,256,320,387")
     ap.add_argument("--max-frontier", type=int, default=4096)
     args = ap.parse_args()
+    if args.leg == "sq8":
+        args.dim, args.ef = args.dim or 768, args.ef or 200
+        return sq8_leg(args)
+    args.dim, args.ef = args.dim or 960, args.ef or 387
 
     import torch
     from alayalite_amd import _native
