@@ -21,6 +21,7 @@
 #include "hnsw_build.h"
 #include "flat_bound.h"
 #include "flat_filtered_kernels.h"
+#include "flat_range_kernels.h"
 #include "flat_kernels.h"
 #include <cstdlib>
 #include "screen_bound.h"
@@ -144,6 +145,11 @@ struct alaya_index {
   // alaya_amd::flat_filtered_plan) and the queries ordered by mask
   DevBuf ff_ids, ff_sums, ff_count, ff_part_d, ff_part_i, ff_qlist;
   uint64_t ff_last[4] = {0, 0, 0, 0};  // alaya_index_flat_filtered_last
+  // exact range search (alaya_index_flat_range_search*): it shares the filtered scan's id list, block sums,
+  // count, query order and partial-list buffers; its own are the per-(chunk, query) hit counts and the
+  // all-ones words that stand for "no mask" on an index without a validity bitmap
+  DevBuf fr_part_n, fr_ones;
+  uint64_t fr_last[6] = {0, 0, 0, 0, 0, 0};  // alaya_index_flat_range_last
   size_t overflow_clean = 0;  // leading bytes of `overflow` known to be zero (kernels leave it clean)
   size_t stab_clean = 0;      // the same for the spill tables
   uint32_t hash_log2_override = 0;
@@ -3098,6 +3104,218 @@ int alaya_flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k, uint32
     out[2] = r.tile;
     out[3] = r.sub_queries;
     out[4] = r.partial_bytes;
+  });
+}
+
+// ---- exact range search: compaction, row-reusing f32 scan with a threshold, gather, sort (flat_range_kernels.hip) ----
+static uint64_t env_u64(const char *name) {
+  const char *e = std::getenv(name);
+  const long long v = e ? std::atoll(e) : 0;
+  return v > 0 ? static_cast<uint64_t>(v) : 0;
+}
+static uint64_t flat_range_forced_rows() { return env_u64("ALAYA_FLAT_RANGE_CHUNK_ROWS"); }
+static uint64_t flat_range_forced_staging() { return env_u64("ALAYA_FLAT_RANGE_STAGING_BYTES"); }
+
+// Every pointer but h_groups is a device pointer.  d_allow null (n_masks 0): no mask.  h_groups / d_groups as
+// do_flat_filtered's.  Masks are served one after another on `stream`; the host waits for each mask's
+// eligible-row count, never for the radii.
+static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const float *d_radii, uint32_t max_results,
+                          const uint32_t *d_allow, uint32_t n_masks, const uint32_t *h_groups, const uint32_t *d_groups,
+                          uint32_t *d_counts, uint32_t *d_ids, float *d_dists, hipStream_t stream) {
+  using namespace alaya_amd;
+  if (!ix->base.ptr) throw ArgError("index has no base vectors");
+  if (ix->generic) throw ArgError("flat range search: float32 rows only");
+  if (max_results == 0 || max_results > kFlatRangeMaxCap) throw ArgError("flat range search: max_results must be in 1..4096");
+  if (nq == 0) return;
+  if (nq > 0xffffffffull) throw ArgError("flat range search: too many queries");
+  const bool masked = d_allow != nullptr;
+  const uint32_t n_lists = masked ? n_masks : 1;  // id lists to scan: one per mask, or the one of no mask
+  std::vector<uint32_t> groups_read;
+  if (n_lists > 1 && !h_groups) {
+    groups_read.resize(nq);
+    hip_check(hipMemcpyAsync(groups_read.data(), d_groups, nq * 4, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "flat range search");
+    check_mask_indices("flat range search", groups_read.data(), nq, n_masks);
+    h_groups = groups_read.data();
+  }
+  // the queries of each mask as an index list, so outputs land in the caller's order
+  std::vector<uint64_t> first(static_cast<size_t>(n_lists) + 1, 0);
+  std::vector<uint32_t> order;
+  if (n_lists > 1) {
+    for (uint64_t i = 0; i < nq; ++i) ++first[h_groups[i] + 1];
+    for (uint32_t g = 0; g < n_lists; ++g) first[g + 1] += first[g];
+    order.resize(nq);
+    std::vector<uint64_t> at(first.begin(), first.end() - 1);
+    for (uint64_t i = 0; i < nq; ++i) order[at[h_groups[i]]++] = static_cast<uint32_t>(i);
+  } else {
+    first[1] = nq;
+  }
+  const uint64_t mask_words = (ix->n + 31) / 32;
+  const uint64_t forced = flat_range_forced_rows(), forced_staging = flat_range_forced_staging();
+  const uint32_t cus = static_cast<uint32_t>(stream_cus(ix, stream));
+  const char *stages_env = std::getenv("ALAYA_FLAT_RANGE_STAGES");
+  const int stages = stages_env ? std::atoi(stages_env) : 3;  // diagnostics: 1 = scans only, 2 = and gathers, else all
+  scratch_acquire(ix, stream);
+  ix->ff_ids.reserve(std::max<uint64_t>(ix->n, 1) * 4);
+  ix->ff_sums.reserve((flat_filtered_blocks(ix->n) + 1) * 4);
+  ix->ff_count.reserve(4);
+  if (n_lists > 1) {
+    ix->ff_qlist.reserve(nq * 4);
+    hip_check(hipMemcpyAsync(ix->ff_qlist.ptr, order.data(), nq * 4, hipMemcpyHostToDevice, stream), "upload query lists");
+    hip_check(hipStreamSynchronize(stream), "flat range search");  // `order` is pageable host memory
+  }
+  const uint32_t *d_valid = ix->has_valid ? ix->valid.as<uint32_t>() : nullptr;
+  if (!masked && !d_valid) {  // no mask, every row valid: the compaction runs over all-ones words
+    ix->fr_ones.reserve(std::max<uint64_t>(mask_words, 1) * 4);
+    hip_check(hipMemsetAsync(ix->fr_ones.ptr, 0xff, mask_words * 4, stream), "flat range search");
+  }
+  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
+  for (uint32_t g = 0; g < n_lists; ++g) {
+    const uint64_t nq_g = first[g + 1] - first[g];
+    if (nq_g == 0) continue;
+    // (mask AND validity AND below n); with no mask the validity bitmap, or the all-ones words, is the mask
+    const uint32_t *words = masked ? d_allow + static_cast<uint64_t>(g) * mask_words
+                                   : (d_valid ? d_valid : ix->fr_ones.as<uint32_t>());
+    hip_check(launch_flat_filtered_compact(words, masked ? d_valid : nullptr, ix->n, ix->ff_sums.as<uint32_t>(),
+                                           ix->ff_ids.as<uint32_t>(), ix->ff_count.as<uint32_t>(), stream),
+              "flat range compaction");
+    uint32_t m = 0;
+    hip_check(hipMemcpyAsync(&m, ix->ff_count.ptr, 4, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "flat range compaction");
+    if (m > ix->n) throw DeviceError("flat range compaction: count past the rows");
+    const FlatRangePlan plan = flat_range_plan(m, nq_g, max_results, ix->stride, cus, forced, forced_staging);
+    if (plan.tile == 0) throw ArgError("flat range search: dim too large for the LDS budget");
+    stats[0] = m;
+    stats[1] = plan.chunks;
+    stats[2] = plan.tile;
+    stats[3] = 0;
+    stats[4] += m;
+    FlatRangeParams p{};
+    p.base = ix->base.as<float>();
+    p.dim = ix->dim;
+    p.stride = ix->stride;
+    p.ip = ix->metric == ALAYA_METRIC_L2 ? 0 : 1;
+    p.queries = d_q;
+    p.q_stride = ix->dim;
+    p.radii = d_radii;
+    p.q_list = n_lists > 1 ? ix->ff_qlist.as<uint32_t>() : nullptr;
+    p.ids = ix->ff_ids.as<uint32_t>();
+    p.n_ids = m;
+    p.chunk_rows = plan.chunk_rows;
+    p.chunks = plan.chunks;
+    p.tile = static_cast<uint32_t>(plan.tile);
+    p.cap = max_results;
+    p.slots = static_cast<uint32_t>(plan.slots);
+    p.out_counts = d_counts;
+    p.out_ids = d_ids;
+    p.out_dists = d_dists;
+    if (m) {
+      // (a buffer that grows is freed first, which waits for the launches that still read it)
+      const uint64_t pairs = plan.chunks * std::min<uint64_t>(nq_g, plan.sub_queries);
+      ix->ff_part_d.reserve(pairs * plan.slots * 4);
+      ix->ff_part_i.reserve(pairs * plan.slots * 4);
+      ix->fr_part_n.reserve(pairs * 4);
+      p.part_d = ix->ff_part_d.as<float>();
+      p.part_i = ix->ff_part_i.as<uint32_t>();
+      p.part_n = ix->fr_part_n.as<uint32_t>();
+    }
+    for (uint64_t sb = 0; sb < nq_g; sb += plan.sub_queries) {
+      p.q_first = first[g] + sb;
+      p.nq = std::min<uint64_t>(plan.sub_queries, nq_g - sb);
+      if (m) {
+        hip_check(launch_flat_range_scan(p, stream), "flat range scan");
+        ++stats[3];
+        ++stats[5];
+      }
+      if (stages >= 2) hip_check(launch_flat_range_gather(p, stream), "flat range gather");  // m = 0: empty rows
+    }
+  }
+  if (stages >= 3) {
+    // the gather left each row's first min(count, cap) hits in id order: range_sort_kernel orders them in place
+    // (a workgroup reads its whole row into LDS before it writes any of it)
+    RangeParams r{};
+    r.radii = d_radii;
+    r.cap = max_results;
+    r.append_ids = d_ids;
+    r.append_dists = d_dists;
+    r.counts = d_counts;
+    r.out_ids = d_ids;
+    r.out_dists = d_dists;
+    hip_check(launch_range_sort(r, nq, stream), "flat range sort");
+  }
+  scratch_release(ix, stream);
+  std::memcpy(ix->fr_last, stats, sizeof(stats));
+}
+
+int alaya_index_flat_range_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, const float *d_radii,
+                                         uint32_t max_results, const uint32_t *d_allow_words, uint32_t n_masks,
+                                         const uint32_t *d_mask_of_query, uint32_t *d_counts, uint32_t *d_ids,
+                                         float *d_dists, void *stream) {
+  return guarded([&] {
+    if (!ix || (nq && (!d_queries || !d_radii || !d_counts || !d_ids || !d_dists))) throw ArgError("invalid arguments");
+    check_range_masks(nq, d_allow_words, n_masks, d_mask_of_query, false);  // (do_flat_range reads the indices back)
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    do_flat_range(ix, d_queries, nq, d_radii, max_results, d_allow_words, n_masks, nullptr, d_mask_of_query, d_counts,
+                  d_ids, d_dists, static_cast<hipStream_t>(stream));
+  });
+}
+
+int alaya_index_flat_range_search(alaya_index *ix, const float *queries, uint64_t nq, const float *radii,
+                                  uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
+                                  const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists) {
+  return guarded([&] {
+    if (!ix || (nq && (!queries || !radii || !counts || !ids || !dists))) throw ArgError("invalid arguments");
+    check_range_masks(nq, allow_words, n_masks, mask_of_query, true);
+    for (uint64_t i = 0; i < nq; ++i)
+      if (radii[i] != radii[i]) throw ArgError("flat range search: a radius is NaN");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    check_range_cap(max_results);  // (before the result buffers are sized by it)
+    if (nq == 0) {
+      do_flat_range(ix, nullptr, 0, nullptr, max_results, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                    ix->stream);  // the index's own refusals
+      return;
+    }
+    scratch_acquire(ix, ix->stream);  // the upload buffers below are the index's, shared with other launches
+    const float *d_q = stage_queries(ix, queries, nq, max_results, "upload queries", /*dists=*/true, /*counters=*/false);
+    const uint32_t *d_allow = allow_words ? stage_masks(ix, allow_words, n_masks) : nullptr;
+    ix->range_radii.reserve(nq * 4);
+    ix->range_cnt.reserve(nq * 4);
+    hip_check(hipMemcpyAsync(ix->range_radii.ptr, radii, nq * 4, hipMemcpyHostToDevice, ix->stream), "upload radii");
+    // the scan orders the queries by mask on the host: it takes the host's indices, and only where there is more
+    // than one mask to order by
+    do_flat_range(ix, d_q, nq, ix->range_radii.as<float>(), max_results, d_allow, n_masks,
+                  n_masks > 1 ? mask_of_query : nullptr, nullptr, ix->range_cnt.as<uint32_t>(), ix->id_buf.as<uint32_t>(),
+                  ix->dist_buf.as<float>(), ix->stream);
+    fetch_results(ix, nq, max_results, ids, dists, nullptr);
+    hip_check(hipMemcpyAsync(counts, ix->range_cnt.ptr, nq * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+    stream_sync(ix, "flat range search");
+  });
+}
+
+int alaya_index_flat_range_last(const alaya_index *ix, uint64_t *out) {
+  return guarded([&] {
+    if (!ix || !out) throw ArgError("invalid arguments");
+    std::memcpy(out, ix->fr_last, sizeof(ix->fr_last));
+  });
+}
+
+int alaya_flat_range_plan(uint64_t n_eligible, uint64_t nq, uint32_t max_results, uint32_t stride, uint32_t cus,
+                          uint64_t *out) {
+  return guarded([&] {
+    if (!out) throw ArgError("invalid arguments");
+    if (max_results == 0 || max_results > alaya_amd::kFlatRangeMaxCap)
+      throw ArgError("flat range plan: max_results must be in 1..4096");
+    const alaya_amd::FlatRangePlan r = alaya_amd::flat_range_plan(n_eligible, nq, max_results, stride, cus,
+                                                                  flat_range_forced_rows(), flat_range_forced_staging());
+    if (r.tile == 0) throw ArgError("flat range plan: dim too large for the LDS budget");
+    out[0] = r.chunk_rows;
+    out[1] = r.chunks;
+    out[2] = r.tile;
+    out[3] = r.sub_queries;
+    out[4] = r.slots;
+    out[5] = r.staging_bytes;
   });
 }
 

@@ -403,6 +403,34 @@ class PyIndexInterface : public LaunchControls {
     return py::make_tuple(widen_ids(ids32, nq, topk, true), dists);
   }
 
+  // --- extra (not in the reference binding): every valid (and, with masks, allowed) row within `radius` (a
+  // number or one per query) of the query, by an exact scan of the rows (alaya_index_flat_range_search).
+  // Returns (counts[nq], ids[nq, max_results], dists[nq, max_results]): counts are exact and not capped, row i
+  // holds min(counts[i], max_results) hits by (distance, id) -- the ones with the smallest ids when there are
+  // more -- then empty slots as exact_search's.  The query forms are exact_search's; allow_words /
+  // mask_of_query as for range_search.  An SQ8 index is scanned on its f32 rows.
+  py::object exact_range_search(py::array queries, py::object radius, uint32_t max_results, py::object allow_words,
+                                py::object mask_of_query) {
+    if (!graph_) throw std::runtime_error("Index is not init yet");
+    py::array q = prepare_queries(queries);
+    const uint64_t nq = q.shape(0);
+    U32Array words;
+    const Masks m = parse_range_masks(allow_words, words, mask_of_query, n_, nq);
+    const std::vector<float> radii = parse_radii(radius, nq);
+    if (max_results == 0 || max_results > 4096) throw py::value_error("max_results must be in 1..4096");
+    std::vector<uint32_t> ids32(nq * max_results);
+    py::array_t<float> dists = out2d<float>(nq, max_results);
+    py::array_t<uint32_t> counts(static_cast<py::ssize_t>(nq));
+    uint32_t *cp = counts.mutable_data();
+    float *dp = dists.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_flat_range_search(ix_, static_cast<const float *>(q.data()), nq, radii.data(), max_results, m.words,
+                                          m.n_masks, m.of_query, cp, ids32.data(), dp));
+    }
+    return py::make_tuple(counts, widen_ids(ids32, nq, max_results, true), dists);
+  }
+
   // --- extra (not in the reference binding): every row the traversal of batch_search at `ef` measures within
   // `radius` (a number or one per query) of the query (alaya_index_range_search; f32 indexes only).  Returns
   // (counts[nq], ids[nq, max_results], dists[nq, max_results], counters[nq, 4]): row i holds its first
@@ -1383,6 +1411,44 @@ class DeviceIndex : public LaunchControls {
     check(alaya_index_flat_filtered_last(ix_, o));
     return py::make_tuple(o[0], o[1], o[2], o[3]);
   }
+  // every valid (and allowed) row within `radius` (a number or one per query) of the query, by an exact scan
+  // (alaya_index_flat_range_search): (counts[nq], ids[nq, max_results], dists[nq, max_results]); words / groups as
+  // range_search's masks, None for no mask
+  py::tuple flat_range_search(F32Array q, py::object radius, uint32_t max_results, py::object allow_words,
+                              py::object mask_of_query) {
+    const uint64_t nq = q.shape(0);
+    U32Array words;
+    const Masks m = parse_range_masks(allow_words, words, mask_of_query, rows(), nq);
+    const std::vector<float> radii = parse_radii(radius, nq);
+    if (max_results == 0 || max_results > 4096) throw py::value_error("max_results must be in 1..4096");
+    py::array_t<uint32_t> ids = out2d<uint32_t>(nq, max_results);
+    py::array_t<float> d = out2d<float>(nq, max_results);
+    py::array_t<uint32_t> counts(static_cast<py::ssize_t>(nq));
+    const float *qp = q.data();
+    uint32_t *ip = ids.mutable_data();
+    float *dp = d.mutable_data();
+    uint32_t *np = counts.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_flat_range_search(ix_, qp, nq, radii.data(), max_results, m.words, m.n_masks, m.of_query, np, ip, dp));
+    }
+    return py::make_tuple(counts, ids, d);
+  }
+  void flat_range_search_device(uintptr_t q, uint64_t nq, uintptr_t radii, uint32_t max_results, uintptr_t allow_words,
+                                uint32_t n_masks, uintptr_t mask_of_query, uintptr_t counts, uintptr_t ids, uintptr_t dists,
+                                uintptr_t stream) {
+    check(alaya_index_flat_range_search_device(ix_, dptr<const float>(q), nq, dptr<const float>(radii), max_results,
+                                               dptr<const uint32_t>(allow_words), n_masks,
+                                               dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(counts),
+                                               dptr<uint32_t>(ids), dptr<float>(dists), dptr<void>(stream)));
+  }
+  // of the last mask: (eligible rows, row chunks, query tile, scan launches); over all masks: (eligible rows,
+  // scan launches)
+  py::tuple flat_range_last() const {
+    uint64_t o[6] = {0, 0, 0, 0, 0, 0};
+    check(alaya_index_flat_range_last(ix_, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3], o[4], o[5]);
+  }
   int flat_contraction() const {
     int c = -1;
     check(alaya_index_flat_last_contraction(ix_, &c));
@@ -1498,6 +1564,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("exact_search", &PyIndexInterface::exact_search, py::arg("queries"), py::arg("topk"))
       .def("exact_search_filtered", &PyIndexInterface::exact_search_filtered, py::arg("queries"), py::arg("topk"),
            py::arg("allow_words"), py::arg("mask_of_query") = py::none())
+      .def("exact_range_search", &PyIndexInterface::exact_range_search, py::arg("queries"), py::arg("radius"),
+           py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none())
       .def("save", &PyIndexInterface::save, py::arg("index_path"), py::arg("data_path"),
            py::arg("quant_path") = std::string())
       .def("load", &PyIndexInterface::load, py::arg("index_path"), py::arg("data_path"),
@@ -1589,6 +1657,10 @@ PYBIND11_MODULE(_alayalitepy, m) {
            py::arg("allow_words"), py::arg("mask_of_query") = py::none())
       .def("flat_search_filtered_device", &DeviceIndex::flat_search_filtered_device)
       .def("flat_filtered_last", &DeviceIndex::flat_filtered_last)
+      .def("flat_range_search", &DeviceIndex::flat_range_search, py::arg("queries"), py::arg("radii"),
+           py::arg("max_results"), py::arg("words") = py::none(), py::arg("groups") = py::none())
+      .def("flat_range_search_device", &DeviceIndex::flat_range_search_device)
+      .def("flat_range_last", &DeviceIndex::flat_range_last)
       .def("flat_diag", &DeviceIndex::flat_diag)
       .def("flat_contraction", &DeviceIndex::flat_contraction)
       .def("search_sq8_device", &DeviceIndex::search_sq8_device)
@@ -1659,6 +1731,13 @@ PYBIND11_MODULE(_alayalitepy, m) {
     check(alaya_flat_filtered_plan(n_allowed, nq, k, stride, cus, o));
     return py::make_tuple(o[0], o[1], o[2], o[3], o[4]);
   }, py::arg("n_allowed"), py::arg("nq"), py::arg("k"), py::arg("stride"), py::arg("cus"));
+  // the exact range scan's launch plan on the host (alaya_flat_range_plan): (rows per chunk, chunks, query
+  // tile, queries per scan launch, stored hits per (chunk, query), staging bytes)
+  m.def("flat_range_plan", [](uint64_t n_eligible, uint64_t nq, uint32_t max_results, uint32_t stride, uint32_t cus) {
+    uint64_t o[6] = {0, 0, 0, 0, 0, 0};
+    check(alaya_flat_range_plan(n_eligible, nq, max_results, stride, cus, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3], o[4], o[5]);
+  }, py::arg("n_eligible"), py::arg("nq"), py::arg("max_results"), py::arg("stride"), py::arg("cus"));
   // the flat search's inner-product bound on the host (flat_bound.h): slack per query, and the test
   m.def("flat_ip_slack", [](int contraction, uint32_t k_acc, F32Array q_norm2, CArray<int> q_exp, float b_max,
                             int base_exp) {

@@ -10,7 +10,7 @@ import numpy as np
 from ._native import PyIndexInterface as _PyIndexInterface
 from .common import VectorLike, VectorLikeBatch, _assert
 from .schema import IndexParams, load_schema
-from .utils import pack_allow, range_csr
+from .utils import exact_range_args, pack_allow, range_csr
 
 
 class Index:
@@ -306,6 +306,49 @@ class Index:
             else:
                 counts, ids, dists, _ = self.__index.range_search(queries[lo:hi], ef_search, radii[lo:hi], max_results,
                                                                   words, None if groups is None else groups[lo:hi])
+            parts.append((counts,) + range_csr(counts, ids, dists, max_results)[1:])
+        if not parts:
+            return (np.zeros(1, np.int64), np.zeros(0, self.__params.id_type), np.zeros(0, np.float32),
+                    np.zeros(0, np.uint32))
+        counts = np.concatenate([p[0] for p in parts])
+        lims = np.zeros(nq + 1, np.int64)
+        np.cumsum(np.minimum(counts.astype(np.int64), max_results), out=lims[1:])
+        return lims, np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts]), counts
+
+    def exact_range_search(self, queries: VectorLikeBatch, radius, max_results: int = 1024, allow=None, groups=None,
+                           _chunk=None):
+        """Every row within distance ``radius`` of each query, exactly: a scan of the rows, no graph.  A row
+        is a hit when it is valid (not removed), allowed by the query's mask (``allow`` / ``groups`` as in
+        ``filtered_search``; no ``allow`` = every row) and its distance is ``<= radius``, inclusive.  The
+        distance is ``exact_search``'s, bit for bit: the index's metric in f32 (squared L2, ``-(q.b)`` for
+        IP, the same on normalised rows and queries for COS); an SQ8 index is scanned on its float32 rows.
+        ``radius`` is a number or an array of shape (nq,), not NaN; ``-inf`` matches nothing, ``inf`` every
+        eligible row.  This is the ground truth for the range recall of ``range_search``, and the call for
+        near-duplicate, threshold-join and clustering queries that need all of the rows.
+
+        Returns ``range_search``'s form ``(lims, ids, dists, counts)``: ``counts[i]`` (uint32) is the exact
+        number of hits, never capped; query i's rows ``ids[lims[i]:lims[i + 1]]`` are
+        ``min(counts[i], max_results)`` of them ordered by (distance, id).  ``counts[i] > max_results``
+        (1..4096) means the list is truncated: it then holds the ``max_results`` hits with the SMALLEST IDS,
+        not the nearest ones (the scan meets rows in ascending id) -- lower the radius, or split the rows
+        with masks.  The result depends on the inputs alone.
+
+        The cost is eligible rows x queries: it is the f32 scan of ``exact_search(allow=)``, each row reused
+        across a tile of 16 queries, and not the MFMA flat scan of the unmasked ``exact_search``
+        ("Round 22")."""
+        self._check_queries(queries, 2, "queries")
+        nq = queries.shape[0]
+        radii = exact_range_args(nq, radius, max_results, allow, groups)
+        words = None
+        if allow is not None:
+            words, groups = self._masks(allow, groups, nq)
+        # chunks of queries: at most 2^26 padded result slots per call
+        step = max(1, (1 << 26) // max_results) if _chunk is None else int(_chunk)
+        parts = []
+        for lo in range(0, nq, step):
+            hi = min(nq, lo + step)
+            counts, ids, dists = self.__index.exact_range_search(queries[lo:hi], radii[lo:hi], max_results, words,
+                                                                 None if groups is None else groups[lo:hi])
             parts.append((counts,) + range_csr(counts, ids, dists, max_results)[1:])
         if not parts:
             return (np.zeros(1, np.int64), np.zeros(0, self.__params.id_type), np.zeros(0, np.float32),

@@ -6,7 +6,7 @@ import hashlib
 
 import numpy as np
 
-__all__ = ["load_fvecs", "load_ivecs", "calc_recall", "calc_gt", "calc_gt_device", "md5", "pack_allow", "range_csr"]
+__all__ = ["load_fvecs", "load_ivecs", "calc_recall", "calc_gt", "calc_gt_device", "calc_range_gt_device", "md5", "pack_allow", "range_csr"]
 
 
 def _load_vecs(file_path, dtype):
@@ -80,6 +80,64 @@ def calc_gt_device(data, query, topk, device=0, metric="l2", allow=None):
         return ids.astype(np.int32), dists
     ids, dists, _ = ix.flat_search(query, topk)
     return ids.astype(np.int32), dists
+
+
+def exact_range_args(nq, radius, max_results, allow=None, groups=None):
+    """The checks ``Index.exact_range_search`` and ``calc_range_gt_device`` make before anything reaches the
+    device: ``radius`` a number or an array of shape (nq,), not NaN; 1 <= ``max_results`` <= 4096; ``groups``
+    only with ``allow``.  Returns the radii as a contiguous float32 array of shape (nq,)."""
+    radii = np.asarray(radius, np.float32)
+    if radii.shape not in ((), (nq,)):
+        raise ValueError(f"radius must be a number or have shape (nq,) = ({nq},), got {radii.shape}")
+    if np.isnan(radii).any():
+        raise ValueError("radius must not be NaN")
+    if not 1 <= int(max_results) <= 4096:
+        raise ValueError(f"max_results must be in 1..4096, got {max_results}")
+    if allow is None and groups is not None:
+        raise ValueError("groups needs allow")
+    return np.ascontiguousarray(np.broadcast_to(radii, (nq,)))
+
+
+def calc_range_gt_device(data, query, radius, max_results=4096, device=0, metric="l2", allow=None):
+    """Every row within ``radius`` of each query, exactly, on the MI355X: ``Index.exact_range_search`` on raw
+    arrays, beside ``calc_gt_device``.  A row is a hit when its f32 distance (``calc_gt_device``'s: l2_sqr,
+    -(q.b) for "ip", the same on normalised copies for "cos") is ``<= radius``, inclusive; ``radius`` is a
+    number or an array of shape (nq,), not NaN.  ``allow`` (a bool array over the rows, shape (n,)) restricts
+    the hits to the allowed rows.  Returns ``(lims, ids int32, dists float32, counts uint32)`` in
+    ``Index.range_search``'s form: ``counts[i]`` is the exact number of hits, never capped, and query i's rows
+    ``ids[lims[i]:lims[i + 1]]`` are ``min(counts[i], max_results)`` of them by (distance, id).  Where
+    ``counts[i] > max_results`` (1..4096) the list is truncated to the hits with the smallest ids, NOT the
+    nearest.  The cost is rows x queries on the f32 scan of ``calc_gt_device(allow=)``, not the MFMA scan."""
+    if metric not in _GT_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_GT_METRICS)}, got {metric!r}")
+    query = np.ascontiguousarray(query, dtype=np.float32)
+    radii = exact_range_args(query.shape[0], radius, max_results)
+    words = None
+    if allow is not None:
+        allow = np.asarray(allow)
+        if allow.ndim != 1:
+            raise ValueError(f"allow must have shape (n,), got {allow.shape}")
+        words = pack_allow(allow, np.shape(data)[0])
+    from . import _native
+
+    data = np.ascontiguousarray(data, dtype=np.float32)
+    if metric == "cos":
+        data = _native._ext.normalize_rows(data)
+        query = _native._ext.normalize_rows(query)
+    ix = _native._ext.DeviceIndex(device)
+    ix.set_base(data, _GT_METRICS[metric])
+    step = max(1, (1 << 26) // max_results)  # at most 2^26 padded result slots per call
+    lims, ids, dists, counts = [np.zeros(1, np.int64)], [], [], []
+    for lo in range(0, query.shape[0], step):
+        c, i, d = ix.flat_range_search(query[lo:lo + step], radii[lo:lo + step], max_results, words)
+        part = range_csr(c, i, d, max_results)
+        lims.append(part[0][1:] + lims[-1][-1])
+        ids.append(part[1].astype(np.int32))
+        dists.append(part[2])
+        counts.append(c)
+    if not counts:
+        return lims[0], np.zeros(0, np.int32), np.zeros(0, np.float32), np.zeros(0, np.uint32)
+    return np.concatenate(lims), np.concatenate(ids), np.concatenate(dists), np.concatenate(counts)
 
 
 def pack_allow(allow, n):

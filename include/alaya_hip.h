@@ -523,6 +523,64 @@ int alaya_index_flat_filtered_last(const alaya_index *ix, uint64_t *out);
  * outside 1..224 or the rows are too wide for the LDS. */
 int alaya_flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k, uint32_t stride, uint32_t cus,
                              uint64_t *out);
+/* ---- exact range search: every eligible row within a radius, by a scan of the rows ---------------
+ * The exact counterpart of alaya_index_range_search (no reference counterpart: find_exact_gt,
+ * include/utils/evaluate.hpp:29-62, keeps the k nearest).  For query i with radius r_i = radii[i] and cap
+ * C = max_results, 1 <= C <= 4096:
+ * 1. Eligible rows: every row below the index's row count that is valid (the validity bitmap) and, when masks
+ *    are given, allowed by the query's mask.  allow_words, n_masks, mask_of_query: alaya_index_filtered_search's
+ *    format (bits past n ignored); allow_words == NULL with n_masks == 0 means no mask, as for
+ *    alaya_index_range_search.  No graph is needed; an index with SQ8 codes is scanned on its f32 rows;
+ *    ALAYA_DIST_GENERIC bases are refused.
+ * 2. Distance: the index's metric in f32 in the reference's order from the start (l2_sqr_avx2; ip_sqr_avx2
+ *    negated for IP and COS) -- the bits of alaya_index_flat_search_filtered and alaya_index_distances.  No
+ *    approximate contraction, no bound, no flag, no recompute.
+ * 3. Hits: a row is a hit when d <= r_i as an f32 comparison, inclusive.  A radius of -inf matches nothing;
+ *    +inf and FLT_MAX match every eligible row with a finite distance.  A NaN radius is ALAYA_ERR_ARG on the
+ *    host entry; on the device entry it matches nothing, and the device entry never waits on the stream to
+ *    read radii.
+ * 4. counts[i] (uint32) is the exact number of hits, never capped.
+ * 5. Row i of ids / dists (nq x C) holds min(counts[i], C) hits ordered by (distance, id) under float
+ *    comparison (-0.0 ties with +0.0, the id decides), with the distance bits of rule 2; the remaining slots
+ *    hold (0xffffffff, FLT_MAX).  counts[i] > C means the list is truncated: it then holds the C hits with the
+ *    smallest ids, because the scan meets rows in ascending id -- alaya_index_range_search's "first C to
+ *    arrive, not the C nearest", with a fixed arrival order.
+ * 6. The result is a function of the inputs alone: not of the row chunking, the grid, the query tile, or how
+ *    a batch is split over launches.  Each (row chunk, query) pair has its own hit list and count, written by
+ *    one wave in id order, and the lists are concatenated in chunk order.
+ * 7. No workgroup waits for another.
+ * Masks are served one after another: (mask AND validity) is compacted into an ascending id list (no mask:
+ * the validity bitmap, or all-ones words), the mask's queries are scanned against chunks of that list, a
+ * gather joins the chunk lists and range_sort_kernel orders each row.  The work grows with eligible rows x
+ * queries; this is the f32 scan of alaya_index_flat_search_filtered, not the MFMA scan of
+ * alaya_index_flat_search.  Environment (diagnostics, read per call; results never depend on them):
+ * ALAYA_FLAT_RANGE_CHUNK_ROWS=r forces the id-list entries per chunk, ALAYA_FLAT_RANGE_STAGING_BYTES=b the
+ * cap on one scan launch's staging (default 256 MiB; raised to what one query tile of one chunk needs),
+ * ALAYA_FLAT_RANGE_STAGES=1 | 2 stops after the scans | the gathers, to time them (outputs then incomplete). */
+int alaya_index_flat_range_search(alaya_index *ix, const float *queries, uint64_t nq, const float *radii,
+                                  uint32_t max_results, const uint32_t *allow_words, uint32_t n_masks,
+                                  const uint32_t *mask_of_query, uint32_t *counts, uint32_t *ids, float *dists);
+/* Same on device buffers, launched on `stream`.  The call waits on `stream` for each mask's eligible-row count
+ * (the scan's grid depends on it) and, with more than one mask, reads d_mask_of_query back and checks it; when
+ * it returns, the last launches may still be running.  Every slot of d_counts, d_ids and d_dists is written. */
+int alaya_index_flat_range_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, const float *d_radii,
+                                         uint32_t max_results, const uint32_t *d_allow_words, uint32_t n_masks,
+                                         const uint32_t *d_mask_of_query, uint32_t *d_counts, uint32_t *d_ids,
+                                         float *d_dists, void *stream);
+/* Introspection of the last call above: of the last mask that had queries, out[0] = eligible rows, out[1] = row
+ * chunks, out[2] = query tile, out[3] = scan launches; over all masks, out[4] = eligible rows summed,
+ * out[5] = scan launches. */
+int alaya_index_flat_range_last(const alaya_index *ix, uint64_t *out);
+/* The range scan's launch plan as pure host arithmetic (no device): for n_eligible rows, nq queries of one
+ * mask, the cap, rows of `stride` floats and `cus` compute units, out[0] = rows per chunk (a multiple of 32;
+ * ALAYA_FLAT_RANGE_CHUNK_ROWS rounded up to one, unless a single query tile's staging would then pass the
+ * cap), out[1] = chunks (no more than fill the CUs twice over at this tile), out[2] = queries per workgroup
+ * (4, 8 or 16), out[3] = queries per scan launch (a multiple of out[2]), out[4] = stored hits per (chunk,
+ * query) = min(max_results, out[0]), out[5] = staging bytes of one launch = out[1] x min(nq, out[3]) x
+ * (8 out[4] + 4), within the staging cap for any nq.  ALAYA_ERR_ARG if max_results is outside 1..4096 or the
+ * rows are too wide for the LDS. */
+int alaya_flat_range_plan(uint64_t n_eligible, uint64_t nq, uint32_t max_results, uint32_t stride, uint32_t cus,
+                          uint64_t *out);
 /* Tuning / introspection: LDS visited-table size (log2 slots, 6..16; 0 = automatic) and layout
  * (0 = automatic, 1 = compact 16-bit slots, 2 = 32-bit id slots, 3 = compact with probe distance
  * capped at 2, a test hook for the spill-on-long-probe path).  Results never depend on either:

@@ -1,6 +1,6 @@
 """Range search on a GIST-shaped device-built index: recall, counts and the two launches' times per radius.
 
-usage: python tools/range_sweep.py [--leg fixed|radius|sq8] [--n 1000000] [--nq 1000] [--dim 960] [--ef 387] [--reps 10] [--rounds 5] [--out FILE]
+usage: python tools/range_sweep.py [--leg fixed|radius|sq8|exact] [--n 1000000] [--nq 1000] [--dim 960] [--ef 387] [--reps 10] [--rounds 5] [--out FILE]
 
 Radii: per query, the exact m-th neighbour distance of the flat search's top 224 (exact_search's answer), for
 m in 1, 10, 50, 200, at max_results 1024 -- so the ground truth, the rows of that answer with d <= r, is exact;
@@ -21,7 +21,11 @@ queries and radii, [--small-ef 64] [--sweep-efs 500,700,...] [--small-sweep-efs 
 
 --leg sq8 measures range search on an SQ8 index (sq8_leg below): filter_sweep.py --leg sq8's index -- config 5's
 shape, 768-d IP text-like rows, SQ8 codes, device-built graph; --n 1000000 --dim 768 --ef 200 are this leg's
-defaults."""
+defaults.
+
+--leg exact measures the exact range scan (exact_leg below): against the exact filtered k-NN with a radius that
+admits nothing, its scan, gather and sort per radius and cap, and -- with the exact call as the ground truth, no
+query left out -- the range recall of both graph range searches, [--target-rows 1000] [--no-graph]."""
 import argparse
 import json
 import os
@@ -285,6 +289,172 @@ def sq8_leg(args):
                   plain_plan={k: int(x) for k, x in plan_plain.items()}, range_plan={k: int(x) for k, x in plan_range.items()}))
 
 
+def exact_leg(args):
+    """--leg exact: the exact range scan (DeviceIndex.flat_range_search_device), GIST-shaped rows, squared L2.
+    Every launch is timed with device events after 3 warm-ups, --rounds rounds of --reps launches, all the
+    launches of a comparison alternated in this process; medians with the spread (max - min) / median.
+      scan    a radius that admits nothing (-1) at max_results 1024 against flat_search_filtered_device (k 10) at
+              the same mask, shares 0.01, 0.1 and 1: the same loads and FMAs without the k-best lists.
+      stores  no mask; radii at each query's exact 10th and 200th neighbour distance and +inf, max_results 1024
+              and 4096; the scans alone (ALAYA_FLAT_RANGE_STAGES=1), with the gathers (2) and the whole call:
+              gather and sort are differences of medians.
+      recall  (skipped with --no-graph) the exact call is the ground truth, no query left out: range recall of
+              range_search expand="fixed" and "radius" at ef --small-ef and --ef, max_results 4096, at the m = 200
+              radius and at a per-query radius whose exact count is about --target-rows (bisection on counts)."""
+    import torch
+    from alayalite_amd import _native
+    from alayalite_amd.utils import pack_allow
+    from workloads.datasets import gist_like
+
+    ext = _native._ext
+    st = torch.cuda.current_stream()
+    n, nq = args.n, args.nq
+    base, queries = gist_like(n, nq, dim=args.dim)
+    print("rows ready", file=sys.stderr, flush=True)
+    dev = ext.DeviceIndex(0)
+    dev.set_base(base, 0)
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    def env(name, value):
+        if value is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = value
+
+    def timed(run):
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(args.reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    def stat(v):
+        med = float(np.median(v))
+        return dict(median_ms=med, spread=(max(v) - min(v)) / med, ms=sorted(v))
+
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    counts = torch.empty((nq,), dtype=torch.int32, device="cuda")
+    ids = torch.empty((nq, 4096), dtype=torch.int32, device="cuda")
+    d = torch.empty((nq, 4096), dtype=torch.float32, device="cuda")
+    k_ids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+    k_d = torch.empty((nq, K), dtype=torch.float32, device="cuda")
+
+    def ranged(radii_t, cap, words=None):
+        dev.flat_range_search_device(qd.data_ptr(), nq, radii_t.data_ptr(), cap, 0 if words is None else words.data_ptr(),
+                                     0 if words is None else 1, 0, counts.data_ptr(), ids.data_ptr(), d.data_ptr(),
+                                     st.cuda_stream)
+
+    def exact(radii, cap):
+        """(counts, ids, dists) of the exact call on the host; ids / dists (nq, cap)."""
+        ranged(torch.from_numpy(np.ascontiguousarray(radii, np.float32)).cuda(), cap)
+        torch.cuda.synchronize()
+        flat = ids.flatten()[:nq * cap].view(nq, cap), d.flatten()[:nq * cap].view(nq, cap)
+        return counts.cpu().numpy().view(np.uint32).copy(), flat[0].cpu().numpy().view(np.uint32), flat[1].cpu().numpy()
+
+    # ---- scan: a radius that admits nothing against the exact filtered k-NN ---------------------------
+    nothing = torch.full((nq,), -1.0, dtype=torch.float32, device="cuda")
+    rng = np.random.default_rng(5)
+    for share in (0.01, 0.1, 1.0):
+        allow = rng.random(n) < share if share < 1 else np.ones(n, bool)
+        words = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+
+        def knn():
+            dev.flat_search_filtered_device(qd.data_ptr(), nq, K, words.data_ptr(), 1, 0, k_ids.data_ptr(), k_d.data_ptr(),
+                                            st.cuda_stream)
+
+        ms = {"knn": [], "range": []}
+        for _ in range(args.rounds):
+            ms["knn"].append(timed(knn))
+            ms["range"].append(timed(lambda: ranged(nothing, 1024, words)))
+        torch.cuda.synchronize()
+        assert int(counts.cpu().numpy().view(np.uint32).max()) == 0
+        a, b = stat(ms["knn"]), stat(ms["range"])
+        emit(dict(leg="scan", share=share, eligible=int(allow.sum()), knn_k10=a, range_nothing=b,
+                  ratio=b["median_ms"] / a["median_ms"], margin=a["spread"],
+                  knn_last=[int(v) for v in dev.flat_filtered_last()], range_last=[int(v) for v in dev.flat_range_last()]))
+
+    # ---- stores: scan, gather and sort per radius and cap ---------------------------------------------
+    gt_ids, gt_d, _ = dev.flat_search(queries, GT)
+    legs = [(f"m={m}", np.ascontiguousarray(gt_d[:, m - 1])) for m in (10, 200)] + [("inf", np.full(nq, np.inf, np.float32))]
+    for name, radii in legs:
+        radii_t = torch.from_numpy(radii).cuda()
+        for cap in (1024, 4096):
+            ms = {1: [], 2: [], 3: []}
+            for _ in range(args.rounds):
+                for stages in (1, 2, 3):
+                    env("ALAYA_FLAT_RANGE_STAGES", None if stages == 3 else str(stages))
+                    ms[stages].append(timed(lambda: ranged(radii_t, cap)))
+            env("ALAYA_FLAT_RANGE_STAGES", None)
+            torch.cuda.synchronize()
+            c = counts.cpu().numpy().view(np.uint32)
+            s1, s2, s3 = stat(ms[1]), stat(ms[2]), stat(ms[3])
+            emit(dict(leg="stores", radius=name, max_results=cap, mean_count=float(c.mean()), max_count=int(c.max()),
+                      truncated=int((c > cap).sum()), scan=s1, scan_gather=s2, total=s3,
+                      gather_ms=s2["median_ms"] - s1["median_ms"], sort_ms=s3["median_ms"] - s2["median_ms"],
+                      range_last=[int(v) for v in dev.flat_range_last()]))
+    if args.no_graph:
+        return
+
+    # ---- recall: the graph range searches against the full ground truth --------------------------------
+    dev.build_graph(32, 100, 100, 0, 0, 2)
+    print("index ready", file=sys.stderr, flush=True)
+    cap, front = 4096, args.max_frontier
+    cnt = torch.empty((nq, 4), dtype=torch.int32, device="cuda")
+    more = torch.zeros((nq, 2), dtype=torch.int32, device="cuda")
+    # per query, a radius whose exact count is about --target-rows: doubled from the 200th distance until
+    # the count passes the target, then 24 bisection steps on the exact counts (cap 1: counts are never capped)
+    lo = np.ascontiguousarray(gt_d[:, 199]).astype(np.float64)
+    hi = lo.copy()
+    for _ in range(12):
+        short = exact(hi, 1)[0] < args.target_rows
+        if not short.any():
+            break
+        hi[short] *= 2
+    for _ in range(24):
+        mid = (lo + hi) / 2
+        over = exact(mid, 1)[0] >= args.target_rows
+        hi[over], lo[~over] = mid[over], mid[~over]
+    wide = hi.astype(np.float32)
+    for name, radii in (("m=200", np.ascontiguousarray(gt_d[:, 199])), (f"about {args.target_rows} rows", wide)):
+        t_counts, t_ids, _ = exact(radii, cap)
+        truth = [set(t_ids[i, :min(int(t_counts[i]), cap)].tolist()) for i in range(nq)]
+        emit(dict(leg="truth", radius=name, mean_count=float(t_counts.mean()), min_count=int(t_counts.min()),
+                  max_count=int(t_counts.max()), truncated=int((t_counts > cap).sum()), left_out=0,
+                  radius_min=float(radii.min()), radius_median=float(np.median(radii)), radius_max=float(radii.max())))
+        radii_t = torch.from_numpy(radii).cuda()
+        for ef in (args.small_ef, args.ef):
+            for radius_mode in (False, True):
+                more.zero_()
+                if radius_mode:
+                    dev.range_search_radius_device(qd.data_ptr(), nq, ef, radii_t.data_ptr(), cap, 0, 0, 0, counts.data_ptr(),
+                                                   ids.data_ptr(), d.data_ptr(), cnt.data_ptr(), st.cuda_stream, front,
+                                                   more.data_ptr())
+                else:
+                    dev.range_search_device(qd.data_ptr(), nq, ef, radii_t.data_ptr(), cap, 0, 0, 0, counts.data_ptr(),
+                                            ids.data_ptr(), d.data_ptr(), cnt.data_ptr(), st.cuda_stream)
+                torch.cuda.synchronize()
+                c = counts.cpu().numpy().view(np.uint32)
+                got = ids.cpu().numpy().view(np.uint32)
+                mo = more.cpu().numpy().view(np.uint32)
+                found = sum(len(truth[i] & set(got[i, :min(int(c[i]), cap)].tolist())) for i in range(nq))
+                emit(dict(leg="recall", radius=name, expand="radius" if radius_mode else "fixed", search_ef=ef,
+                          max_results=cap, max_frontier=front if radius_mode else None,
+                          recall=found / float(sum(len(t) for t in truth) or 1), truth_rows=sum(len(t) for t in truth),
+                          mean_count=float(c.mean()), truncated=int((c > cap).sum()),
+                          frontier_cut=int((mo[:, 0] > front).sum()), n_dist=float(cnt.cpu().numpy()[:, 0].mean())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1000000)
@@ -294,7 +464,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", choices=("fixed", "radius", "sq8"), default="fixed")
+    ap.add_argument("--leg", choices=("fixed", "radius", "sq8", "exact"), default="fixed")
+    ap.add_argument("--target-rows", type=int, default=1000, help="exact leg: rows per query of the wide radius")
+    ap.add_argument("--no-graph", action="store_true", help="exact leg: skip the recall part (no graph build)")
     ap.add_argument("--small-ef", type=int, default=64)
     ap.add_argument("--sweep-efs", default="500,700,1000,1400,2000,2800,4000")
     ap.add_argument("--small-sweep-efs", default="64,72,80,96,112,128,160,200,256,320,387")
@@ -304,6 +476,8 @@ def main():
         args.dim, args.ef = args.dim or 768, args.ef or 200
         return sq8_leg(args)
     args.dim, args.ef = args.dim or 960, args.ef or 387
+    if args.leg == "exact":
+        return exact_leg(args)
 
     import torch
     from alayalite_amd import _native
