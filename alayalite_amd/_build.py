@@ -29,7 +29,7 @@ LIB = os.path.join(HERE, "libalaya_hip.so")
 EXT = os.path.join(HERE, "_alayalitepy" + sysconfig.get_config_var("EXT_SUFFIX"))
 
 LIB_SOURCES = ["search_kernels.hip", "build_kernels.hip", "extend_kernels.hip", "flat_kernels.hip", "flat_filtered_kernels.hip", "flat_range_kernels.hip", "capi.cpp", "hnsw_build.cpp", "graph_update.cpp"]
-LIB_HEADERS = ["search_kernels.h", "search_variants.h", "search_device.h", "screen_bound.h", "build_kernels.h", "extend_kernels.h", "flat_kernels.h", "flat_filtered_kernels.h", "flat_range_kernels.h", "flat_bound.h", "hnsw_build.h", "host_distance.h", "graph_update.h"]
+LIB_HEADERS = ["search_kernels.h", "search_variants.h", "search_device.h", "screen_bound.h", "build_kernels.h", "extend_kernels.h", "flat_kernels.h", "flat_filtered_kernels.h", "flat_range_kernels.h", "exact_scan_plan.h", "exact_scan_device.h", "flat_bound.h", "hnsw_build.h", "host_distance.h", "graph_update.h"]
 EXT_SOURCES = ["pybind_module.cpp"]
 
 

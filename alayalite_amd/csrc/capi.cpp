@@ -2944,14 +2944,66 @@ int alaya_index_flat_last_contraction(const alaya_index *ix, int *contraction) {
 }
 
 // ---- exact filtered k-NN: compaction, row-reusing f32 scan, merge (flat_filtered_kernels.hip) ------
-static uint64_t flat_filter_forced_rows() {
-  const char *e = std::getenv("ALAYA_FLAT_FILTER_CHUNK_ROWS");
+static uint64_t env_u64(const char *name) {
+  const char *e = std::getenv(name);
   const long long v = e ? std::atoll(e) : 0;
   return v > 0 ? static_cast<uint64_t>(v) : 0;
 }
+static uint64_t flat_filter_forced_rows() { return env_u64("ALAYA_FLAT_FILTER_CHUNK_ROWS"); }
+
+// ---- what the two exact scans' drivers share (do_flat_filtered, do_flat_range) --------------------------
+// Both run between scratch_acquire and scratch_release: the buffers below are the index's scratch.
+//
+// The queries of each of n_lists id lists as an index list, so outputs land in the caller's order: the queries
+// of list g are order[first[g] .. first[g + 1]), and with more than one list `order` is uploaded to ff_qlist
+// (the host waits for it).  h_groups: the queries' list indices on the host (checked by the caller), or null:
+// with more than one list they are read back from d_groups and checked here.  what: the caller's label.
+static std::vector<uint64_t> flat_group_queries(alaya_index *ix, uint64_t nq, uint32_t n_lists, const uint32_t *h_groups,
+                                                const uint32_t *d_groups, const char *what, hipStream_t stream) {
+  std::vector<uint64_t> first(static_cast<size_t>(n_lists) + 1, 0);
+  if (n_lists <= 1) {
+    first[n_lists] = nq;
+    return first;
+  }
+  std::vector<uint32_t> groups_read;
+  if (!h_groups) {
+    groups_read.resize(nq);
+    hip_check(hipMemcpyAsync(groups_read.data(), d_groups, nq * 4, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), what);
+    check_mask_indices(what, groups_read.data(), nq, n_lists);
+    h_groups = groups_read.data();
+  }
+  for (uint64_t i = 0; i < nq; ++i) ++first[h_groups[i] + 1];
+  for (uint32_t g = 0; g < n_lists; ++g) first[g + 1] += first[g];
+  std::vector<uint32_t> order(nq);
+  std::vector<uint64_t> at(first.begin(), first.end() - 1);
+  for (uint64_t i = 0; i < nq; ++i) order[at[h_groups[i]]++] = static_cast<uint32_t>(i);
+  ix->ff_qlist.reserve(nq * 4);
+  hip_check(hipMemcpyAsync(ix->ff_qlist.ptr, order.data(), nq * 4, hipMemcpyHostToDevice, stream), "upload query lists");
+  hip_check(hipStreamSynchronize(stream), what);  // `order` is pageable host memory
+  return first;
+}
+
+// (words AND valid AND below n) as an ascending id list in ff_ids; returns its length, which the host waits
+// for.  what: the caller's label, "flat filtered compaction" or "flat range compaction".  Called once per
+// mask: the reserves are of the same sizes each time, so only the first of a call can allocate.
+static uint32_t flat_compact_ids(alaya_index *ix, const uint32_t *words, const uint32_t *valid, const char *what,
+                                 hipStream_t stream) {
+  ix->ff_ids.reserve(std::max<uint64_t>(ix->n, 1) * 4);
+  ix->ff_sums.reserve((alaya_amd::flat_filtered_blocks(ix->n) + 1) * 4);
+  ix->ff_count.reserve(4);
+  hip_check(alaya_amd::launch_flat_filtered_compact(words, valid, ix->n, ix->ff_sums.as<uint32_t>(),
+                                                    ix->ff_ids.as<uint32_t>(), ix->ff_count.as<uint32_t>(), stream),
+            what);
+  uint32_t m = 0;
+  hip_check(hipMemcpyAsync(&m, ix->ff_count.ptr, 4, hipMemcpyDeviceToHost, stream), "D2H");
+  hip_check(hipStreamSynchronize(stream), what);
+  if (m > ix->n) throw DeviceError(std::string(what) + ": count past the rows");
+  return m;
+}
 
 // Every pointer but h_groups is a device pointer.  h_groups: the queries' mask indices on the host (checked
-// by the caller), or null: with more than one mask they are read back from d_groups and checked here.
+// by the caller), or null: with more than one mask they are read back from d_groups and checked.
 // Masks are served one after another on `stream`; the host waits for each mask's allowed-row count.
 static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, const uint32_t *d_allow,
                              uint32_t n_masks, const uint32_t *h_groups, const uint32_t *d_groups, uint32_t *d_ids,
@@ -2962,51 +3014,17 @@ static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uin
   if (k == 0 || k > kFilteredMaxK) throw ArgError("flat filtered search: k must be in 1..224");
   if (nq == 0) return;
   if (nq > 0xffffffffull) throw ArgError("flat filtered search: too many queries");
-  std::vector<uint32_t> groups_read;
-  if (n_masks > 1 && !h_groups) {
-    groups_read.resize(nq);
-    hip_check(hipMemcpyAsync(groups_read.data(), d_groups, nq * 4, hipMemcpyDeviceToHost, stream), "D2H");
-    hip_check(hipStreamSynchronize(stream), "flat filtered search");
-    check_mask_indices("flat filtered search", groups_read.data(), nq, n_masks);
-    h_groups = groups_read.data();
-  }
-  // the queries of each mask as an index list, so outputs land in the caller's order
-  std::vector<uint64_t> first(static_cast<size_t>(n_masks) + 1, 0);
-  std::vector<uint32_t> order;
-  if (n_masks > 1) {
-    for (uint64_t i = 0; i < nq; ++i) ++first[h_groups[i] + 1];
-    for (uint32_t g = 0; g < n_masks; ++g) first[g + 1] += first[g];
-    order.resize(nq);
-    std::vector<uint64_t> at(first.begin(), first.end() - 1);
-    for (uint64_t i = 0; i < nq; ++i) order[at[h_groups[i]]++] = static_cast<uint32_t>(i);
-  } else {
-    first[1] = nq;
-  }
   const uint64_t mask_words = (ix->n + 31) / 32;
   const uint64_t forced = flat_filter_forced_rows();
   const uint32_t cus = static_cast<uint32_t>(stream_cus(ix, stream));
   scratch_acquire(ix, stream);
-  ix->ff_ids.reserve(std::max<uint64_t>(ix->n, 1) * 4);
-  ix->ff_sums.reserve((flat_filtered_blocks(ix->n) + 1) * 4);
-  ix->ff_count.reserve(4);
-  if (n_masks > 1) {
-    ix->ff_qlist.reserve(nq * 4);
-    hip_check(hipMemcpyAsync(ix->ff_qlist.ptr, order.data(), nq * 4, hipMemcpyHostToDevice, stream), "upload query lists");
-    hip_check(hipStreamSynchronize(stream), "flat filtered search");  // `order` is pageable host memory
-  }
+  const std::vector<uint64_t> first = flat_group_queries(ix, nq, n_masks, h_groups, d_groups, "flat filtered search", stream);
   uint64_t stats[4] = {0, 0, 0, 0};
   for (uint32_t g = 0; g < n_masks; ++g) {
     const uint64_t nq_g = first[g + 1] - first[g];
     if (nq_g == 0) continue;
-    hip_check(launch_flat_filtered_compact(d_allow + static_cast<uint64_t>(g) * mask_words,
-                                           ix->has_valid ? ix->valid.as<uint32_t>() : nullptr, ix->n,
-                                           ix->ff_sums.as<uint32_t>(), ix->ff_ids.as<uint32_t>(),
-                                           ix->ff_count.as<uint32_t>(), stream),
-              "flat filtered compaction");
-    uint32_t m = 0;
-    hip_check(hipMemcpyAsync(&m, ix->ff_count.ptr, 4, hipMemcpyDeviceToHost, stream), "D2H");
-    hip_check(hipStreamSynchronize(stream), "flat filtered compaction");
-    if (m > ix->n) throw DeviceError("flat filtered compaction: count past the rows");
+    const uint32_t m = flat_compact_ids(ix, d_allow + static_cast<uint64_t>(g) * mask_words,
+                                        ix->has_valid ? ix->valid.as<uint32_t>() : nullptr, "flat filtered compaction", stream);
     const FlatFilteredPlan plan = flat_filtered_plan(m, nq_g, k, ix->stride, cus, forced);
     if (plan.tile == 0) throw ArgError("flat filtered search: k / dim too large for the LDS budget");
     stats[0] += m;
@@ -3108,11 +3126,6 @@ int alaya_flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k, uint32
 }
 
 // ---- exact range search: compaction, row-reusing f32 scan with a threshold, gather, sort (flat_range_kernels.hip) ----
-static uint64_t env_u64(const char *name) {
-  const char *e = std::getenv(name);
-  const long long v = e ? std::atoll(e) : 0;
-  return v > 0 ? static_cast<uint64_t>(v) : 0;
-}
 static uint64_t flat_range_forced_rows() { return env_u64("ALAYA_FLAT_RANGE_CHUNK_ROWS"); }
 static uint64_t flat_range_forced_staging() { return env_u64("ALAYA_FLAT_RANGE_STAGING_BYTES"); }
 
@@ -3130,40 +3143,13 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
   if (nq > 0xffffffffull) throw ArgError("flat range search: too many queries");
   const bool masked = d_allow != nullptr;
   const uint32_t n_lists = masked ? n_masks : 1;  // id lists to scan: one per mask, or the one of no mask
-  std::vector<uint32_t> groups_read;
-  if (n_lists > 1 && !h_groups) {
-    groups_read.resize(nq);
-    hip_check(hipMemcpyAsync(groups_read.data(), d_groups, nq * 4, hipMemcpyDeviceToHost, stream), "D2H");
-    hip_check(hipStreamSynchronize(stream), "flat range search");
-    check_mask_indices("flat range search", groups_read.data(), nq, n_masks);
-    h_groups = groups_read.data();
-  }
-  // the queries of each mask as an index list, so outputs land in the caller's order
-  std::vector<uint64_t> first(static_cast<size_t>(n_lists) + 1, 0);
-  std::vector<uint32_t> order;
-  if (n_lists > 1) {
-    for (uint64_t i = 0; i < nq; ++i) ++first[h_groups[i] + 1];
-    for (uint32_t g = 0; g < n_lists; ++g) first[g + 1] += first[g];
-    order.resize(nq);
-    std::vector<uint64_t> at(first.begin(), first.end() - 1);
-    for (uint64_t i = 0; i < nq; ++i) order[at[h_groups[i]]++] = static_cast<uint32_t>(i);
-  } else {
-    first[1] = nq;
-  }
   const uint64_t mask_words = (ix->n + 31) / 32;
   const uint64_t forced = flat_range_forced_rows(), forced_staging = flat_range_forced_staging();
   const uint32_t cus = static_cast<uint32_t>(stream_cus(ix, stream));
   const char *stages_env = std::getenv("ALAYA_FLAT_RANGE_STAGES");
   const int stages = stages_env ? std::atoi(stages_env) : 3;  // diagnostics: 1 = scans only, 2 = and gathers, else all
   scratch_acquire(ix, stream);
-  ix->ff_ids.reserve(std::max<uint64_t>(ix->n, 1) * 4);
-  ix->ff_sums.reserve((flat_filtered_blocks(ix->n) + 1) * 4);
-  ix->ff_count.reserve(4);
-  if (n_lists > 1) {
-    ix->ff_qlist.reserve(nq * 4);
-    hip_check(hipMemcpyAsync(ix->ff_qlist.ptr, order.data(), nq * 4, hipMemcpyHostToDevice, stream), "upload query lists");
-    hip_check(hipStreamSynchronize(stream), "flat range search");  // `order` is pageable host memory
-  }
+  const std::vector<uint64_t> first = flat_group_queries(ix, nq, n_lists, h_groups, d_groups, "flat range search", stream);
   const uint32_t *d_valid = ix->has_valid ? ix->valid.as<uint32_t>() : nullptr;
   if (!masked && !d_valid) {  // no mask, every row valid: the compaction runs over all-ones words
     ix->fr_ones.reserve(std::max<uint64_t>(mask_words, 1) * 4);
@@ -3176,13 +3162,7 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
     // (mask AND validity AND below n); with no mask the validity bitmap, or the all-ones words, is the mask
     const uint32_t *words = masked ? d_allow + static_cast<uint64_t>(g) * mask_words
                                    : (d_valid ? d_valid : ix->fr_ones.as<uint32_t>());
-    hip_check(launch_flat_filtered_compact(words, masked ? d_valid : nullptr, ix->n, ix->ff_sums.as<uint32_t>(),
-                                           ix->ff_ids.as<uint32_t>(), ix->ff_count.as<uint32_t>(), stream),
-              "flat range compaction");
-    uint32_t m = 0;
-    hip_check(hipMemcpyAsync(&m, ix->ff_count.ptr, 4, hipMemcpyDeviceToHost, stream), "D2H");
-    hip_check(hipStreamSynchronize(stream), "flat range compaction");
-    if (m > ix->n) throw DeviceError("flat range compaction: count past the rows");
+    const uint32_t m = flat_compact_ids(ix, words, masked ? d_valid : nullptr, "flat range compaction", stream);
     const FlatRangePlan plan = flat_range_plan(m, nq_g, max_results, ix->stride, cus, forced, forced_staging);
     if (plan.tile == 0) throw ArgError("flat range search: dim too large for the LDS budget");
     stats[0] = m;

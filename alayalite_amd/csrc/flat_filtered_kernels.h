@@ -7,17 +7,15 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "exact_scan_plan.h"
+
 namespace alaya_amd {
 
-constexpr uint32_t kFilteredPassRows = 32;   // rows one wave takes per pass: 8 lane groups x 4 rows
-constexpr uint32_t kFilteredWaveQueries = 4; // queries of one wave (its register sub-tile)
-constexpr uint32_t kFilteredMaxTile = 16;    // queries per workgroup: 4, 8 or 16 (1, 2 or 4 waves)
 constexpr uint32_t kFilteredMaxK = 224;
 constexpr size_t kFilteredPartialCap = size_t(256) << 20;  // bytes of partial lists per scan launch
-constexpr size_t kFilteredLdsMax = 160 * 1024;
 
 struct FlatFilteredPlan {
-  uint64_t chunk_rows;     // id-list entries per row chunk, a multiple of kFilteredPassRows
+  uint64_t chunk_rows;     // id-list entries per row chunk, a multiple of kScanPassRows
   uint64_t chunks;         // row chunks (0 when nothing is allowed)
   uint64_t tile;           // queries per workgroup (0: the shape does not fit the LDS)
   uint64_t sub_queries;    // queries per scan launch, a multiple of the tile

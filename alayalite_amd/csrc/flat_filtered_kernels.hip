@@ -2,20 +2,15 @@
 //
 // Stands in for the reference's exact search (find_exact_gt, include/utils/evaluate.hpp:29-62) over
 // the subset of rows that are valid and that a mask allows.  Every distance is computed in f32 in
-// the reference's summation order from the start (l2_sqr_avx2 / ip_sqr_avx2, restated below), so
-// there is no approximate contraction, no bound, no flag and no host recompute -- unlike the MFMA
-// flat scan of flat_kernels.hip, whose exact_l2 / exact_ip give the same bits.
+// the reference's summation order from the start (l2_sqr_avx2 / ip_sqr_avx2, restated in
+// exact_scan_device.h), so there is no approximate contraction, no bound, no flag and no host recompute --
+// unlike the MFMA flat scan of flat_kernels.hip, whose exact_l2 / exact_ip give the same bits.
 //
 //   1. compaction  (mask AND validity) -> ascending id list + count: word popcounts, an exclusive scan
 //                  of the per-block sums, a scatter.
-//   2. scan        grid = row chunks (ranges of the id list) x query tiles.  A workgroup holds its tile's
-//                  queries in LDS; wave w owns queries 4w..4w+3 of the tile and streams the chunk's rows
-//                  32 per pass: lane group g (8 lanes) takes rows 4g..4g+3 of the pass, lane m of the
-//                  group the reference's accumulators 4m..4m+3.  A lane's 16-byte slice of each of its 4
-//                  rows meets the 4 queries' slices before it is dropped: 64 accumulators, 4 global and
-//                  4 LDS 16-byte reads per 64 fmaf.  The waves of a workgroup read the same rows at the
-//                  same time, so a row leaves memory once per tile.  Each wave keeps its queries' k best
-//                  by (distance, id) as sorted lists in LDS and writes them out at the end.
+//   2. scan        grid = row chunks (ranges of the id list) x query tiles; the distance pass is
+//                  exact_scan_device.h's, shared with the exact range scan.  Each wave keeps its queries'
+//                  k best by (distance, id) as sorted lists in LDS and writes them out at the end.
 //   3. merge       one wave per query folds the chunk lists into the k outputs, empty slots
 //                  (all-ones id, FLT_MAX).
 //
@@ -27,7 +22,11 @@
 #include <algorithm>
 #include <cfloat>
 
+#include "exact_scan_device.h"
+
 namespace alaya_amd {
+
+using namespace exact_scan;
 
 namespace {
 
@@ -154,54 +153,6 @@ __device__ __forceinline__ void ff_insert(float *Ld, uint32_t *Li, uint32_t k, f
   ff_wave_fence();
 }
 
-// ---- the reference order, restated ---------------------------------------------------------------
-// l2_sqr_avx2 / ip_sqr_avx2: four 8-wide accumulators over 32-element blocks (lane m of 8 owns elements
-// 4m..4m+3 of each block, one fmaf per element), then the whole 8-element blocks into the first
-// accumulator (lanes 0-1), the horizontal sum (xor 2, xor 4, xor 1, then (s0 + s1) + (s2 + s3)), the
-// scalar tail through fmaf, and for inner products the negation last.
-// Lane xor inside a group of 8 by DPP: xor 1 / 2 quad_perm, xor 4 row_ror:12 / row_ror:4 by lane bit 2.
-template <int kXor>
-__device__ __forceinline__ float ff_xor(float v) {
-  const int x = __float_as_int(v);
-  if constexpr (kXor == 1) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false));
-  } else if constexpr (kXor == 2) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false));
-  } else {
-    const int up = __builtin_amdgcn_update_dpp(0, x, 0x12C, 0xF, 0xF, false);
-    const int down = __builtin_amdgcn_update_dpp(0, x, 0x124, 0xF, 0xF, false);
-    return __int_as_float((__lane_id() & 4) ? down : up);
-  }
-}
-
-constexpr int kRows = 4;     // rows of a lane group per pass
-constexpr int kQueries = 4;  // queries of a wave
-
-// one 16-byte slice of each of the lane's rows against the same slice of each of the wave's queries
-template <bool kIp>
-__device__ __forceinline__ void ff_block(float (&acc)[kRows][kQueries][4], const float4 (&y)[kRows], const float *q,
-                                         uint32_t stride, uint32_t off) {
-#pragma unroll
-  for (int c = 0; c < kQueries; ++c) {
-    const float4 x = *reinterpret_cast<const float4 *>(q + c * stride + off);
-#pragma unroll
-    for (int j = 0; j < kRows; ++j) {
-      if constexpr (kIp) {
-        acc[j][c][0] = fmaf(x.x, y[j].x, acc[j][c][0]);
-        acc[j][c][1] = fmaf(x.y, y[j].y, acc[j][c][1]);
-        acc[j][c][2] = fmaf(x.z, y[j].z, acc[j][c][2]);
-        acc[j][c][3] = fmaf(x.w, y[j].w, acc[j][c][3]);
-      } else {
-        const float d0 = x.x - y[j].x, d1 = x.y - y[j].y, d2 = x.z - y[j].z, d3 = x.w - y[j].w;
-        acc[j][c][0] = fmaf(d0, d0, acc[j][c][0]);
-        acc[j][c][1] = fmaf(d1, d1, acc[j][c][1]);
-        acc[j][c][2] = fmaf(d2, d2, acc[j][c][2]);
-        acc[j][c][3] = fmaf(d3, d3, acc[j][c][3]);
-      }
-    }
-  }
-}
-
 }  // namespace
 
 template <bool kIp>
@@ -214,15 +165,7 @@ __global__ void __launch_bounds__(256) flat_filtered_scan_kernel(FlatFilteredPar
   const uint64_t q_tiles = (p.nq + tile - 1) / tile;
   const uint64_t chunk = blockIdx.x / q_tiles;
   const uint64_t q0 = (blockIdx.x % q_tiles) * tile;  // first query (of the launch) of this tile
-  for (uint32_t i = threadIdx.x; i < tile * stride; i += blockDim.x) {
-    const uint32_t ql = i / stride, e = i - ql * stride;
-    float v = 0.f;
-    if (q0 + ql < p.nq && e < p.dim) {
-      const uint64_t src = p.q_list ? p.q_list[p.q_first + q0 + ql] : p.q_first + q0 + ql;
-      v = p.queries[src * p.q_stride + e];
-    }
-    qs[i] = v;
-  }
+  load_query_tile(qs, tile, stride, p.dim, p.queries, p.q_stride, p.q_list, p.q_first, q0, p.nq);
   for (uint32_t i = threadIdx.x; i < tile * k; i += blockDim.x) {
     ld[i] = FLT_MAX;
     li[i] = kEmptyId;
@@ -240,71 +183,11 @@ __global__ void __launch_bounds__(256) flat_filtered_scan_kernel(FlatFilteredPar
   const uint32_t T = p.dim >> 5;
   const uint32_t nb8 = (p.dim - 32 * T) >> 3;
   const uint32_t tail0 = 32 * T + 8 * nb8;
-  for (uint64_t pb = r0; pb < r1; pb += kFilteredPassRows) {
-    // the lane group's rows, in ascending id order; a slot past the chunk recomputes the chunk's first row
+  for (uint64_t pb = r0; pb < r1; pb += kScanPassRows) {
     uint32_t rid[kRows];
     bool ok[kRows];
-    const float *row[kRows];
-#pragma unroll
-    for (int j = 0; j < kRows; ++j) {
-      const uint64_t at = pb + g * kRows + j;
-      ok[j] = at < r1;
-      rid[j] = p.ids[ok[j] ? at : r0];
-      row[j] = p.base + static_cast<uint64_t>(rid[j]) * stride;
-    }
-    float acc[kRows][kQueries][4];
-#pragma unroll
-    for (int j = 0; j < kRows; ++j)
-#pragma unroll
-      for (int c = 0; c < kQueries; ++c)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) acc[j][c][a] = 0.f;
-    if (T > 0) {
-      float4 y[kRows];
-#pragma unroll
-      for (int j = 0; j < kRows; ++j) y[j] = *reinterpret_cast<const float4 *>(row[j] + 4 * m);
-      for (uint32_t t = 0; t < T; ++t) {
-        // the next block's slices are requested before this block's arithmetic
-        float4 yn[kRows];
-        const uint32_t tn = t + 1 < T ? t + 1 : t;
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) yn[j] = *reinterpret_cast<const float4 *>(row[j] + 32 * tn + 4 * m);
-        ff_block<kIp>(acc, y, q, stride, 32 * t + 4 * m);
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) y[j] = yn[j];
-      }
-    }
-    if (m < 2) {
-      for (uint32_t bb = 0; bb < nb8; ++bb) {
-        const uint32_t off = 32 * T + 8 * bb + 4 * m;
-        float4 y[kRows];
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) y[j] = *reinterpret_cast<const float4 *>(row[j] + off);
-        ff_block<kIp>(acc, y, q, stride, off);
-      }
-    }
     float dist[kRows][kQueries];
-#pragma unroll
-    for (int j = 0; j < kRows; ++j) {
-#pragma unroll
-      for (int c = 0; c < kQueries; ++c) {
-        float a0 = acc[j][c][0], a1 = acc[j][c][1], a2 = acc[j][c][2], a3 = acc[j][c][3];
-        a0 += ff_xor<2>(a0); a1 += ff_xor<2>(a1); a2 += ff_xor<2>(a2); a3 += ff_xor<2>(a3);
-        a0 += ff_xor<4>(a0); a1 += ff_xor<4>(a1); a2 += ff_xor<4>(a2); a3 += ff_xor<4>(a3);
-        const float s0 = a0 + ff_xor<1>(a0), s1 = a1 + ff_xor<1>(a1);
-        const float s2 = a2 + ff_xor<1>(a2), s3 = a3 + ff_xor<1>(a3);
-        float res = (s0 + s1) + (s2 + s3);
-        for (uint32_t e = tail0; e < p.dim; ++e) {
-          if constexpr (kIp) {
-            res = fmaf(q[c * stride + e], row[j][e], res);
-          } else {
-            const float d = q[c * stride + e] - row[j][e];
-            res = fmaf(d, d, res);
-          }
-        }
-        dist[j][c] = kIp ? -res : res;
-      }
-    }
+    pass<kIp>(p.ids, p.base, pb, r0, r1, q, p.dim, stride, T, nb8, tail0, g, m, dist, rid, ok);
     // every lane of a group holds its rows' 16 distances; lane 0 of the group offers them
 #pragma unroll
     for (int c = 0; c < kQueries; ++c) {
@@ -374,6 +257,7 @@ __global__ void __launch_bounds__(64) flat_filtered_merge_kernel(FlatFilteredPar
         }
       }
     }
+    // query_row(), spelled out: behind a call the compiler lays this kernel's blocks out in another order
     const uint64_t dst = (p.q_list ? p.q_list[p.q_first + qi] : p.q_first + qi) * k;
     for (uint32_t e = lane; e < k; e += 64) {
       p.out_ids[dst + e] = Li[e];
@@ -393,31 +277,17 @@ FlatFilteredPlan flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k,
   FlatFilteredPlan r{};
   k = std::max<uint32_t>(k, 1);
   cus = std::max<uint32_t>(cus, 1);
-  // Query tile: 16 (four waves share each row read), smaller for a handful of queries, and smaller
-  // where two workgroups would no longer fit a CU's LDS -- the second one hides the row loads' latency.
-  uint32_t tile = nq <= 4 ? 4 : (nq <= 8 ? 8 : kFilteredMaxTile);
-  while (tile > kFilteredWaveQueries && flat_filtered_lds(tile, stride, k) > kFilteredLdsMax / 2) tile /= 2;
-  if (flat_filtered_lds(tile, stride, k) > kFilteredLdsMax) return r;  // tile = 0: does not fit
+  const uint32_t tile = scan_tile(nq, [&](uint32_t t) { return flat_filtered_lds(t, stride, k); });
+  if (tile == 0) return r;  // does not fit
   r.tile = tile;
-  const uint64_t q_tiles = std::max<uint64_t>(1, (nq + tile - 1) / tile);
-  // no more chunks than fill the CUs twice over at this tile -- rounded down: two workgroups are resident
-  // per CU, and a grid a little past 2 x cus would run a second, nearly empty round
-  const uint64_t max_chunks = std::max<uint64_t>(1, 2ull * cus / q_tiles);
-  const uint64_t passes = (n_allowed + kFilteredPassRows - 1) / kFilteredPassRows;
-  uint64_t chunk_rows = kFilteredPassRows * std::max<uint64_t>(1, (passes + max_chunks - 1) / max_chunks);
-  if (forced_rows) chunk_rows = (forced_rows + kFilteredPassRows - 1) / kFilteredPassRows * kFilteredPassRows;
+  uint64_t chunk_rows = scan_chunk_rows(n_allowed, nq, tile, cus, forced_rows);
   // one query tile's lists stay under the cap (only a forced chunk size can ask for more)
   const uint64_t cap_chunks = kFilteredPartialCap / (static_cast<uint64_t>(tile) * k * 8);
   if ((n_allowed + chunk_rows - 1) / chunk_rows > cap_chunks)
-    chunk_rows = kFilteredPassRows * ((passes + cap_chunks - 1) / cap_chunks);
+    chunk_rows = kScanPassRows * ((scan_passes(n_allowed) + cap_chunks - 1) / cap_chunks);
   r.chunk_rows = chunk_rows;
   r.chunks = (n_allowed + chunk_rows - 1) / chunk_rows;
-  const uint64_t all = (std::max<uint64_t>(nq, 1) + tile - 1) / tile * tile;
-  r.sub_queries = all;
-  if (r.chunks) {
-    const uint64_t fit = kFilteredPartialCap / (r.chunks * k * 8) / tile * tile;  // >= tile by cap_chunks
-    r.sub_queries = std::min(all, fit);
-  }
+  r.sub_queries = scan_sub_queries(nq, tile, r.chunks, kFilteredPartialCap, k * 8ull);  // >= tile by cap_chunks
   r.partial_bytes = r.chunks * std::min<uint64_t>(nq, r.sub_queries) * k * 8;
   return r;
 }
@@ -444,21 +314,17 @@ hipError_t launch_flat_filtered_compact(const uint32_t *words, const uint32_t *v
 namespace {
 template <bool kIp>
 hipError_t scan_launch(const FlatFilteredParams &p, uint32_t grid, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL(flat_filtered_scan_kernel<kIp>, dim3(grid), dim3(p.tile / kFilteredWaveQueries * 64), lds, s, p);
+  hipLaunchKernelGGL(flat_filtered_scan_kernel<kIp>, dim3(grid), dim3(p.tile / kScanWaveQueries * 64), lds, s, p);
   return hipGetLastError();
 }
 }  // namespace
 
 hipError_t launch_flat_filtered_scan(const FlatFilteredParams &p, hipStream_t s) {
-  if (p.tile != 4 && p.tile != 8 && p.tile != 16) return hipErrorInvalidValue;
-  if (p.k == 0 || p.k > kFilteredMaxK || p.nq == 0 || p.chunks == 0 || p.chunk_rows == 0) return hipErrorInvalidValue;
-  if (p.chunks * p.chunk_rows < p.n_ids || (p.chunks - 1) * p.chunk_rows >= p.n_ids) return hipErrorInvalidValue;
+  const uint32_t grid = scan_grid(p.tile, p.nq, p.n_ids, p.chunk_rows, p.chunks);
+  if (grid == 0 || p.k == 0 || p.k > kFilteredMaxK) return hipErrorInvalidValue;
   const size_t lds = flat_filtered_lds(p.tile, p.stride, p.k);
-  if (lds > kFilteredLdsMax) return hipErrorInvalidValue;
-  const uint64_t grid = (p.nq + p.tile - 1) / p.tile * p.chunks;
-  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-  return p.ip ? scan_launch<true>(p, static_cast<uint32_t>(grid), lds, s)
-              : scan_launch<false>(p, static_cast<uint32_t>(grid), lds, s);
+  if (lds > kScanLdsMax) return hipErrorInvalidValue;
+  return p.ip ? scan_launch<true>(p, grid, lds, s) : scan_launch<false>(p, grid, lds, s);
 }
 
 hipError_t launch_flat_filtered_merge(const FlatFilteredParams &p, hipStream_t s) {

@@ -8,17 +8,15 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "exact_scan_plan.h"
+
 namespace alaya_amd {
 
-constexpr uint32_t kFlatRangePassRows = 32;    // rows one wave takes per pass: 8 lane groups x 4 rows
-constexpr uint32_t kFlatRangeWaveQueries = 4;  // queries of one wave (its register sub-tile)
-constexpr uint32_t kFlatRangeMaxTile = 16;     // queries per workgroup: 4, 8 or 16 (1, 2 or 4 waves)
 constexpr uint32_t kFlatRangeMaxCap = 4096;    // stored hits per query
 constexpr size_t kFlatRangeStagingCap = size_t(256) << 20;  // bytes of partial lists and counts per scan launch
-constexpr size_t kFlatRangeLdsMax = 160 * 1024;
 
 struct FlatRangePlan {
-  uint64_t chunk_rows;     // id-list entries per row chunk, a multiple of kFlatRangePassRows
+  uint64_t chunk_rows;     // id-list entries per row chunk, a multiple of kScanPassRows
   uint64_t chunks;         // row chunks (0 when no row is eligible)
   uint64_t tile;           // queries per workgroup (0: the queries do not fit the LDS)
   uint64_t sub_queries;    // queries per scan launch, a multiple of the tile
