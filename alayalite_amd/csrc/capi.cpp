@@ -152,6 +152,11 @@ struct alaya_index {
   uint64_t fr_last[6] = {0, 0, 0, 0, 0, 0};  // alaya_index_flat_range_last
   size_t overflow_clean = 0;  // leading bytes of `overflow` known to be zero (kernels leave it clean)
   size_t stab_clean = 0;      // the same for the spill tables
+  // leading bytes of the two areas zeroed at least once since their buffer was allocated: equal to the
+  // clean prefixes until scratch_suspect clears those; what alaya_index_spill_residue may read.  Reset where
+  // a buffer is replaced: `overflow` in set_base and prepare_spill, `stab` in prepare_spill alone (nothing
+  // else releases or reallocates it)
+  size_t overflow_zeroed = 0, stab_zeroed = 0;
   uint32_t hash_log2_override = 0;
   int helpers_mode = -1;          // distance helpers: -1 automatic, 0 off, 1 on (alaya_index_set_helpers)
   DevBuf help_stats;              // per searcher of the last helper launch: (memo distances, memo expansions)
@@ -296,10 +301,12 @@ void prepare_spill(alaya_index *ix, SearchParams &p, uint64_t slots, hipStream_t
   if (bytes > ix->overflow.bytes) {
     ix->overflow.reserve(bytes);
     ix->overflow_clean = 0;
+    ix->overflow_zeroed = 0;
   }
   if (ix->overflow_clean < ix->overflow.bytes) {
     hip_check(hipMemsetAsync(ix->overflow.ptr, 0, ix->overflow.bytes, stream), "hipMemsetAsync");
     ix->overflow_clean = ix->overflow.bytes;
+    ix->overflow_zeroed = ix->overflow.bytes;
   }
   uint32_t cap = kDirtyCap;
   if (const char *e = std::getenv("ALAYA_DIRTY_CAP")) cap = static_cast<uint32_t>(std::strtoul(e, nullptr, 10));  // tests
@@ -316,10 +323,12 @@ void prepare_spill(alaya_index *ix, SearchParams &p, uint64_t slots, hipStream_t
     if (tbytes > ix->stab.bytes) {
       ix->stab.reserve(tbytes);
       ix->stab_clean = 0;
+      ix->stab_zeroed = 0;
     }
     if (ix->stab_clean < ix->stab.bytes) {
       hip_check(hipMemsetAsync(ix->stab.ptr, 0, ix->stab.bytes, stream), "hipMemsetAsync");
       ix->stab_clean = ix->stab.bytes;
+      ix->stab_zeroed = ix->stab.bytes;
     }
     const uint32_t rbits = p.vis_lbits - (st - 3);
     p.spill_table = ix->stab.as<uint16_t>();
@@ -1476,6 +1485,7 @@ int alaya_index_set_base(alaya_index *ix, const float *rows, uint64_t n, uint32_
     ix->generic = generic;
     ix->overflow.release();
     ix->overflow_clean = 0;
+    ix->overflow_zeroed = 0;
     ix->norms_ready = false;
     ix->tiles_ready = false;
     ix->capacity = n;
@@ -3405,6 +3415,51 @@ int alaya_index_scout_policy_stats(alaya_index *ix, uint32_t *policy, uint64_t *
     if (early_posts) *early_posts = t[0];
     if (confirmed) *confirmed = t[1];
     if (abandoned) *abandoned = t[2];
+  });
+}
+
+int alaya_index_spill_residue(alaya_index *ix, uint64_t *overflow_words, uint64_t *stab_entries,
+                              uint64_t *overflow_bytes, uint64_t *stab_bytes) {
+  return guarded_scratch(ix, [&] {
+    if (!ix) throw ArgError("null index");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    scratch_drain(ix);
+    // the areas as far as a launch has zeroed them: the clean prefixes, and after scratch_suspect what they were
+    const size_t ob = std::min(ix->overflow_zeroed, ix->overflow.bytes) / 4 * 4;
+    const size_t sb = std::min(ix->stab_zeroed, ix->stab.bytes) / 2 * 2;
+    uint64_t words = 0, entries = 0;
+    if (ob) {
+      std::vector<uint32_t> h(ob / 4);
+      hip_check(hipMemcpy(h.data(), ix->overflow.ptr, ob, hipMemcpyDeviceToHost), "D2H");
+      for (const uint32_t w : h) words += w != 0;
+    }
+    if (sb) {
+      std::vector<uint16_t> h(sb / 2);
+      hip_check(hipMemcpy(h.data(), ix->stab.ptr, sb, hipMemcpyDeviceToHost), "D2H");
+      for (const uint16_t e : h) entries += e != 0;
+    }
+    if (overflow_words) *overflow_words = words;
+    if (stab_entries) *stab_entries = entries;
+    if (overflow_bytes) *overflow_bytes = ob;
+    if (stab_bytes) *stab_bytes = sb;
+  });
+}
+
+int alaya_index_spill_mark(alaya_index *ix, uint64_t word_index) {
+  return guarded_scratch(ix, [&] {
+    if (!ix) throw ArgError("null index");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (word_index >= std::min(ix->overflow_zeroed, ix->overflow.bytes) / 4)
+      throw ArgError("spill_mark: word_index is past the bitset area a launch has prepared");
+    set_device(ix);
+    scratch_drain(ix);
+    uint32_t w = 0;
+    uint32_t *at = ix->overflow.as<uint32_t>() + word_index;
+    hip_check(hipMemcpy(&w, at, 4, hipMemcpyDeviceToHost), "D2H");
+    w |= 1u;
+    hip_check(hipMemcpy(at, &w, 4, hipMemcpyHostToDevice), "H2D");
+    scratch_suspect(ix);  // the next launch zeroes both areas again
   });
 }
 

@@ -222,6 +222,13 @@ class LaunchControls {
     d["scout_policy"] = scout_policy();
     return d;
   }
+  // (nonzero bitset words, nonzero spill-table entries, bitset bytes read, table bytes read)
+  py::tuple spill_residue() {
+    uint64_t w = 0, e = 0, wb = 0, eb = 0;
+    check(alaya_index_spill_residue(ix_, &w, &e, &wb, &eb));
+    return py::make_tuple(w, e, wb, eb);
+  }
+  void spill_mark(uint64_t word_index) { check(alaya_index_spill_mark(ix_, word_index)); }
 
  protected:
   alaya_index *ix_ = nullptr;
@@ -1594,6 +1601,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("scout_stats", &PyIndexInterface::scout_stats)
       .def("scout_policy_stats", &PyIndexInterface::scout_policy_stats)
       .def("last_plan", &PyIndexInterface::last_plan)
+      .def("spill_residue", &PyIndexInterface::spill_residue)
+      .def("spill_mark", &PyIndexInterface::spill_mark)
       .def("set_rerank_mode", &PyIndexInterface::set_rerank_mode)
       .def("rerank_mode", &PyIndexInterface::rerank_mode)
       .def("device_distances", &PyIndexInterface::device_distances)
@@ -1651,6 +1660,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("scout_stats", &DeviceIndex::scout_stats)
       .def("scout_policy_stats", &DeviceIndex::scout_policy_stats)
       .def("last_plan", &DeviceIndex::last_plan)
+      .def("spill_residue", &DeviceIndex::spill_residue)
+      .def("spill_mark", &DeviceIndex::spill_mark)
       .def("flat_search", &DeviceIndex::flat_search, py::arg("queries"), py::arg("k"))
       .def("flat_search_device", &DeviceIndex::flat_search_device)
       .def("flat_search_filtered", &DeviceIndex::flat_search_filtered, py::arg("queries"), py::arg("k"),

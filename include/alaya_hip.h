@@ -659,6 +659,21 @@ int alaya_index_last_launch(const alaya_index *ix, uint32_t *workgroups, uint32_
  * compact: 1 = 16-bit slots), resident workgroups per CU, and the scout flags (below; 0 = no scouts). */
 int alaya_index_last_plan(const alaya_index *ix, uint32_t *lds_bytes, uint32_t *hash_log2, uint32_t *compact,
                           uint32_t *groups_per_cu, uint32_t *scout);
+/* Diagnostics of the visited set's second level.  Every graph search -- and the batched build's -- shares one
+ * per-index scratch: an n-bit bitset and a dirty-word list per persistent searcher, and for AVX-512-order SQ8
+ * searches a spill table per searcher.  A launch zeroes the bitsets and tables once; after that every query
+ * that spilled puts back what it set before its searcher takes the next query, and a call that saw a device
+ * error has the next launch zero them again.
+ * alaya_index_spill_residue waits for the index's last launch and reads both areas back, as far as a launch
+ * has zeroed them: the nonzero 32-bit words of the bitsets, the nonzero 16-bit entries of the tables, and the
+ * bytes of each it looked at (0 before the first search, or for an area no search has used).  Between
+ * launches both counts are 0.
+ * alaya_index_spill_mark sets bit 0 of one word of the bitset area (ALAYA_ERR_ARG past the bytes above) and
+ * marks both areas as after a device error, so the residue then reports that word and the next launch zeroes
+ * the areas before it runs: the one way to see either without a device error.  The tables are not touched. */
+int alaya_index_spill_residue(alaya_index *ix, uint64_t *overflow_words, uint64_t *stab_entries,
+                              uint64_t *overflow_bytes, uint64_t *stab_bytes);
+int alaya_index_spill_mark(alaya_index *ix, uint64_t word_index);
 /* Scout of the screened graph search at d = 768 / 960 (L2, integer screen): in a batch that leaves the
  * second wave per SIMD idle, every searcher wave gets a scout wave in its workgroup, which computes the
  * screen's bounds for the neighbours of the nodes the searcher will probably pop next; the searcher
