@@ -22,6 +22,8 @@
 #include "flat_bound.h"
 #include "flat_filtered_kernels.h"
 #include "flat_range_kernels.h"
+#include "flat_range_mfma_kernels.h"
+#include "flat_range_bound.h"
 #include "flat_kernels.h"
 #include <cstdlib>
 #include "screen_bound.h"
@@ -150,6 +152,11 @@ struct alaya_index {
   // all-ones words that stand for "no mask" on an index without a validity bitmap
   DevBuf fr_part_n, fr_ones;
   uint64_t fr_last[6] = {0, 0, 0, 0, 0, 0};  // alaya_index_flat_range_last
+  // its MFMA scan (flat_range_mfma_kernels.hip): the launch's padded queries, their norms and thresholds, the
+  // per-wave counters of one scan launch and the call's three sums (alaya_index_flat_range_path)
+  DevBuf fr_qpad, fr_qmeta, fr_wave_stats, fr_stats;
+  int fr_path = 0;  // the last call's path: 0 the f32 scan, 1 the MFMA scan (for any of its masks)
+  hipEvent_t fr_done = nullptr;  // recorded after the last MFMA call's launches: what alaya_index_flat_range_path waits for
   size_t overflow_clean = 0;  // leading bytes of `overflow` known to be zero (kernels leave it clean)
   size_t stab_clean = 0;      // the same for the spill tables
   // leading bytes of the two areas zeroed at least once since their buffer was allocated: equal to the
@@ -1435,6 +1442,7 @@ void alaya_index_destroy(alaya_index *ix) {
   (void)hipSetDevice(ix->device);
   if (ix->scratch_used) (void)hipEventSynchronize(ix->scratch_ev);
   if (ix->scratch_ev) (void)hipEventDestroy(ix->scratch_ev);
+  if (ix->fr_done) (void)hipEventDestroy(ix->fr_done);
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
   delete ix;
 }
@@ -3138,6 +3146,10 @@ int alaya_flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k, uint32
 // ---- exact range search: compaction, row-reusing f32 scan with a threshold, gather, sort (flat_range_kernels.hip) ----
 static uint64_t flat_range_forced_rows() { return env_u64("ALAYA_FLAT_RANGE_CHUNK_ROWS"); }
 static uint64_t flat_range_forced_staging() { return env_u64("ALAYA_FLAT_RANGE_STAGING_BYTES"); }
+// The MFMA scan runs from this eligible share m / n of a mask upwards.  Measured ("Round 24"): faster
+// from 0.2 at 128 and 960 columns with a tight radius, but up to 3.1x slower at radius +inf, which the rule cannot
+// see -- so above 1: never by itself, only with ALAYA_FLAT_RANGE_MFMA=1.
+constexpr double kFlatRangeMfmaShare = 2.0;
 
 // Every pointer but h_groups is a device pointer.  d_allow null (n_masks 0): no mask.  h_groups / d_groups as
 // do_flat_filtered's.  Masks are served one after another on `stream`; the host waits for each mask's
@@ -3158,7 +3170,14 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
   const uint32_t cus = static_cast<uint32_t>(stream_cus(ix, stream));
   const char *stages_env = std::getenv("ALAYA_FLAT_RANGE_STAGES");
   const int stages = stages_env ? std::atoi(stages_env) : 3;  // diagnostics: 1 = scans only, 2 = and gathers, else all
+  // the path: ALAYA_FLAT_RANGE_MFMA = 0 / 1 forces the f32 / the MFMA scan; unset, the f32 scan's diagnostics
+  // select the f32 scan, else the mask's eligible share decides (kFlatRangeMfmaShare)
+  const char *mfma_env = std::getenv("ALAYA_FLAT_RANGE_MFMA");
+  const int mfma_mode = (mfma_env && *mfma_env) ? (std::atoi(mfma_env) != 0 ? 1 : 0) : ((forced || forced_staging) ? 0 : -1);
+  const bool mfma_possible = mfma_mode == 1 || (mfma_mode < 0 && kFlatRangeMfmaShare <= 1.0);
+  if (mfma_possible) ensure_norms(ix, stream);  // ahead of the scratch: it waits for the norms once
   scratch_acquire(ix, stream);
+  bool mfma_used = false;
   const std::vector<uint64_t> first = flat_group_queries(ix, nq, n_lists, h_groups, d_groups, "flat range search", stream);
   const uint32_t *d_valid = ix->has_valid ? ix->valid.as<uint32_t>() : nullptr;
   if (!masked && !d_valid) {  // no mask, every row valid: the compaction runs over all-ones words
@@ -3173,13 +3192,57 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
     const uint32_t *words = masked ? d_allow + static_cast<uint64_t>(g) * mask_words
                                    : (d_valid ? d_valid : ix->fr_ones.as<uint32_t>());
     const uint32_t m = flat_compact_ids(ix, words, masked ? d_valid : nullptr, "flat range compaction", stream);
-    const FlatRangePlan plan = flat_range_plan(m, nq_g, max_results, ix->stride, cus, forced, forced_staging);
+    const bool mfma = m != 0 && (mfma_mode == 1 || (mfma_mode < 0 && static_cast<double>(m) >= kFlatRangeMfmaShare * static_cast<double>(ix->n)));
+    FlatRangePlan plan{};
+    if (mfma) {
+      const FlatRangeMfmaPlan mp = flat_range_mfma_plan(ix->n, nq_g, max_results, cus);
+      plan.chunk_rows = mp.chunk_rows;
+      plan.chunks = mp.chunks;
+      plan.tile = kRangeMfmaQueries;
+      plan.sub_queries = mp.sub_queries;
+      plan.slots = mp.slots;
+      plan.staging_bytes = mp.staging_bytes;
+    } else {
+      plan = flat_range_plan(m, nq_g, max_results, ix->stride, cus, forced, forced_staging);
+    }
     if (plan.tile == 0) throw ArgError("flat range search: dim too large for the LDS budget");
     stats[0] = m;
     stats[1] = plan.chunks;
     stats[2] = plan.tile;
     stats[3] = 0;
     stats[4] += m;
+    FlatRangeMfmaParams mq{};
+    if (mfma) {
+      const uint64_t nq_up = std::min<uint64_t>(plan.sub_queries, (nq_g + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries);
+      mq.qwidth = flat_range_mfma_width(ix->stride);
+      ix->fr_qpad.reserve(nq_up * mq.qwidth * 4);
+      ix->fr_qmeta.reserve(nq_up * 16);
+      ix->fr_wave_stats.reserve(plan.chunks * (nq_up / 32) * 12);
+      ix->fr_stats.reserve(32);
+      if (!mfma_used) hip_check(launch_flat_range_mfma_clear(ix->fr_stats.as<unsigned long long>(), stream), "flat range search");
+      mfma_used = true;
+      mq.base = ix->base.as<float>();
+      mq.norms = ix->norms.as<float>();
+      mq.n = ix->n;
+      mq.dim = ix->dim;
+      mq.stride = ix->stride;
+      mq.ip = ix->metric == ALAYA_METRIC_L2 ? 0 : 1;
+      mq.max_norm = ix->max_norm;
+      mq.queries = d_q;
+      mq.q_stride = ix->dim;
+      mq.radii = d_radii;
+      mq.q_list = n_lists > 1 ? ix->ff_qlist.as<uint32_t>() : nullptr;
+      mq.words = words;
+      mq.valid = masked ? d_valid : nullptr;
+      mq.chunk_rows = plan.chunk_rows;
+      mq.chunks = plan.chunks;
+      mq.cap = max_results;
+      mq.slots = static_cast<uint32_t>(plan.slots);
+      mq.qpad = ix->fr_qpad.as<float>();
+      mq.qmeta = ix->fr_qmeta.as<float>();
+      mq.wave_stats = ix->fr_wave_stats.as<uint32_t>();
+      mq.stats = ix->fr_stats.as<unsigned long long>();
+    }
     FlatRangeParams p{};
     p.base = ix->base.as<float>();
     p.dim = ix->dim;
@@ -3212,7 +3275,17 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
     for (uint64_t sb = 0; sb < nq_g; sb += plan.sub_queries) {
       p.q_first = first[g] + sb;
       p.nq = std::min<uint64_t>(plan.sub_queries, nq_g - sb);
-      if (m) {
+      if (mfma) {
+        mq.q_first = p.q_first;
+        mq.nq = p.nq;
+        mq.part_n = p.part_n;
+        mq.part_i = p.part_i;
+        mq.part_d = p.part_d;
+        hip_check(launch_flat_range_mfma_prepare(mq, stream), "flat range prepare");
+        hip_check(launch_flat_range_mfma_scan(mq, stream), "flat range MFMA scan");
+        ++stats[3];
+        ++stats[5];
+      } else if (m) {
         hip_check(launch_flat_range_scan(p, stream), "flat range scan");
         ++stats[3];
         ++stats[5];
@@ -3235,6 +3308,11 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
   }
   scratch_release(ix, stream);
   std::memcpy(ix->fr_last, stats, sizeof(stats));
+  ix->fr_path = mfma_used ? 1 : 0;
+  if (mfma_used) {
+    if (!ix->fr_done) hip_check(hipEventCreateWithFlags(&ix->fr_done, hipEventDisableTiming), "flat range search");
+    hip_check(hipEventRecord(ix->fr_done, stream), "flat range search");
+  }
 }
 
 int alaya_index_flat_range_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, const float *d_radii,
@@ -3288,6 +3366,48 @@ int alaya_index_flat_range_last(const alaya_index *ix, uint64_t *out) {
   return guarded([&] {
     if (!ix || !out) throw ArgError("invalid arguments");
     std::memcpy(out, ix->fr_last, sizeof(ix->fr_last));
+  });
+}
+
+int alaya_index_flat_range_path(alaya_index *ix, uint64_t *out) {
+  return guarded([&] {
+    if (!ix || !out) throw ArgError("invalid arguments");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    out[0] = static_cast<uint64_t>(ix->fr_path);
+    out[1] = out[2] = out[3] = 0;
+    if (!ix->fr_path) return;
+    set_device(ix);
+    unsigned long long sums[3] = {0, 0, 0};
+    hip_check(hipEventSynchronize(ix->fr_done), "flat range path");  // the call's own launches, no other stream
+    hip_check(hipMemcpy(sums, ix->fr_stats.ptr, sizeof(sums), hipMemcpyDeviceToHost), "D2H");
+    for (int j = 0; j < 3; ++j) out[1 + j] = sums[j];
+  });
+}
+
+int alaya_flat_range_mfma_plan(uint64_t n, uint64_t nq, uint32_t max_results, uint32_t cus, uint64_t *out) {
+  return guarded([&] {
+    if (!out) throw ArgError("invalid arguments");
+    if (max_results == 0 || max_results > alaya_amd::kFlatRangeMaxCap)
+      throw ArgError("flat range plan: max_results must be in 1..4096");
+    const alaya_amd::FlatRangeMfmaPlan r = alaya_amd::flat_range_mfma_plan(n, nq, max_results, cus);
+    out[0] = r.chunk_rows;
+    out[1] = r.chunks;
+    out[2] = alaya_amd::kRangeMfmaQueries;
+    out[3] = r.sub_queries;
+    out[4] = r.slots;
+    out[5] = r.staging_bytes;
+  });
+}
+
+int alaya_flat_range_bound(int ip, int contraction, uint32_t k_acc, float b_max, const float *radii, const float *q_norm2,
+                           uint64_t n, float *lo, float *hi) {
+  return guarded([&] {
+    if (n && (!radii || !q_norm2 || !lo || !hi)) throw ArgError("invalid arguments");
+    for (uint64_t i = 0; i < n; ++i) {
+      const alaya_amd::FlatRangeBound b = alaya_amd::flat_range_bound(ip != 0, radii[i], q_norm2[i], b_max, k_acc, contraction);
+      lo[i] = b.lo;
+      hi[i] = b.hi;
+    }
   });
 }
 

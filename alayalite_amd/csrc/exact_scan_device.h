@@ -159,5 +159,43 @@ __device__ __forceinline__ void pass(const uint32_t *ids, const float *base, uin
   }
 }
 
+// The reference distance of a single (query, row) pair on a group of 8 lanes (lane m of the group), the order above
+// (flat_range_mfma_kernel verifies its band with it):
+// 32-blocks, 8-blocks on lanes 0-1, the xor 2 / 4 / 1 sum, the scalar tail, the negation for IP.  q: the padded
+// query (16-byte aligned), row: the base row.
+template <bool kIp>
+__device__ __forceinline__ float pair_distance(const float *q, const float *row, uint32_t dim, uint32_t m) {
+  const uint32_t T = dim >> 5;
+  const uint32_t nb8 = (dim - 32 * T) >> 3;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  auto step = [&](uint32_t off) {
+    const float4 x = *reinterpret_cast<const float4 *>(q + off);
+    const float4 y = *reinterpret_cast<const float4 *>(row + off);
+    if constexpr (kIp) {
+      a0 = fmaf(x.x, y.x, a0); a1 = fmaf(x.y, y.y, a1); a2 = fmaf(x.z, y.z, a2); a3 = fmaf(x.w, y.w, a3);
+    } else {
+      const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
+      a0 = fmaf(d0, d0, a0); a1 = fmaf(d1, d1, a1); a2 = fmaf(d2, d2, a2); a3 = fmaf(d3, d3, a3);
+    }
+  };
+  for (uint32_t t = 0; t < T; ++t) step(32 * t + 4 * m);
+  if (m < 2)
+    for (uint32_t bb = 0; bb < nb8; ++bb) step(32 * T + 8 * bb + 4 * m);
+  a0 += lane_xor<2>(a0); a1 += lane_xor<2>(a1); a2 += lane_xor<2>(a2); a3 += lane_xor<2>(a3);
+  a0 += lane_xor<4>(a0); a1 += lane_xor<4>(a1); a2 += lane_xor<4>(a2); a3 += lane_xor<4>(a3);
+  const float s0 = a0 + lane_xor<1>(a0), s1 = a1 + lane_xor<1>(a1);
+  const float s2 = a2 + lane_xor<1>(a2), s3 = a3 + lane_xor<1>(a3);
+  float res = (s0 + s1) + (s2 + s3);
+  for (uint32_t e = 32 * T + 8 * nb8; e < dim; ++e) {
+    if constexpr (kIp) {
+      res = fmaf(q[e], row[e], res);
+    } else {
+      const float d = q[e] - row[e];
+      res = fmaf(d, d, res);
+    }
+  }
+  return kIp ? -res : res;
+}
+
 }  // namespace exact_scan
 }  // namespace alaya_amd

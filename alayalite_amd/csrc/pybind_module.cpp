@@ -1456,6 +1456,13 @@ class DeviceIndex : public LaunchControls {
     check(alaya_index_flat_range_last(ix_, o));
     return py::make_tuple(o[0], o[1], o[2], o[3], o[4], o[5]);
   }
+  // of the last exact range search: (path: 0 f32 scan, 1 MFMA scan; pairs verified exactly; band pairs among
+  // them; pairs proven hits without a distance)
+  py::tuple flat_range_path() const {
+    uint64_t o[4] = {0, 0, 0, 0};
+    check(alaya_index_flat_range_path(ix_, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3]);
+  }
   int flat_contraction() const {
     int c = -1;
     check(alaya_index_flat_last_contraction(ix_, &c));
@@ -1672,6 +1679,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
            py::arg("max_results"), py::arg("words") = py::none(), py::arg("groups") = py::none())
       .def("flat_range_search_device", &DeviceIndex::flat_range_search_device)
       .def("flat_range_last", &DeviceIndex::flat_range_last)
+      .def("flat_range_path", &DeviceIndex::flat_range_path)
       .def("flat_diag", &DeviceIndex::flat_diag)
       .def("flat_contraction", &DeviceIndex::flat_contraction)
       .def("search_sq8_device", &DeviceIndex::search_sq8_device)
@@ -1749,6 +1757,20 @@ PYBIND11_MODULE(_alayalitepy, m) {
     check(alaya_flat_range_plan(n_eligible, nq, max_results, stride, cus, o));
     return py::make_tuple(o[0], o[1], o[2], o[3], o[4], o[5]);
   }, py::arg("n_eligible"), py::arg("nq"), py::arg("max_results"), py::arg("stride"), py::arg("cus"));
+  // the MFMA range scan's launch plan (alaya_flat_range_mfma_plan), same fields as flat_range_plan
+  m.def("flat_range_mfma_plan", [](uint64_t n, uint64_t nq, uint32_t max_results, uint32_t cus) {
+    uint64_t o[6] = {0, 0, 0, 0, 0, 0};
+    check(alaya_flat_range_mfma_plan(n, nq, max_results, cus, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3], o[4], o[5]);
+  }, py::arg("n"), py::arg("nq"), py::arg("max_results"), py::arg("cus"));
+  // the MFMA range scan's thresholds on the host (flat_range_bound.h): (lo, hi) per query
+  m.def("flat_range_bound", [](int ip, int contraction, uint32_t k_acc, float b_max, F32Array radii, F32Array q_norm2) {
+    if (radii.size() != q_norm2.size()) throw std::invalid_argument("radii and q_norm2 differ in size");
+    py::array_t<float> lo(radii.size()), hi(radii.size());
+    check(alaya_flat_range_bound(ip, contraction, k_acc, b_max, radii.data(), q_norm2.data(),
+                                 static_cast<uint64_t>(radii.size()), lo.mutable_data(), hi.mutable_data()));
+    return py::make_tuple(lo, hi);
+  }, py::arg("ip"), py::arg("contraction"), py::arg("k_acc"), py::arg("b_max"), py::arg("radii"), py::arg("q_norm2"));
   // the flat search's inner-product bound on the host (flat_bound.h): slack per query, and the test
   m.def("flat_ip_slack", [](int contraction, uint32_t k_acc, F32Array q_norm2, CArray<int> q_exp, float b_max,
                             int base_exp) {

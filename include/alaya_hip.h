@@ -581,6 +581,34 @@ int alaya_index_flat_range_last(const alaya_index *ix, uint64_t *out);
  * rows are too wide for the LDS. */
 int alaya_flat_range_plan(uint64_t n_eligible, uint64_t nq, uint32_t max_results, uint32_t stride, uint32_t cus,
                           uint64_t *out);
+/* The second scan of alaya_index_flat_range_search*: an MFMA scan (csrc/flat_range_mfma_kernels.hip) that walks
+ * all rows of the index as 32-row tiles -- one word of (mask AND validity AND below n) each -- computes an
+ * approximate distance by the bf16 hi/lo split contraction and classifies every (query, row) pair against two
+ * per-query thresholds (csrc/flat_range_bound.h): proven within the radius, proven outside, or the band, whose
+ * reference-order f32 distance decides.  Proven hits are counted without a distance unless they are among the
+ * first `slots` of their (chunk, query) pair, which are stored.  The answer is the f32 scan's bit for bit
+ * (rules 1-7 above).  Path rule, per mask: ALAYA_FLAT_RANGE_MFMA=0 / 1 forces the f32 / the MFMA scan; unset,
+ * ALAYA_FLAT_RANGE_CHUNK_ROWS or ALAYA_FLAT_RANGE_STAGING_BYTES select the f32 scan, and otherwise the MFMA
+ * scan runs from a fixed eligible share of the rows upwards (DESIGN.md "Round 24"; the measured share is 0.2, but the scan loses at radii that admit
+ * most rows, so the share is set above 1: never).
+ * alaya_index_flat_range_last keeps its meaning on both paths (out[2] = 128 on the MFMA scan).
+ * alaya_index_flat_range_path, of the last call (waits for that call's launches): out[0] = 1 when a mask ran the MFMA
+ * scan, else 0; over its MFMA launches, out[1] = pairs whose exact distance was computed, out[2] = those of
+ * them in the band, out[3] = pairs counted as proven hits without a distance. */
+int alaya_index_flat_range_path(alaya_index *ix, uint64_t *out);
+/* The MFMA range scan's launch plan as pure host arithmetic: for n rows (all of the index's), nq queries of one
+ * mask, the cap and `cus` compute units, out[0] = rows per chunk (a multiple of 128: a super-tile of four
+ * 32-row tiles), out[1] = chunks, out[2] = 128 queries per workgroup, out[3] = queries per scan launch (a
+ * multiple of 128), out[4] = stored hits per (chunk, query), out[5] = staging bytes of one launch, within the
+ * 256 MiB staging cap. */
+int alaya_flat_range_mfma_plan(uint64_t n, uint64_t nq, uint32_t max_results, uint32_t cus, uint64_t *out);
+/* The MFMA range scan's thresholds, evaluated on the host by the function the scan's prologue calls
+ * (flat_range_bound.h): for radius radii[i] and |q|^2 = q_norm2[i] (an f32 sum), rows with |b| <= b_max, the
+ * contraction (0 = f32, 1 = bf16 hi/lo split) over k_acc columns and the metric (ip = 0: L2 with d~ = (|q|^2
+ * + |b|^2) - 2 C~; 1: d~ = -C~):  d~ <= lo[i] proves d_ref <= radius, d~ > hi[i] proves d_ref > radius.
+ * lo = -inf, hi = +inf: no bound. */
+int alaya_flat_range_bound(int ip, int contraction, uint32_t k_acc, float b_max, const float *radii, const float *q_norm2,
+                           uint64_t n, float *lo, float *hi);
 /* Tuning / introspection: LDS visited-table size (log2 slots, 6..16; 0 = automatic) and layout
  * (0 = automatic, 1 = compact 16-bit slots, 2 = 32-bit id slots, 3 = compact with probe distance
  * capped at 2, a test hook for the spill-on-long-probe path).  Results never depend on either:

@@ -1,6 +1,6 @@
 """Range search on a GIST-shaped device-built index: recall, counts and the two launches' times per radius.
 
-usage: python tools/range_sweep.py [--leg fixed|radius|sq8|exact] [--n 1000000] [--nq 1000] [--dim 960] [--ef 387] [--reps 10] [--rounds 5] [--out FILE]
+usage: python tools/range_sweep.py [--leg fixed|radius|sq8|exact|mfma] [--n 1000000] [--nq 1000] [--dim 960] [--ef 387] [--reps 10] [--rounds 5] [--out FILE]
 
 Radii: per query, the exact m-th neighbour distance of the flat search's top 224 (exact_search's answer), for
 m in 1, 10, 50, 200, at max_results 1024 -- so the ground truth, the rows of that answer with d <= r, is exact;
@@ -25,7 +25,10 @@ defaults.
 
 --leg exact measures the exact range scan (exact_leg below): against the exact filtered k-NN with a radius that
 admits nothing, its scan, gather and sort per radius and cap, and -- with the exact call as the ground truth, no
-query left out -- the range recall of both graph range searches, [--target-rows 1000] [--no-graph]."""
+query left out -- the range recall of both graph range searches, [--target-rows 1000] [--no-graph].
+
+--leg mfma measures the exact range search's MFMA scan (ALAYA_FLAT_RANGE_MFMA=1) against its f32 scan (=0) with
+--leg exact's rows, queries and timing (mfma_leg below); run it once per width, --dim 960 and --dim 128."""
 import argparse
 import json
 import os
@@ -455,6 +458,104 @@ def exact_leg(args):
                           frontier_cut=int((mo[:, 0] > front).sum()), n_dist=float(cnt.cpu().numpy()[:, 0].mean())))
 
 
+def mfma_leg(args):
+    """--leg mfma: DeviceIndex.flat_range_search_device under ALAYA_FLAT_RANGE_MFMA=1 against =0, max_results 1024,
+    device events, 3 warm-ups then --rounds rounds of --reps launches, the launches of a comparison alternated in
+    this process; medians with the spread (max - min) / median.
+      radius  no mask; radius at each query's exact 10th and 200th neighbour distance and +inf; the unmasked
+              flat_search_device (k 10) in the same rounds as the yardstick; flat_range_path() of the MFMA call
+              (verified, band, proven pairs); the counts of the two paths are compared.
+      share   masks of share 0.01, 0.05, 0.1, 0.2, 0.5 and 1 at the 10th-neighbour radius, both paths.
+    gain = f32 median / MFMA median; it counts when it exceeds 1 + the f32 scan's own spread.  tflops: 2 n nq
+    k_acc operations over the MFMA call's median (k_acc = the stride rounded up to 64)."""
+    import torch
+    from alayalite_amd import _native
+    from alayalite_amd.utils import pack_allow
+    from workloads.datasets import gist_like
+
+    st = torch.cuda.current_stream()
+    n, nq, cap = args.n, args.nq, 1024
+    base, queries = gist_like(n, nq, dim=args.dim)
+    dev = _native._ext.DeviceIndex(0)
+    dev.set_base(base, 0)
+    k_acc = -(-(-(-args.dim // 32) * 32) // 64) * 64
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    def timed(run):
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(args.reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    def stat(v):
+        med = float(np.median(v))
+        return dict(median_ms=med, spread=(max(v) - min(v)) / med, ms=sorted(v))
+
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    counts = torch.empty((nq,), dtype=torch.int32, device="cuda")
+    ids = torch.empty((nq, cap), dtype=torch.int32, device="cuda")
+    d = torch.empty((nq, cap), dtype=torch.float32, device="cuda")
+    k_ids = torch.empty((nq, K), dtype=torch.int32, device="cuda")
+    k_d = torch.empty((nq, K), dtype=torch.float32, device="cuda")
+    flags = torch.empty((nq,), dtype=torch.int32, device="cuda")
+
+    def ranged(path, radii_t, words=None):
+        os.environ["ALAYA_FLAT_RANGE_MFMA"] = str(path)
+        dev.flat_range_search_device(qd.data_ptr(), nq, radii_t.data_ptr(), cap, 0 if words is None else words.data_ptr(),
+                                     0 if words is None else 1, 0, counts.data_ptr(), ids.data_ptr(), d.data_ptr(),
+                                     st.cuda_stream)
+
+    def knn():
+        dev.flat_search_device(qd.data_ptr(), nq, K, k_ids.data_ptr(), k_d.data_ptr(), flags.data_ptr(), st.cuda_stream)
+
+    def compare(rec, radii_t, words, yardstick):
+        ms = {0: [], 1: [], "knn": []}
+        for _ in range(args.rounds):
+            for path in (0, 1):
+                ms[path].append(timed(lambda: ranged(path, radii_t, words)))
+            if yardstick:
+                ms["knn"].append(timed(knn))
+        got = {}
+        for path in (0, 1):
+            ranged(path, radii_t, words)
+            torch.cuda.synchronize()
+            got[path] = counts.cpu().numpy().view(np.uint32).copy()
+        assert np.array_equal(got[0], got[1])
+        path = [int(v) for v in dev.flat_range_path()]
+        f32, mfma = stat(ms[0]), stat(ms[1])
+        rec.update(mean_count=float(got[1].mean()), f32=f32, mfma=mfma, gain=f32["median_ms"] / mfma["median_ms"],
+                   counts_as_gain=f32["median_ms"] / mfma["median_ms"] > 1 + f32["spread"], path=path,
+                   range_last=[int(v) for v in dev.flat_range_last()],
+                   tflops=2.0 * n * nq * k_acc / (mfma["median_ms"] * 1e-3) / 1e12)
+        if yardstick:
+            rec.update(knn_k10=stat(ms["knn"]))
+        emit(rec)
+
+    _, gt_d, _ = dev.flat_search(queries, GT)
+    r10 = torch.from_numpy(np.ascontiguousarray(gt_d[:, 9])).cuda()
+    r200 = torch.from_numpy(np.ascontiguousarray(gt_d[:, 199])).cuda()
+    for name, radii_t in (("m=10", r10), ("m=200", r200), ("inf", torch.full((nq,), float("inf"), device="cuda"))):
+        compare(dict(leg="radius", radius=name), radii_t, None, True)
+    rng = np.random.default_rng(5)
+    for share in (0.01, 0.05, 0.1, 0.2, 0.5, 1.0):
+        allow = rng.random(n) < share if share < 1 else np.ones(n, bool)
+        words = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+        compare(dict(leg="share", share=share, eligible=int(allow.sum())), r10, words, False)
+    os.environ.pop("ALAYA_FLAT_RANGE_MFMA", None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1000000)
@@ -464,7 +565,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", choices=("fixed", "radius", "sq8", "exact"), default="fixed")
+    ap.add_argument("--leg", choices=("fixed", "radius", "sq8", "exact", "mfma"), default="fixed")
     ap.add_argument("--target-rows", type=int, default=1000, help="exact leg: rows per query of the wide radius")
     ap.add_argument("--no-graph", action="store_true", help="exact leg: skip the recall part (no graph build)")
     ap.add_argument("--small-ef", type=int, default=64)
@@ -478,6 +579,8 @@ def main():
     args.dim, args.ef = args.dim or 960, args.ef or 387
     if args.leg == "exact":
         return exact_leg(args)
+    if args.leg == "mfma":
+        return mfma_leg(args)
 
     import torch
     from alayalite_amd import _native
