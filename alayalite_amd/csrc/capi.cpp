@@ -396,7 +396,8 @@ bool helpers_requested(const alaya_index *ix, const SearchParams &p, uint64_t nq
 // in every wave's region (hop: the through search's kernel).  range: the range search -- its own kernel's
 // registers and no result pool (more: its radius mode's kernel).
 uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchVariant &v, uint64_t nq, uint32_t ef,
-                      int W = 1, uint32_t filter_k = 0, bool hop = false, bool range = false, bool more = false) {
+                      int W = 1, uint32_t filter_k = 0, bool hop = false, bool range = false, bool more = false,
+                      bool filter_screen = false) {
   const uint32_t lbits = std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(ix->n, 2)));
   const int mode = ix->visited_mode_override;  // 0 auto, 1 compact, 2 wide, 3 compact + short probes
   auto set_mode = [&](uint32_t l, bool compact) {
@@ -447,6 +448,7 @@ uint32_t size_visited(alaya_index *ix, SearchParams &p, const alaya_amd::SearchV
                 ? alaya_amd::range_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, probe_lds, &vgpr_blocks)
             : range ? alaya_amd::range_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
             : !filter_k ? alaya_amd::search_occupancy(v, p.ip, W, probe_lds, &vgpr_blocks)
+            : filter_screen ? alaya_amd::filtered_screen_search_occupancy(ix->dim, W, probe_lds, &vgpr_blocks)
             : hop ? alaya_amd::filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks)
             : p.sq8_order ? alaya_amd::filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, probe_lds, &vgpr_blocks)
                           : alaya_amd::filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, probe_lds, &vgpr_blocks),
@@ -505,6 +507,7 @@ int stream_cus(const alaya_index *ix, hipStream_t s) {
 }
 
 bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStream_t stream);
+bool filter_screen_asked(uint32_t dim);
 
 // What policy wants of a search's kernel: the features (kMode bits, search_variants.h) of one launch,
 // decided in the order they depend on each other -- stamps and the prefetch check come with the
@@ -782,9 +785,10 @@ void do_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint3
 }
 
 // Filtered graph search (alaya_index_filtered_search*, filtered_search_kernel): planned as the plain
-// (mode 0) search of the shape -- one searcher per wave, no helpers, screen, scout or two-waves mode --
+// (mode 0) search of the shape -- one searcher per wave, no helpers, scout or two-waves mode --
 // with a result pool of k entries at the end of every wave's LDS region and the occupancy of the
-// filtered kernel itself.  d_allow: n_masks x ceil(n / 32) words; d_mask_of_query: nq indices or null.
+// filtered kernel itself.  Where filter_screen_asked and ensure_screen settle on the integer screen the launch
+// is filtered_screen_search_kernel's: the same plan with that kernel's occupancy, the same results.  d_allow: n_masks x ceil(n / 32) words; d_mask_of_query: nq indices or null.
 //
 // sq8: the search stage of the filtered SQ8 search (alaya_index_filtered_search_sq8*, filtered_sq8_search_kernel) --
 // the same plan for the mode-0 SQ8 request of the shape (four waves per workgroup beside the shared scale / min,
@@ -825,7 +829,12 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   const SearchVariant &plain = resolve_search_variant({ix->dim, p.ip, p.sq8_order, ix->generic, 0});
   int W = search_waves(p);
   while (W > 1 && static_cast<uint64_t>(W) > nq) W /= 2;
-  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k, hop, range != nullptr, more != nullptr);
+  // The integer candidate screen (filtered_screen_search_kernel): the plain f32 filtered launch only, where the
+  // width has a screening kernel (L2, no generic order) and the integer format is the one asked for; the records
+  // are built here if no batch_search built them, and a failed allocation leaves the plain filtered kernel.
+  const bool screen = !sq8 && !hop && !range && !more && filter_screen_asked(ix->dim) &&
+                      ensure_screen(ix, p, true, stream) && ix->screen_format == 3u;
+  p.hash_log2 = size_visited(ix, p, plain, nq, ef, W, k, hop, range != nullptr, more != nullptr, screen);
   const size_t traversal_lds = search_wave_lds_bytes(ix->stride, ef, p.hash_log2, p.vis_rbits != kVisWide, p.sq8_order);
   p.wave_lds = static_cast<uint32_t>(traversal_lds + (range ? 0 : filter_result_lds_bytes(k)));
   FilterParams f{};
@@ -844,6 +853,7 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
             : range ? range_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
             : sq8 ? filtered_sq8_search_occupancy(ix->dim, p.sq8_order, p.ip, W, lds, &per_cu)
             : hop ? filtered_hop_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu)
+            : screen ? filtered_screen_search_occupancy(ix->dim, W, lds, &per_cu)
                 : filtered_search_occupancy(ix->dim, ix->generic, p.ip, W, lds, &per_cu),
             "occupancy");
   per_cu = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(per_cu, max_search_waves_per_cu() / W)));
@@ -855,12 +865,19 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
   scratch_acquire(ix, stream);
   const uint64_t searchers = static_cast<uint64_t>(grid) * W;
   prepare_spill(ix, p, searchers, stream);
-  record_launch(ix, p, grid, W, lds, per_cu, searchers, stream);  // (no scout, helpers or screen: p has none set)
+  if (screen) {
+    p.screen = 3u;
+    p.screen_u8 = ix->screen_copy[1].rows.as<uint8_t>();
+    ix->screen_stats.reserve(searchers * 8);
+    p.screen_stats = ix->screen_stats.as<uint32_t>();
+  }
+  record_launch(ix, p, grid, W, lds, per_cu, searchers, stream);  // (no scout or helpers: p has none set)
   hip_check(more    ? launch_range_more_search(p, f, *range, *more, grid, W, lds, stream)
             : range && sq8 ? launch_range_sq8_search(p, f, *range, grid, W, lds, stream)
             : range ? launch_range_search(p, f, *range, grid, W, lds, stream)
             : sq8 ? launch_filtered_sq8_search(p, f, grid, W, lds, stream)
             : hop ? launch_filtered_hop_search(p, f, HopParams{d_through}, grid, W, lds, stream)
+            : screen ? launch_filtered_screen_search(p, f, grid, W, lds, stream)
                   : launch_filtered_search(p, f, grid, W, lds, stream),
             "filtered search launch");
   scratch_release(ix, stream);
@@ -878,6 +895,26 @@ void do_filtered_search(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t
 // screened width.  ALAYA_SEARCH_SCREEN = 8 / 1 still ask for the other two.
 uint32_t screen_default(uint32_t dim) {
   return (dim == 512 || dim == 768 || dim == 960 || dim == 1024) ? 3u : 0u;
+}
+
+// The format ALAYA_SEARCH_SCREEN names (ensure_screen), or the width's default.
+uint32_t screen_asked(uint32_t dim) {
+  const char *e = std::getenv("ALAYA_SEARCH_SCREEN");
+  const int asked = e && e[0] ? std::atoi(e) : -1;
+  return asked < 0 ? screen_default(dim) : (asked == 0 ? 0u : (asked == 9 ? 3u : (asked == 8 ? 2u : 1u)));
+}
+
+// Whether a plain f32 filtered launch of this width screens (filtered_screen_search_kernel) when the integer
+// screen is what ALAYA_SEARCH_SCREEN or its default names: ALAYA_FILTER_SCREEN = 0 / 1, unset = the default.
+// Default: on wherever batch_search screens by default (screen_default).  Measured on MI355X against the same
+// call unscreened, alternated in one process, medians of 5 (profiles/r25/): d = 960 1M rows 1k queries 5.377 ->
+// 3.221 ms, 10k queries 51.31 -> 29.82 ms; d = 768 500k rows 3.887 -> 2.792 ms; every screened run below every
+// unscreened one by far more than their 0.3 % spread, at every allowed share.  d = 512 / 1024 were not measured
+// at size and follow batch_search's default.
+bool filter_screen_asked(uint32_t dim) {
+  const char *e = std::getenv("ALAYA_FILTER_SCREEN");
+  const bool on = e && e[0] ? std::atoi(e) != 0 : screen_default(dim) == 3u;
+  return on && screen_asked(dim) == 3u;
 }
 
 // Rows [first, first + count) of the base into the screening copy of `format`.
@@ -899,10 +936,7 @@ void screen_fill(alaya_index *ix, uint32_t format, uint64_t first, uint64_t coun
 bool ensure_screen(alaya_index *ix, const SearchParams &p, bool eligible, hipStream_t stream) {
   ix->screen_format = 0;
   if (!eligible || !alaya_amd::search_has_screen(ix->dim, p.sq8_order, ix->generic, p.ip)) return false;
-  const char *e = std::getenv("ALAYA_SEARCH_SCREEN");
-  const int asked = e && e[0] ? std::atoi(e) : -1;
-  const uint32_t format =
-      asked < 0 ? screen_default(ix->dim) : (asked == 0 ? 0u : (asked == 9 ? 3u : (asked == 8 ? 2u : 1u)));
+  const uint32_t format = screen_asked(ix->dim);
   if (format == 0) return false;
   const uint32_t copy = format == 3 ? 2u : format;  // the integer pass reads format 2's records
   alaya_index::ScreenCopy &c = ix->screen_copy[copy - 1];

@@ -231,6 +231,13 @@ size_t filter_result_lds_bytes(uint32_t k);
 hipError_t filtered_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);
 hipError_t launch_filtered_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
                                   hipStream_t stream);
+// The filtered search under the integer candidate screen (filtered_screen_search_kernel; L2 on f32 rows of the
+// widths search_has_screen serves): the filtered search's plan and LDS layout, with p.screen == 3, p.screen_u8
+// the 8-bit records and p.screen_stats a row per searcher; its own kernel's resident workgroups per CU, and its
+// launch.  Both return hipErrorInvalidValue for a shape without such a kernel.
+hipError_t filtered_screen_search_occupancy(uint32_t dim, int waves, size_t lds, int *blocks_per_cu);
+hipError_t launch_filtered_screen_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
+                                         hipStream_t stream);
 // The through search (filtered_hop_search_kernel; f32 rows): the filtered search's plan and LDS layout, its
 // own kernel's resident workgroups per CU, and its launch.
 hipError_t filtered_hop_search_occupancy(uint32_t dim, bool generic, bool ip, int waves, size_t lds, int *blocks_per_cu);

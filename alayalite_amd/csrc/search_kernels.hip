@@ -2830,4 +2830,204 @@ hipError_t launch_range_rerank(const SearchParams &p, const RangeParams &r, uint
   return hipGetLastError();
 }
 
+// --------------------------------------------------------------------------------------------
+// Filtered search under the integer candidate screen: filtered_search_kernel's contract, bit for bit -- the
+// traversal pool, the visited set, every pop, the four counters, the result pool -- for L2 on f32 rows of
+// d = 512 / 768 / 960 / 1024, one searcher per wave, on the 8-bit records of hnsw_search_kernel's screen
+// (p.screen == 3: screen_query_codes, screen_dots_int, screen_int_bound).
+//
+// The rule.  An expansion hands its fresh candidates, in adjacency order, to pool.insert and -- the allowed,
+// valid ones -- to result.insert.  LinearPool::insert rejects `full && d >= last`, and while a pool is full
+// its last distance only falls.  So with tau_t = the traversal pool's worst distance and w_r = the result
+// pool's, both read once at the start of the expansion, a candidate with d >= tau_t changes nothing in the
+// traversal pool, and one with d >= w_r nothing in a full result pool.  A candidate whose proven lower bound
+// lb on d satisfies
+//     lb >= tau_t   and   (row not allowed or not valid,  or  result pool full and lb >= w_r)
+// -- `lb >= (ok ? max(tau_t, w_r) : tau_t)` with w_r = +inf for a pool that is not full -- is therefore dropped
+// before its f32 row is read: it stays visited and counted in n_dist.  Written as two comparisons so that a
+// NaN worst distance (rows that are not finite) keeps the candidate, as the pools' own tests would.  The
+// screen runs only once the traversal pool is full; until then, and in query_begin, the kernel is the plain
+// filtered kernel.
+//
+// Per expansion: the candidate's allow (and validity) word and its record's header and code sums are loaded
+// first, in straight-line code; the integer pass over the nf records follows, so those words arrive behind
+// the records; the bound and the decision; survivors are compacted in adjacency order with their allow bit
+// beside them (L.sd, free between two merges); a pass of one, two or the full number of rows per lane group
+// reads the survivors' f32 rows; then the two merges.  A survivor kept only for the result pool
+// (lb >= tau_t) goes through the traversal merge, which rejects it by its own test.
+// --------------------------------------------------------------------------------------------
+namespace {
+template <int kChunks>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(search_min_waves<kChunks, 0, kModeScreen>() ? search_min_waves<kChunks, 0, kModeScreen>() : 1, 8)))
+    filtered_screen_search_kernel(SearchParams p, FilterParams f) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  static_assert(kChunks >= 16 && kChunks % 2 == 0, "screen: wide f32 L2 rows");
+  constexpr int kSpace = 0;
+  constexpr bool kIP = false;
+  const int lane = lane_id();
+  const int wave = static_cast<int>(threadIdx.x >> 6);
+  const int W = static_cast<int>(blockDim.x >> 6);
+  const Lds L = carve_lds<kSpace>(p, smem, wave);
+  const Lds Lr = result_lds(L, f);
+  const uint64_t bit_words = (p.n + 31) / 32;
+  const uint64_t slot = static_cast<uint64_t>(blockIdx.x) * W + wave;
+  uint32_t *slot_bits = p.overflow_bits + slot * bit_words;
+  uint32_t *slot_dirty = p.dirty_words + slot * p.dirty_cap;
+  uint32_t *oks = reinterpret_cast<uint32_t *>(L.sd);  // the survivors' allow bits, between two merges
+  uint32_t n_screened = 0, n_screened_out = 0;         // wave-uniform, over the searcher's queries
+
+  for (;;) {
+    uint32_t qi = 0;
+    if (lane == 0) qi = atomicAdd(p.work_counter, 1u);
+    qi = read_lane(qi, 0);
+    if (qi >= p.nq) break;
+    const uint32_t *mask = f.allow + static_cast<uint64_t>(f.mask_of_query != nullptr ? f.mask_of_query[qi] : 0u) * f.mask_words;
+    for (uint32_t e = lane; e <= f.k; e += 64) {
+      Lr.pd[e] = 0.f;
+      Lr.pi[e] = 0u;
+    }
+    PoolState rs{0u, 0u, f.k};
+    Visited vs;
+    PoolState ps;
+    uint32_t n_dist = 0, n_expand = 0, n_dist_up = 0, n_hops_up = 0;
+    // (query_begin's first wave_sync orders the reset above before any offer)
+    query_begin<kIP, kChunks, kSpace>(p, L, qi, slot_bits, slot_dirty, nullptr, vs, ps, n_dist_up, n_hops_up,
+                                      [&](bool has, uint32_t id, float d) {
+                                        bool ok = false;
+                                        if (has) {
+                                          ok = ((mask[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                          if (p.valid != nullptr) ok = ok && ((p.valid[id >> 5] >> (id & 31)) & 1u) != 0u;
+                                        }
+                                        result_offer(rs, Lr, ok, id, d);
+                                      });
+    const ScreenQuery sq = screen_query_codes<kChunks>(p, L.q);  // the query's codes, in registers for the query
+
+    uint32_t pred = kEmpty, pred_v = kEmpty;  // adjacency prefetch of the predicted next pop
+    while (ps.cur < ps.size) {
+      const uint32_t u = pool_pop(ps, L);
+      ++n_expand;
+      uint32_t v = u == pred ? pred_v : adjacency_row(p, static_cast<int>(p.R), u);
+      const int cnt = adjacency_count(static_cast<int>(p.R), v);
+      bool act = lane < cnt;
+      if (p.dedup_edges) {  // graphs with repeated ids in a row: keep the first occurrence only
+        for (int j = 0; j < cnt; ++j) {
+          const uint32_t vj = read_lane(v, j);
+          if (j < lane && vj == v) act = false;
+        }
+      }
+      if (!vs.spilled && vs.count + 64 > vs.limit) spill_begin(vs);
+      const bool fresh = visit(vs, v, act);
+      const uint64_t fm = ballot(fresh);
+      const int nf = __popcll(fm);
+      pred = ps.cur < ps.size ? (L.pi[ps.cur] & kIdMask) : kEmpty;
+      if (pred != kEmpty) pred_v = adjacency_row(p, static_cast<int>(p.R), pred, pred_v);
+      if (nf == 0) continue;
+      // compact fresh ids in adjacency order
+      if (fresh) L.cid[__popcll(fm & ((1ull << lane) - 1ull))] = v;
+      wave_sync();
+      // The lane's candidate, and its allow word (and validity word): issued here, ahead of the screen pass,
+      // which needs the bit at the decision.
+      bool has = lane < nf;
+      uint32_t cid = has ? L.cid[lane] : 0u;
+      uint32_t aw = 0u, vw = 0xffffffffu;
+      if (has) {
+        aw = mask[cid >> 5];
+        if (p.valid != nullptr) vw = p.valid[cid >> 5];
+      }
+      bool ok = false;
+      int nd = nf;  // candidates whose f32 row is read
+      const bool screened = ps.size == ps.ef;
+      if (screened) {
+        const float tau_t = L.pd[ps.size - 1];
+        const bool r_full = rs.size == rs.ef;
+        const float w_r = r_full ? Lr.pd[rs.size - 1] : 0.f;
+        // the record's header and code sums, ahead of the pass's loads (a lane past the list reads row 0's)
+        const uint8_t *rp = p.screen_u8 + static_cast<uint64_t>(cid) * screen_u8_record_bytes(p.stride);
+        const float4 head = *reinterpret_cast<const float4 *>(rp);
+        const uint2 sums = *reinterpret_cast<const uint2 *>(rp + screen_u8_sums_offset(p.stride));
+        screen_dots_int<kChunks>(p, sq.codes, L.cid, nf, reinterpret_cast<uint32_t *>(L.cd), NoHook());
+        const float lb = screen_int_bound(p.stride, sq.err, sq.lo, sq.scale, sq.a1, sq.a2, head.x, head.y, head.z, sums.x,
+                                          sums.y, __float_as_uint(L.cd[lane]));  // (past the list: a bound nobody reads)
+        ok = has && (((aw & vw) >> (cid & 31)) & 1u) != 0u;
+        // lb == 0: no bound (never screened out)
+        const bool drop = lb > 0.f && lb >= tau_t && (!ok || (r_full && lb >= w_r));
+        const bool keep = has && !drop;
+        const uint64_t km = ballot(keep);
+        nd = __popcll(km);
+        n_screened += static_cast<uint32_t>(nf);
+        n_screened_out += static_cast<uint32_t>(nf - nd);
+        if (nd == 0) {
+          n_dist += nf;
+          continue;
+        }
+        // (every lane read its id before screen_dots_int's closing wave_sync)
+        if (keep) {
+          const int at = __popcll(km & ((1ull << lane) - 1ull));
+          L.cid[at] = cid;
+          oks[at] = ok ? 1u : 0u;
+        }
+        wave_sync();
+        has = lane < nd;
+        cid = has ? L.cid[lane] : 0u;
+        ok = has && oks[lane] != 0u;
+      }
+      // few survivors: a pass of one or two rows per lane group issues no more chunks than it needs
+      constexpr int kFull = RowPass<kChunks, 0>::kR;
+      if (nd <= 8) {
+        space_distances<kIP, kChunks, kSpace, false, 1>(p, L, L.cid, nd, L.cd);
+      } else if (kFull > 2 && nd <= 16) {
+        space_distances<kIP, kChunks, kSpace, false, 2>(p, L, L.cid, nd, L.cd);
+      } else {
+        space_distances<kIP, kChunks, kSpace>(p, L, L.cid, nd, L.cd);
+      }
+      n_dist += nf;
+      if (!screened) ok = has && (((aw & vw) >> (cid & 31)) & 1u) != 0u;  // the words arrive behind the rows
+      const float cd = has ? L.cd[lane] : 0.f;
+      wave_sync();
+      pool_merge(ps, L, has, cid, cd, [&](uint32_t nx) {
+        if (nx != pred) {
+          pred = nx;
+          pred_v = adjacency_row(p, static_cast<int>(p.R), nx, pred_v);
+        }
+      });
+      result_offer(rs, Lr, ok, cid, cd);
+    }
+
+    query_end(p, Lr, rs, qi, n_dist, n_expand, n_dist_up, n_hops_up);
+    visit_end(vs);
+    wave_sync();
+  }
+  screen_stats_out(p, slot, n_screened, n_screened_out, lane);
+}
+}  // namespace
+
+template <int... kChunks>
+static const void *filtered_screen_symbol_of(int chunks) {
+  const void *sym = nullptr;
+  ((chunks == kChunks ? (sym = reinterpret_cast<const void *>(&filtered_screen_search_kernel<kChunks>), 0) : 0), ...);
+  return sym;
+}
+
+// nullptr: the width has no such kernel (the caller asked search_has_screen first)
+static const void *filtered_screen_kernel_symbol(uint32_t dim) {
+  return filtered_screen_symbol_of<16, 24, 30, 32>(search_chunks(dim, false));
+}
+
+hipError_t launch_filtered_screen_search(const SearchParams &p, const FilterParams &f, int grid, int waves, size_t lds,
+                                         hipStream_t stream) {
+  const void *sym = filtered_screen_kernel_symbol(p.dim);
+  if (sym == nullptr || p.ip || p.generic || p.screen != 3u || p.screen_u8 == nullptr) return hipErrorInvalidValue;
+  SearchParams arg = p;
+  FilterParams farg = f;
+  void *args[] = {&arg, &farg};
+  return hipLaunchKernel(sym, dim3(grid), dim3(64 * waves), args, lds, stream);
+}
+
+hipError_t filtered_screen_search_occupancy(uint32_t dim, int waves, size_t lds, int *blocks_per_cu) {
+  const void *sym = filtered_screen_kernel_symbol(dim);
+  if (sym == nullptr) return hipErrorInvalidValue;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, sym, 64 * waves, lds);
+}
+
 }  // namespace alaya_amd

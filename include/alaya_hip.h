@@ -135,7 +135,15 @@ int alaya_index_shard_search_device(alaya_index *ix, const float *d_queries, uin
  * validity bitmap's layout as 32-bit words); n = the index's row count, removed rows included; bits
  * past n are ignored.  mask_of_query: nq indices below n_masks, the mask of each query; may be NULL
  * when n_masks == 1.  Environment ALAYA_FILTER_GRID=n (diagnostics, read per launch) holds the launch
- * to n workgroups, so every wave runs several queries one after the other; results never depend on it. */
+ * to n workgroups, so every wave runs several queries one after the other; results never depend on it.
+ * Candidate screen: where alaya_index_batch_search screens on the 8-bit records under integer dot products
+ * by default (L2 on f32 rows, d = 512 / 768 / 960 / 1024; ALAYA_SEARCH_SCREEN unset or 9) this search does
+ * too: once the traversal pool is full, a fresh candidate whose proven lower bound reaches the traversal
+ * pool's worst distance and -- if its row is allowed and valid -- the full result pool's worst distance
+ * does not read its f32 row.  Ids, distance bits and counters are those of the unscreened search; the
+ * records are built at the first such search if none exist.  Environment ALAYA_FILTER_SCREEN=0 (read per
+ * launch) turns only this search's screen off; ALAYA_SEARCH_SCREEN = 0, 1 or 8 leave it off as well.
+ * alaya_index_screen_stats then reports this launch's counts, (0, 0) after an unscreened one. */
 int alaya_index_filtered_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t ef,
                                 const uint32_t *allow_words, uint32_t n_masks, const uint32_t *mask_of_query,
                                 uint32_t *ids, float *dists, uint32_t *counters);

@@ -1,6 +1,6 @@
 """Filtered graph search on a GIST-shaped device-built index: rate and recall per allowed share.
 
-usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact|through] [--n 1000000] [--nq 1000] [--ef 387]
+usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact|through|screen] [--n 1000000] [--nq 1000] [--ef 387]
                                     [--shares 1,0.5,0.1,0.01] [--reps 20] [--out FILE]
 
   sweep     per share of allowed rows: queries/s of DeviceIndex.filtered_search_device, recall@10 of its
@@ -37,6 +37,14 @@ usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact
             rows against calc_gt_device(base[rows]) -- at --ef, and at the smallest ef of --hop-ladder that
             reaches recall 0.95, where one does -- and which of the three calls is the fastest that reaches
             0.95.  At share 1 the through / plain ratio is the all-ones launch's cost.
+  screen    the filtered search under the integer candidate screen (filtered_screen_search_kernel, the default
+            where batch_search screens) alternated in one process with the same call under ALAYA_FILTER_SCREEN=0
+            (filtered_search_kernel, the launch as it was before the screen), --rounds rounds of --reps launches
+            each after 3 warm-ups, per share: times, medians and spreads, the rule's verdict (the slowest
+            screened run faster than the fastest unscreened one by more than the unscreened runs' spread),
+            whether ids, distance bits and counters are equal, the launch's screen counts, both plans and the
+            recall@10 over the allowed rows; last, for orientation, the unfiltered batch search of the same
+            index with ALAYA_SEARCH_SCOUT=0 and as the environment plans it.
 Every leg prints one JSON line per measurement; --out appends them to a file."""
 import argparse
 import json
@@ -398,9 +406,100 @@ def through_leg(args):
         emit(rec)
 
 
+def screen_leg(args):
+    """The screened filtered search against the unscreened one, alternated in one process."""
+    import torch
+    from alayalite_amd import _native
+    from alayalite_amd.utils import calc_gt_device, pack_allow
+    from workloads.datasets import gist_like
+
+    ext = _native._ext
+    st = torch.cuda.current_stream()
+    n, nq, ef = args.n, args.nq, args.ef
+    base, queries = gist_like(n, nq, dim=args.dim)
+    dev = ext.DeviceIndex(0)
+    dev.set_base(base, 0)
+    dev.build_graph(32, 100, 100, 0, 0, 2)
+    print("index ready", file=sys.stderr, flush=True)
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    out = {on: (torch.empty((nq, K), dtype=torch.int32, device="cuda"), torch.empty((nq, K), dtype=torch.float32, device="cuda"),
+                torch.empty((nq, 4), dtype=torch.int32, device="cuda")) for on in (False, True)}
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim, k=K, ef=ef, metric="l2")
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    def timed(run):
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(args.reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    def stats(ms):
+        med = float(np.median(ms))
+        return dict(ms=sorted(ms), median=med, spread=(max(ms) - min(ms)) / med, qps=nq / med * 1e3)
+
+    for share in [float(s) for s in args.shares.split(",")]:
+        allow = np.ones(n, bool) if share >= 1.0 else np.random.default_rng(100 + round(1000 * share)).random(n) < share
+        words = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+
+        def filtered(on):
+            os.environ["ALAYA_FILTER_SCREEN"] = "1" if on else "0"  # (read per launch)
+            ids, dd, cnt = out[on]
+            dev.filtered_search_device(qd.data_ptr(), nq, K, ef, words.data_ptr(), 1, 0, ids.data_ptr(), dd.data_ptr(),
+                                       cnt.data_ptr(), st.cuda_stream)
+
+        ms = {False: [], True: []}
+        for _ in range(args.rounds):  # alternated: same rows, graph, queries and clocks
+            for on in (False, True):
+                ms[on].append(timed(lambda: filtered(on)))
+        plans, counts = {}, {}
+        for on in (False, True):
+            filtered(on)
+            torch.cuda.synchronize()
+            plans[on] = {k: int(v) for k, v in dev.last_plan().items()}
+            counts[on] = [int(v) for v in dev.screen_stats()]
+        host = {on: [t.cpu().numpy() for t in out[on]] for on in (False, True)}
+        rows = np.flatnonzero(allow)
+        gt_local, _ = calc_gt_device(base[rows], queries, K)
+        gt = np.where(gt_local >= 0, rows[np.clip(gt_local, 0, len(rows) - 1)], -1)
+        n_dist = float(host[True][2][:, 0].sum())
+        emit(dict(leg="screen", share=share, allowed=int(allow.sum()), unscreened=stats(ms[False]), screened=stats(ms[True]),
+                  screened_over_unscreened_qps=float(np.median(ms[False])) / float(np.median(ms[True])),
+                  faster_by_the_rule=max(ms[True]) < min(ms[False]) - (max(ms[False]) - min(ms[False])),
+                  equal_ids_distance_bits_counters=all(np.array_equal(a.view(np.uint32), b.view(np.uint32))
+                                                       for a, b in zip(host[False], host[True])),
+                  screen_stats=counts[True], screen_stats_unscreened=counts[False],
+                  dropped_share_of_n_dist=counts[True][1] / max(n_dist, 1.0), n_dist_per_query=n_dist / nq,
+                  recall_at_10=recall(host[True][0].view(np.uint32), gt),
+                  unscreened_recall_at_10=recall(host[False][0].view(np.uint32), gt),
+                  screened_plan=plans[True], unscreened_plan=plans[False]))
+    os.environ.pop("ALAYA_FILTER_SCREEN", None)
+    ids, dd, cnt = out[True]
+    for scout in ("0", None):  # orientation: the unfiltered search this kernel can approach, then the default one
+        if scout is None:
+            os.environ.pop("ALAYA_SEARCH_SCOUT", None)
+        else:
+            os.environ["ALAYA_SEARCH_SCOUT"] = scout
+        ms_u = [timed(lambda: dev.search_device(qd.data_ptr(), nq, K, ef, ids.data_ptr(), dd.data_ptr(), cnt.data_ptr(),
+                                                st.cuda_stream)) for _ in range(args.rounds)]
+        emit(dict(leg="screen-unfiltered", scout="off" if scout == "0" else "default", **stats(ms_u),
+                  screen_stats=[int(v) for v in dev.screen_stats()], plan={k: int(v) for k, v in dev.last_plan().items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact", "through"), default="sweep")
+    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact", "through", "screen"),
+                    default="sweep")
     ap.add_argument("--space", choices=("f32", "sq8"), default="f32",
                     help="exact leg: f32 = GIST-shaped L2 rows; sq8 = config 5's text-like IP rows with SQ8 codes")
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -425,6 +524,10 @@ def main():
         args.ef = args.ef or 387
         return through_leg(args)
     args.shares = args.shares or "1,0.5,0.1,0.01"
+    if args.leg == "screen":
+        args.dim = args.dim or 960
+        args.ef = args.ef or 387
+        return screen_leg(args)
     if args.leg in ("sq8", "sq8-ab"):
         args.dim = args.dim or 768
         return sq8_legs(args)
