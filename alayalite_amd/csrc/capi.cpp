@@ -21,6 +21,7 @@
 #include "hnsw_build.h"
 #include "flat_bound.h"
 #include "flat_filtered_kernels.h"
+#include "flat_filtered_mfma_kernels.h"
 #include "flat_range_kernels.h"
 #include "flat_range_mfma_kernels.h"
 #include "flat_range_bound.h"
@@ -147,6 +148,12 @@ struct alaya_index {
   // alaya_amd::flat_filtered_plan) and the queries ordered by mask
   DevBuf ff_ids, ff_sums, ff_count, ff_part_d, ff_part_i, ff_qlist;
   uint64_t ff_last[4] = {0, 0, 0, 0};  // alaya_index_flat_filtered_last
+  // its MFMA scan (flat_filtered_mfma_kernels.hip) borrows the range MFMA scan's query pad, meta and per-wave
+  // counter buffers below; its own are the call's two sums (alaya_index_flat_filtered_path)
+  DevBuf ff_stats;
+  int ff_path = 0;            // the last call's path: 0 the f32 scan, 1 the MFMA scan (for any of its masks)
+  uint64_t ff_pairs = 0;      // eligible rows x queries, summed over the last call's masks, when ff_path is 1
+  hipEvent_t ff_done = nullptr;  // recorded after the last MFMA call's launches: what alaya_index_flat_filtered_path waits for
   // exact range search (alaya_index_flat_range_search*): it shares the filtered scan's id list, block sums,
   // count, query order and partial-list buffers; its own are the per-(chunk, query) hit counts and the
   // all-ones words that stand for "no mask" on an index without a validity bitmap
@@ -1477,6 +1484,7 @@ void alaya_index_destroy(alaya_index *ix) {
   if (ix->scratch_used) (void)hipEventSynchronize(ix->scratch_ev);
   if (ix->scratch_ev) (void)hipEventDestroy(ix->scratch_ev);
   if (ix->fr_done) (void)hipEventDestroy(ix->fr_done);
+  if (ix->ff_done) (void)hipEventDestroy(ix->ff_done);
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
   delete ix;
 }
@@ -3054,6 +3062,13 @@ static uint32_t flat_compact_ids(alaya_index *ix, const uint32_t *words, const u
   return m;
 }
 
+// The MFMA scan (flat_filtered_mfma_kernels.hip) runs from this eligible share m / n of a mask upwards.  Measured
+// ("Round 26"; 1M rows, 1k queries, L2): at k = 10 faster from a share of 0.5 at 128 columns (2.0x at 1)
+// but only at 1 at 960 columns (1.75x; 0.91x at 0.5), and at k = 100 slower at every share (0.43x - 0.48x at 1) --
+// the crossover moves with k and the width, which a share rule cannot see.  So above 1: never by itself, only with
+// ALAYA_FLAT_FILTER_MFMA=1.
+constexpr double kFlatFilterMfmaShare = 2.0;
+
 // Every pointer but h_groups is a device pointer.  h_groups: the queries' mask indices on the host (checked
 // by the caller), or null: with more than one mask they are read back from d_groups and checked.
 // Masks are served one after another on `stream`; the host waits for each mask's allowed-row count.
@@ -3069,17 +3084,69 @@ static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uin
   const uint64_t mask_words = (ix->n + 31) / 32;
   const uint64_t forced = flat_filter_forced_rows();
   const uint32_t cus = static_cast<uint32_t>(stream_cus(ix, stream));
+  // the path: ALAYA_FLAT_FILTER_MFMA = 0 / 1 forces the f32 / the MFMA scan; unset, the f32 scan's chunk
+  // diagnostic selects the f32 scan, else the mask's eligible share decides (kFlatFilterMfmaShare)
+  const char *mfma_env = std::getenv("ALAYA_FLAT_FILTER_MFMA");
+  const int mfma_mode = (mfma_env && *mfma_env) ? (std::atoi(mfma_env) != 0 ? 1 : 0) : (forced ? 0 : -1);
+  const bool mfma_possible = mfma_mode == 1 || (mfma_mode < 0 && kFlatFilterMfmaShare <= 1.0);
+  if (mfma_possible) ensure_norms(ix, stream);  // ahead of the scratch: it waits for the norms once
   scratch_acquire(ix, stream);
+  bool mfma_used = false;
+  uint64_t mfma_pairs = 0;
   const std::vector<uint64_t> first = flat_group_queries(ix, nq, n_masks, h_groups, d_groups, "flat filtered search", stream);
+  const uint32_t *d_valid = ix->has_valid ? ix->valid.as<uint32_t>() : nullptr;
   uint64_t stats[4] = {0, 0, 0, 0};
   for (uint32_t g = 0; g < n_masks; ++g) {
     const uint64_t nq_g = first[g + 1] - first[g];
     if (nq_g == 0) continue;
-    const uint32_t m = flat_compact_ids(ix, d_allow + static_cast<uint64_t>(g) * mask_words,
-                                        ix->has_valid ? ix->valid.as<uint32_t>() : nullptr, "flat filtered compaction", stream);
-    const FlatFilteredPlan plan = flat_filtered_plan(m, nq_g, k, ix->stride, cus, forced);
+    const uint32_t *words = d_allow + static_cast<uint64_t>(g) * mask_words;
+    // (the MFMA scan reads the mask's words, not the id list: the compaction then only counts)
+    const uint32_t m = flat_compact_ids(ix, words, d_valid, "flat filtered compaction", stream);
+    const bool mfma = m != 0 && (mfma_mode == 1 || (mfma_mode < 0 && static_cast<double>(m) >= kFlatFilterMfmaShare * static_cast<double>(ix->n)));
+    FlatFilteredPlan plan{};
+    if (mfma) {
+      const FlatFilteredMfmaPlan mp = flat_filtered_mfma_plan(ix->n, nq_g, k, cus);
+      plan.chunk_rows = mp.chunk_rows;
+      plan.chunks = mp.chunks;
+      plan.tile = kFilteredMfmaQueries;
+      plan.sub_queries = mp.sub_queries;
+      plan.partial_bytes = mp.partial_bytes;
+    } else {
+      plan = flat_filtered_plan(m, nq_g, k, ix->stride, cus, forced);
+    }
     if (plan.tile == 0) throw ArgError("flat filtered search: k / dim too large for the LDS budget");
     stats[0] += m;
+    FlatFilteredMfmaParams mq{};
+    if (mfma) {
+      const uint64_t nq_up = std::min<uint64_t>(plan.sub_queries, (nq_g + kFilteredMfmaQueries - 1) / kFilteredMfmaQueries * kFilteredMfmaQueries);
+      mq.qwidth = flat_filtered_mfma_width(ix->stride);
+      ix->fr_qpad.reserve(nq_up * mq.qwidth * 4);
+      ix->fr_qmeta.reserve(nq_up * 8);
+      ix->fr_wave_stats.reserve(plan.chunks * (nq_up / 32) * 8);
+      ix->ff_stats.reserve(16);
+      if (!mfma_used) hip_check(launch_flat_filtered_mfma_clear(ix->ff_stats.as<unsigned long long>(), stream), "flat filtered search");
+      mfma_used = true;
+      mfma_pairs += static_cast<uint64_t>(m) * nq_g;
+      mq.base = ix->base.as<float>();
+      mq.norms = ix->norms.as<float>();
+      mq.n = ix->n;
+      mq.dim = ix->dim;
+      mq.stride = ix->stride;
+      mq.ip = ix->metric == ALAYA_METRIC_L2 ? 0 : 1;
+      mq.max_norm = ix->max_norm;
+      mq.queries = d_q;
+      mq.q_stride = ix->dim;
+      mq.q_list = n_masks > 1 ? ix->ff_qlist.as<uint32_t>() : nullptr;
+      mq.words = words;
+      mq.valid = d_valid;
+      mq.chunk_rows = plan.chunk_rows;
+      mq.chunks = plan.chunks;
+      mq.k = k;
+      mq.qpad = ix->fr_qpad.as<float>();
+      mq.qmeta = ix->fr_qmeta.as<float>();
+      mq.wave_stats = ix->fr_wave_stats.as<uint32_t>();
+      mq.stats = ix->ff_stats.as<unsigned long long>();
+    }
     FlatFilteredParams p{};
     p.base = ix->base.as<float>();
     p.dim = ix->dim;
@@ -3106,8 +3173,17 @@ static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uin
     for (uint64_t sb = 0; sb < nq_g; sb += plan.sub_queries) {
       p.q_first = first[g] + sb;
       p.nq = std::min<uint64_t>(plan.sub_queries, nq_g - sb);
-      if (m) {
+      if (mfma) {
+        mq.q_first = p.q_first;
+        mq.nq = p.nq;
+        mq.part_d = p.part_d;
+        mq.part_i = p.part_i;
+        hip_check(launch_flat_filtered_mfma_prepare(mq, stream), "flat filtered prepare");
+        hip_check(launch_flat_filtered_mfma_scan(mq, stream), "flat filtered MFMA scan");
+      } else if (m) {
         hip_check(launch_flat_filtered_scan(p, stream), "flat filtered scan");
+      }
+      if (m) {
         stats[1] = plan.chunks;
         stats[2] = plan.tile;
         ++stats[3];
@@ -3117,6 +3193,12 @@ static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uin
   }
   scratch_release(ix, stream);
   std::memcpy(ix->ff_last, stats, sizeof(stats));
+  ix->ff_path = mfma_used ? 1 : 0;
+  ix->ff_pairs = mfma_pairs;
+  if (mfma_used) {
+    if (!ix->ff_done) hip_check(hipEventCreateWithFlags(&ix->ff_done, hipEventDisableTiming), "flat filtered search");
+    hip_check(hipEventRecord(ix->ff_done, stream), "flat filtered search");
+  }
 }
 
 int alaya_index_flat_search_filtered_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k,
@@ -3159,6 +3241,36 @@ int alaya_index_flat_filtered_last(const alaya_index *ix, uint64_t *out) {
   return guarded([&] {
     if (!ix || !out) throw ArgError("invalid arguments");
     std::memcpy(out, ix->ff_last, sizeof(ix->ff_last));
+  });
+}
+
+int alaya_index_flat_filtered_path(alaya_index *ix, uint64_t *out) {
+  return guarded([&] {
+    if (!ix || !out) throw ArgError("invalid arguments");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    out[0] = static_cast<uint64_t>(ix->ff_path);
+    out[1] = out[2] = out[3] = 0;
+    if (!ix->ff_path) return;
+    set_device(ix);
+    unsigned long long sums[2] = {0, 0};
+    hip_check(hipEventSynchronize(ix->ff_done), "flat filtered path");  // the call's own launches, no other stream
+    hip_check(hipMemcpy(sums, ix->ff_stats.ptr, sizeof(sums), hipMemcpyDeviceToHost), "D2H");
+    out[1] = sums[0];
+    out[2] = sums[1];
+    out[3] = ix->ff_pairs;
+  });
+}
+
+int alaya_flat_filtered_mfma_plan(uint64_t n, uint64_t nq, uint32_t k, uint32_t cus, uint64_t *out) {
+  return guarded([&] {
+    if (!out) throw ArgError("invalid arguments");
+    if (k == 0 || k > alaya_amd::kFilteredMaxK) throw ArgError("flat filtered plan: k must be in 1..224");
+    const alaya_amd::FlatFilteredMfmaPlan r = alaya_amd::flat_filtered_mfma_plan(n, nq, k, cus);
+    out[0] = r.chunk_rows;
+    out[1] = r.chunks;
+    out[2] = alaya_amd::kFilteredMfmaQueries;
+    out[3] = r.sub_queries;
+    out[4] = r.partial_bytes;
   });
 }
 

@@ -1418,6 +1418,13 @@ class DeviceIndex : public LaunchControls {
     check(alaya_index_flat_filtered_last(ix_, o));
     return py::make_tuple(o[0], o[1], o[2], o[3]);
   }
+  // of the last exact filtered search: (path: 0 f32 scan, 1 MFMA scan; pairs verified exactly; pairs inserted
+  // into a chunk's list; eligible rows x queries over the masks)
+  py::tuple flat_filtered_path() const {
+    uint64_t o[4] = {0, 0, 0, 0};
+    check(alaya_index_flat_filtered_path(ix_, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3]);
+  }
   // every valid (and allowed) row within `radius` (a number or one per query) of the query, by an exact scan
   // (alaya_index_flat_range_search): (counts[nq], ids[nq, max_results], dists[nq, max_results]); words / groups as
   // range_search's masks, None for no mask
@@ -1680,6 +1687,7 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("flat_range_search_device", &DeviceIndex::flat_range_search_device)
       .def("flat_range_last", &DeviceIndex::flat_range_last)
       .def("flat_range_path", &DeviceIndex::flat_range_path)
+      .def("flat_filtered_path", &DeviceIndex::flat_filtered_path)
       .def("flat_diag", &DeviceIndex::flat_diag)
       .def("flat_contraction", &DeviceIndex::flat_contraction)
       .def("search_sq8_device", &DeviceIndex::search_sq8_device)
@@ -1750,6 +1758,12 @@ PYBIND11_MODULE(_alayalitepy, m) {
     check(alaya_flat_filtered_plan(n_allowed, nq, k, stride, cus, o));
     return py::make_tuple(o[0], o[1], o[2], o[3], o[4]);
   }, py::arg("n_allowed"), py::arg("nq"), py::arg("k"), py::arg("stride"), py::arg("cus"));
+  // the MFMA filtered scan's launch plan (alaya_flat_filtered_mfma_plan), same fields as flat_filtered_plan
+  m.def("flat_filtered_mfma_plan", [](uint64_t n, uint64_t nq, uint32_t k, uint32_t cus) {
+    uint64_t o[5] = {0, 0, 0, 0, 0};
+    check(alaya_flat_filtered_mfma_plan(n, nq, k, cus, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3], o[4]);
+  }, py::arg("n"), py::arg("nq"), py::arg("k"), py::arg("cus"));
   // the exact range scan's launch plan on the host (alaya_flat_range_plan): (rows per chunk, chunks, query
   // tile, queries per scan launch, stored hits per (chunk, query), staging bytes)
   m.def("flat_range_plan", [](uint64_t n_eligible, uint64_t nq, uint32_t max_results, uint32_t stride, uint32_t cus) {

@@ -521,6 +521,22 @@ int alaya_index_flat_search_filtered_device(alaya_index *ix, const float *d_quer
  * valid rows summed over the masks that had queries, out[1] = row chunks of the last scan, out[2] = its
  * query tile, out[3] = scan launches. */
 int alaya_index_flat_filtered_last(const alaya_index *ix, uint64_t *out);
+/* Environment ALAYA_FLAT_FILTER_MFMA (read per call): 1 serves every mask that has an eligible row with the
+ * MFMA scan (find_exact_gt over a subset has no counterpart), for masks that allow a large share of the rows:
+ * all n rows stream as 32-row tiles through a bf16 hi/lo split matrix contraction, a (query, row) pair is
+ * skipped when its approximate distance proves it behind the query's k-th best exact distance so far, and
+ * every other eligible pair gets the reference-order f32 distance -- the same ids and distance bits.  0 or
+ * unset: the row-reusing f32 scan above (unset, with ALAYA_FLAT_FILTER_CHUNK_ROWS set: also the f32 scan).
+ * alaya_index_flat_filtered_last then reports the MFMA scan's chunks (of all rows) and 128 as the query tile.
+ * alaya_index_flat_filtered_path, of the last call (waits for that call's launches): out[0] = 1 when a mask ran
+ * the MFMA scan, out[1] = (query, row) pairs whose exact distance was computed, out[2] = pairs inserted into a
+ * chunk's list, out[3] = eligible rows x queries summed over the masks; (0, 0, 0, 0) after an f32-scan call. */
+int alaya_index_flat_filtered_path(alaya_index *ix, uint64_t *out);
+/* The MFMA scan's launch plan as pure host arithmetic: for n rows, nq queries of one mask, k and `cus` compute
+ * units, out[0] = rows per chunk (a multiple of 128, at least max(1024, 32 k rounded up)), out[1] = chunks
+ * (out[0] out[1] >= n), out[2] = 128 queries per workgroup, out[3] = queries per scan launch (a multiple of
+ * 128), out[4] = bytes of partial lists of one launch, at most 256 MiB.  ALAYA_ERR_ARG if k is outside 1..224. */
+int alaya_flat_filtered_mfma_plan(uint64_t n, uint64_t nq, uint32_t k, uint32_t cus, uint64_t *out);
 /* The scan's launch plan as pure host arithmetic (no device; find_exact_gt over a subset has no
  * counterpart): for n_allowed rows, nq queries of one mask, k, rows of `stride` floats and `cus` compute
  * units, out[0] = rows per chunk (a multiple of the 32 rows a wave takes per pass; ALAYA_FLAT_FILTER_CHUNK_ROWS

@@ -1,6 +1,6 @@
 """Filtered graph search on a GIST-shaped device-built index: rate and recall per allowed share.
 
-usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact|through|screen] [--n 1000000] [--nq 1000] [--ef 387]
+usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact|mfma|through|screen] [--n 1000000] [--nq 1000] [--ef 387]
                                     [--shares 1,0.5,0.1,0.01] [--reps 20] [--out FILE]
 
   sweep     per share of allowed rows: queries/s of DeviceIndex.filtered_search_device, recall@10 of its
@@ -30,6 +30,12 @@ usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact
             flat search's time, last the two crossover shares.  --space sq8 runs config 5's shape
             (768-d IP, SQ8 codes) against filtered_search_sq8_device at m = k, ef 200; --dim 128 the
             narrow L2 shape.
+  mfma      the exact filtered scan on the MFMA scan (ALAYA_FLAT_FILTER_MFMA=1) alternated in one process with the
+            f32 scan (=0: the kernel and plan of the default path) and the unmasked flat search as the floor,
+            --rounds rounds of --reps launches each after a warm-up, per k of --ks and per share (default 0.05 .. 1):
+            times, medians, spreads, the ratio, whether the two filtered answers' ids and distance bits are equal,
+            flat_filtered_path()'s verified and inserted pairs per query, and the rule's verdict (the slowest MFMA
+            run faster than the fastest f32 run by more than the f32 runs' spread); last, per k, the shares won.
   through   the through search (DeviceIndex.filtered_search_hop_device: the traversal that steps through
             disallowed neighbours) alternated with the plain filtered search and the exact filtered scan in
             one process, --rounds rounds of --reps launches each after 3 warm-ups, per share of 1 .. 0.01:
@@ -293,6 +299,85 @@ def exact_leg(args):
               against_unmasked_exact_share=crossover(lambda g: float(np.median(flat_ms)))))
 
 
+def mfma_leg(args):
+    """The exact filtered search on the MFMA scan against the f32 scan and the unmasked exact search."""
+    import torch
+    from alayalite_amd import _native
+    from alayalite_amd.utils import pack_allow
+    from workloads.datasets import gist_like
+
+    ext = _native._ext
+    st = torch.cuda.current_stream()
+    n, nq = args.n, args.nq
+    base, queries = gist_like(n, nq, dim=args.dim)
+    dev = ext.DeviceIndex(0)
+    dev.set_base(base, 0)
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    flags = torch.empty((nq,), dtype=torch.int32, device="cuda")
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim, metric="l2")
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    def timed(run):
+        run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(args.reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    wins = []
+    for k in [int(v) for v in args.ks.split(",")]:
+        out = {m: (torch.empty((nq, k), dtype=torch.int32, device="cuda"), torch.empty((nq, k), dtype=torch.float32, device="cuda"))
+               for m in ("1", "0", "flat")}
+
+        def flat():
+            dev.flat_search_device(qd.data_ptr(), nq, k, out["flat"][0].data_ptr(), out["flat"][1].data_ptr(), flags.data_ptr(),
+                                   st.cuda_stream)
+
+        for share in [float(s) for s in args.shares.split(",")]:
+            allow = np.ones(n, bool) if share >= 1.0 else np.random.default_rng(100 + round(1000 * share)).random(n) < share
+            words = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+
+            def masked(mode):
+                os.environ["ALAYA_FLAT_FILTER_MFMA"] = mode  # read per call
+                dev.flat_search_filtered_device(qd.data_ptr(), nq, k, words.data_ptr(), 1, 0, out[mode][0].data_ptr(),
+                                                out[mode][1].data_ptr(), st.cuda_stream)
+
+            ms = {"1": [], "0": [], "flat": []}
+            for _ in range(args.rounds):  # alternated: same rows, queries and clocks
+                ms["1"].append(timed(lambda: masked("1")))
+                path = [int(v) for v in dev.flat_filtered_path()]
+                plan = [int(v) for v in dev.flat_filtered_last()]
+                ms["0"].append(timed(lambda: masked("0")))
+                ms["flat"].append(timed(flat))
+            med = {m: float(np.median(v)) for m, v in ms.items()}
+            spread0 = max(ms["0"]) - min(ms["0"])
+            win = max(ms["1"]) < min(ms["0"]) - spread0
+            same = all(bool(torch.equal(out["1"][j], out["0"][j])) for j in (0, 1))  # int32 ids, f32 bits (no NaN here)
+            emit(dict(leg="mfma", k=k, share=share, eligible=int(allow.sum()), mfma_ms=sorted(ms["1"]), f32_ms=sorted(ms["0"]),
+                      unmasked_ms=sorted(ms["flat"]), mfma_median=med["1"], f32_median=med["0"], unmasked_median=med["flat"],
+                      mfma_spread=(max(ms["1"]) - min(ms["1"])) / med["1"], f32_spread=spread0 / med["0"],
+                      f32_over_mfma=med["0"] / med["1"], ids_and_bits_equal=same, mfma_wins_by_the_rule=bool(win),
+                      verified_per_query=path[1] / nq, inserted_per_query=path[2] / nq, eligible_pairs=path[3],
+                      chunks=plan[1], scan_launches=plan[3],
+                      # the contraction's accumulated products over the whole call's time, the verify loop included:
+                      # 2 x n x nq x k_acc, k_acc the row width padded to 64 columns -- not a rate of useful work
+                      contraction_tflops_over_call=2.0 * n * nq * (-(-args.dim // 64) * 64) / (med["1"] * 1e-3) / 1e12))
+            wins.append((k, share, bool(win)))
+    os.environ.pop("ALAYA_FLAT_FILTER_MFMA", None)
+    for k in sorted({w[0] for w in wins}):
+        won = sorted(s for kk, s, w in wins if kk == k and w)
+        emit(dict(leg="mfma-crossover", k=k, shares_won=won, faster_from_share=won[0] if won else None))
+
+
 def through_leg(args):
     """The through search against the plain filtered search and the exact filtered scan, alternated."""
     import torch
@@ -498,7 +583,7 @@ def screen_leg(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact", "through", "screen"),
+    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact", "mfma", "through", "screen"),
                     default="sweep")
     ap.add_argument("--space", choices=("f32", "sq8"), default="f32",
                     help="exact leg: f32 = GIST-shaped L2 rows; sq8 = config 5's text-like IP rows with SQ8 codes")
@@ -509,6 +594,7 @@ def main():
     ap.add_argument("--ef-ladder", default="40,60,80,100,120,160,200,260,340,440")
     ap.add_argument("--shares", default="", help="default 1,0.5,0.1,0.01 (exact leg: 0.001,0.01,0.05,0.1,0.2,0.5,1)")
     ap.add_argument("--hop-ladder", default="10,16,24,32,48,64,96,128,192,256", help="through leg: the short ef sweep")
+    ap.add_argument("--ks", default="10,100", help="mfma leg: the k values")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default="")
@@ -518,6 +604,10 @@ def main():
         args.dim = args.dim or (768 if args.space == "sq8" else 960)
         args.ef = args.ef or (200 if args.space == "sq8" else 387)
         return exact_leg(args)
+    if args.leg == "mfma":
+        args.shares = args.shares or "0.05,0.1,0.2,0.5,1"
+        args.dim = args.dim or 960
+        return mfma_leg(args)
     if args.leg == "through":
         args.shares = args.shares or "1,0.5,0.2,0.1,0.05,0.02,0.01"
         args.dim = args.dim or 960
