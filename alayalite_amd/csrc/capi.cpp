@@ -25,6 +25,7 @@
 #include "flat_range_kernels.h"
 #include "flat_range_mfma_kernels.h"
 #include "flat_range_bound.h"
+#include "flat_select_kernels.h"
 #include "flat_kernels.h"
 #include <cstdlib>
 #include "screen_bound.h"
@@ -164,6 +165,12 @@ struct alaya_index {
   DevBuf fr_qpad, fr_qmeta, fr_wave_stats, fr_stats;
   int fr_path = 0;  // the last call's path: 0 the f32 scan, 1 the MFMA scan (for any of its masks)
   hipEvent_t fr_done = nullptr;  // recorded after the last MFMA call's launches: what alaya_index_flat_range_path waits for
+  // exact k-NN by selection (alaya_index_flat_select_search*, flat_select_kernels.hip): the per-query windows,
+  // histograms, span keys, edges, counts below the edge, states and radii, the eligible-row counter, and the
+  // range scan's nq x 4096 sorted lists and counts that are cut at k.  It borrows the range MFMA scan's query pad
+  // and meta buffers.
+  DevBuf sel_win, sel_hist, sel_span, sel_edge, sel_cum, sel_done, sel_radii, sel_eligible, sel_ids, sel_d, sel_cnt;
+  uint64_t sel_last[3] = {0, 0, 0};  // alaya_index_flat_select_last: full passes, pairs verified, fallback queries
   size_t overflow_clean = 0;  // leading bytes of `overflow` known to be zero (kernels leave it clean)
   size_t stab_clean = 0;      // the same for the spill tables
   // leading bytes of the two areas zeroed at least once since their buffer was allocated: equal to the
@@ -2921,6 +2928,44 @@ int alaya_index_flat_search_device(alaya_index *ix, const float *d_queries, uint
   });
 }
 
+// One query answered by exhaustive exact distances on the device and a host sort by (distance, id), over the
+// valid rows only: what a flat search falls back to.  d_query: the query's row on the device; ids, dists: k
+// host slots; vbits: the validity words, fetched at the first call (empty: every row is valid).
+static void flat_exhaustive_query(alaya_index *ix, const float *d_query, uint32_t k, uint32_t *ids, float *dists,
+                                  std::vector<uint32_t> &vbits) {
+  if (!ix->iota.ptr || ix->iota.bytes < ix->n * 4) {
+    std::vector<uint32_t> io(ix->n);
+    for (uint64_t i = 0; i < ix->n; ++i) io[i] = static_cast<uint32_t>(i);
+    ix->iota.reserve(ix->n * 4);
+    hip_check(hipMemcpy(ix->iota.ptr, io.data(), ix->n * 4, hipMemcpyHostToDevice), "H2D");
+  }
+  if (ix->has_valid && vbits.empty()) {
+    vbits.assign((ix->n + 31) / 32, 0u);
+    hip_check(hipMemcpy(vbits.data(), ix->valid.ptr, vbits.size() * 4, hipMemcpyDeviceToHost), "D2H");
+  }
+  ix->dout_buf.reserve(ix->n * 4);
+  SearchParams sp = base_params(ix);
+  sp.queries = d_query;
+  sp.q_stride = ix->dim;
+  hip_check(alaya_amd::launch_row_distances(sp, ix->iota.as<uint32_t>(), static_cast<uint32_t>(ix->n), 1,
+                                            ix->dout_buf.as<float>(), ix->stream), "exhaustive");
+  std::vector<float> all(ix->n);
+  hip_check(hipMemcpyAsync(all.data(), ix->dout_buf.ptr, ix->n * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
+  hip_check(hipStreamSynchronize(ix->stream), "exhaustive");
+  std::vector<uint32_t> order;
+  order.reserve(ix->n);
+  for (uint64_t i = 0; i < ix->n; ++i)
+    if (vbits.empty() || ((vbits[i >> 5] >> (i & 31)) & 1u)) order.push_back(static_cast<uint32_t>(i));
+  const uint64_t kk = std::min<uint64_t>(k, order.size());
+  std::partial_sort(order.begin(), order.begin() + kk, order.end(), [&](uint32_t a, uint32_t b) {
+    return all[a] < all[b] || (all[a] == all[b] && a < b);
+  });
+  for (uint64_t j = 0; j < k; ++j) {  // slots past the valid rows: (0xffffffff, FLT_MAX), as the scan
+    ids[j] = j < kk ? order[j] : 0xffffffffu;
+    dists[j] = j < kk ? all[order[j]] : FLT_MAX;
+  }
+}
+
 int alaya_index_flat_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k,
                             uint32_t *ids, float *dists, uint32_t *n_recomputed) {
   return guarded([&] {
@@ -2959,37 +3004,7 @@ int alaya_index_flat_search(alaya_index *ix, const float *queries, uint64_t nq, 
     for (uint64_t q = 0; q < nq; ++q) {
       if (!flags[q]) continue;
       ++redo;
-      if (!ix->iota.ptr || ix->iota.bytes < ix->n * 4) {
-        std::vector<uint32_t> io(ix->n);
-        for (uint64_t i = 0; i < ix->n; ++i) io[i] = static_cast<uint32_t>(i);
-        ix->iota.reserve(ix->n * 4);
-        hip_check(hipMemcpy(ix->iota.ptr, io.data(), ix->n * 4, hipMemcpyHostToDevice), "H2D");
-      }
-      if (ix->has_valid && vbits.empty()) {
-        vbits.assign((ix->n + 31) / 32, 0u);
-        hip_check(hipMemcpy(vbits.data(), ix->valid.ptr, vbits.size() * 4, hipMemcpyDeviceToHost), "D2H");
-      }
-      ix->dout_buf.reserve(ix->n * 4);
-      SearchParams sp = base_params(ix);
-      sp.queries = ix->q_buf.as<float>() + q * ix->dim;
-      sp.q_stride = ix->dim;
-      hip_check(alaya_amd::launch_row_distances(sp, ix->iota.as<uint32_t>(), static_cast<uint32_t>(ix->n), 1,
-                                                ix->dout_buf.as<float>(), ix->stream), "exhaustive");
-      std::vector<float> all(ix->n);
-      hip_check(hipMemcpyAsync(all.data(), ix->dout_buf.ptr, ix->n * 4, hipMemcpyDeviceToHost, ix->stream), "D2H");
-      hip_check(hipStreamSynchronize(ix->stream), "exhaustive");
-      std::vector<uint32_t> order;
-      order.reserve(ix->n);
-      for (uint64_t i = 0; i < ix->n; ++i)
-        if (vbits.empty() || ((vbits[i >> 5] >> (i & 31)) & 1u)) order.push_back(static_cast<uint32_t>(i));
-      const uint64_t kk = std::min<uint64_t>(k, order.size());
-      std::partial_sort(order.begin(), order.begin() + kk, order.end(), [&](uint32_t a, uint32_t b) {
-        return all[a] < all[b] || (all[a] == all[b] && a < b);
-      });
-      for (uint64_t j = 0; j < k; ++j) {  // slots past the valid rows: (0xffffffff, FLT_MAX), as the scan
-        ids[q * k + j] = j < kk ? order[j] : 0xffffffffu;
-        dv[q * k + j] = j < kk ? all[order[j]] : FLT_MAX;
-      }
+      flat_exhaustive_query(ix, ix->q_buf.as<float>() + q * ix->dim, k, ids + q * k, dv.data() + q * k, vbits);
     }
     if (dists) std::memcpy(dists, dv.data(), nq * k * 4);
     if (n_recomputed) *n_recomputed = redo;
@@ -3302,7 +3317,7 @@ constexpr double kFlatRangeMfmaShare = 2.0;
 // eligible-row count, never for the radii.
 static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const float *d_radii, uint32_t max_results,
                           const uint32_t *d_allow, uint32_t n_masks, const uint32_t *h_groups, const uint32_t *d_groups,
-                          uint32_t *d_counts, uint32_t *d_ids, float *d_dists, hipStream_t stream) {
+                          uint32_t *d_counts, uint32_t *d_ids, float *d_dists, hipStream_t stream, bool force_mfma = false) {
   using namespace alaya_amd;
   if (!ix->base.ptr) throw ArgError("index has no base vectors");
   if (ix->generic) throw ArgError("flat range search: float32 rows only");
@@ -3319,7 +3334,8 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
   // the path: ALAYA_FLAT_RANGE_MFMA = 0 / 1 forces the f32 / the MFMA scan; unset, the f32 scan's diagnostics
   // select the f32 scan, else the mask's eligible share decides (kFlatRangeMfmaShare)
   const char *mfma_env = std::getenv("ALAYA_FLAT_RANGE_MFMA");
-  const int mfma_mode = (mfma_env && *mfma_env) ? (std::atoi(mfma_env) != 0 ? 1 : 0) : ((forced || forced_staging) ? 0 : -1);
+  // (force_mfma: the selection search's radii are made for the MFMA scan's thresholds)
+  const int mfma_mode = force_mfma ? 1 : (mfma_env && *mfma_env) ? (std::atoi(mfma_env) != 0 ? 1 : 0) : ((forced || forced_staging) ? 0 : -1);
   const bool mfma_possible = mfma_mode == 1 || (mfma_mode < 0 && kFlatRangeMfmaShare <= 1.0);
   if (mfma_possible) ensure_norms(ix, stream);  // ahead of the scratch: it waits for the norms once
   scratch_acquire(ix, stream);
@@ -3554,6 +3570,194 @@ int alaya_flat_range_bound(int ip, int contraction, uint32_t k_acc, float b_max,
       lo[i] = b.lo;
       hi[i] = b.hi;
     }
+  });
+}
+
+// ---- exact k-NN by selection: span, histogram passes, radius, the MFMA range scan, cut (flat_select_kernels.hip) ----
+static bool flat_select_forced() {
+  const char *e = std::getenv("ALAYA_FLAT_SELECT");
+  return e && *e && std::atoi(e) != 0;
+}
+
+// Every pointer is a device pointer; d_ids / d_dists hold (nq, k).  The host waits on `stream` between the
+// passes (it reads the queries' states) and after the range scan (it reads the counts), so the results are
+// complete when this returns.  Returns the queries answered by the exhaustive recompute.
+static uint32_t do_flat_select(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, uint32_t *d_ids, float *d_dists,
+                               hipStream_t stream) {
+  using namespace alaya_amd;
+  if (!ix->base.ptr) throw ArgError("index has no base vectors");
+  if (ix->generic) throw ArgError("flat select search: float32 rows only");
+  if (k == 0 || k > kSelectMaxK) throw ArgError("flat select search needs 1 <= k <= " + std::to_string(kSelectMaxK));
+  if (nq == 0) return 0;
+  if (nq > 0x7fffffffull) throw ArgError("flat select search: too many queries");
+  if (ix->n == 0) throw ArgError("flat select search: the index has no rows");
+  const uint32_t cus = static_cast<uint32_t>(stream_cus(ix, stream));
+  const uint32_t cap = kFlatRangeMaxCap;
+  ensure_norms(ix, stream);  // ahead of the scratch: it waits for the norms once
+  scratch_acquire(ix, stream);
+  const uint64_t nq_up = (nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries;
+  const FlatRangeMfmaPlan plan = flat_range_mfma_plan(ix->n, nq, 1, cus);  // (a list of one: no floor on the chunk)
+  FlatSelectParams p{};
+  p.base = ix->base.as<float>();
+  p.norms = ix->norms.as<float>();
+  p.n = ix->n;
+  p.dim = ix->dim;
+  p.stride = ix->stride;
+  p.ip = ix->metric == ALAYA_METRIC_L2 ? 0 : 1;
+  p.max_norm = ix->max_norm;
+  p.valid = ix->has_valid ? ix->valid.as<uint32_t>() : nullptr;
+  p.chunk_rows = plan.chunk_rows;
+  p.chunks = plan.chunks;
+  p.nq = nq;
+  p.qwidth = flat_range_mfma_width(ix->stride);
+  ix->fr_qpad.reserve(nq_up * p.qwidth * 4);
+  ix->fr_qmeta.reserve(nq_up * 16);
+  ix->sel_win.reserve(nq_up * 12);
+  ix->sel_hist.reserve(nq_up * kSelectPitch * 4);
+  ix->sel_span.reserve(nq_up * 8);
+  ix->sel_edge.reserve(nq_up * 4);
+  ix->sel_cum.reserve(nq_up * 4);
+  ix->sel_done.reserve(nq_up * 4);
+  ix->sel_radii.reserve(nq_up * 4);
+  ix->sel_eligible.reserve(4);
+  ix->sel_ids.reserve(nq * cap * 4);
+  ix->sel_d.reserve(nq * cap * 4);
+  ix->sel_cnt.reserve(nq * 4);
+  p.qpad = ix->fr_qpad.as<float>();
+  p.qmeta = ix->fr_qmeta.as<float>();
+  p.win = ix->sel_win.as<float>();
+  p.hist = ix->sel_hist.as<uint32_t>();
+  p.span_keys = ix->sel_span.as<uint32_t>();
+  p.eligible = ix->sel_eligible.as<uint32_t>();
+  p.edge = ix->sel_edge.as<float>();
+  p.cum = ix->sel_cum.as<uint32_t>();
+  p.done = ix->sel_done.as<uint32_t>();
+  p.radii = ix->sel_radii.as<float>();
+  {
+    // the range scan's prepare kernel pads the queries and sums |q|^2; its thresholds (of radius 0) are not read
+    hip_check(hipMemsetAsync(ix->sel_radii.ptr, 0, nq_up * 4, stream), "flat select search");
+    FlatRangeMfmaParams mq{};
+    mq.dim = ix->dim;
+    mq.ip = p.ip;
+    mq.max_norm = ix->max_norm;
+    mq.queries = d_q;
+    mq.q_stride = ix->dim;
+    mq.radii = p.radii;
+    mq.nq = nq;
+    mq.qpad = ix->fr_qpad.as<float>();
+    mq.qwidth = p.qwidth;
+    mq.qmeta = ix->fr_qmeta.as<float>();
+    hip_check(launch_flat_range_mfma_prepare(mq, stream), "flat select prepare");
+  }
+  // 1. span: min and max of d~ over a strided sample of whole super-tiles with at least k eligible rows -- the
+  //    max over k eligible rows bounds the k-th d~ from above
+  uint32_t eligible = 0;
+  p.span = 1;
+  p.sup_step = flat_select_sample_step(ix->n, k);
+  for (;;) {
+    hip_check(launch_flat_select_init(p, stream), "flat select init");
+    hip_check(launch_flat_select_scan(p, stream), "flat select span");
+    hip_check(hipMemcpyAsync(&eligible, p.eligible, 4, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "flat select span");
+    if (eligible >= k || p.sup_step == 1) break;
+    p.sup_step = 1;  // a validity bitmap that leaves the sample short: span over every row
+  }
+  p.span = 0;
+  const bool all = eligible < k;  // fewer than k eligible rows in all (the last span saw every row): radius +inf
+  uint64_t full_passes = 0;
+  if (!all) {
+    const uint32_t target = flat_select_target(k);
+    std::vector<uint32_t> done(nq);
+    hip_check(launch_flat_select_window(p, stream), "flat select window");
+    if (p.sup_step > 1) {  // a histogram of the sample proposes [lo, e): at least k of its own rows lie below e
+      hip_check(launch_flat_select_clear(p, stream), "flat select clear");
+      hip_check(launch_flat_select_scan(p, stream), "flat select sample");
+      hip_check(launch_flat_select_pick(p, k, target, 1, stream), "flat select pick");
+      p.sup_step = 1;
+    }
+    // 2, 3. full passes: every decision is from counts over all rows.  At most kSelectMaxPasses; a query still
+    //       running then keeps the edge of its last pass, which admits at least k rows like any other
+    for (uint32_t pass = 0; pass < kSelectMaxPasses; ++pass) {
+      hip_check(launch_flat_select_clear(p, stream), "flat select clear");
+      hip_check(launch_flat_select_scan(p, stream), "flat select histogram");
+      hip_check(launch_flat_select_pick(p, k, target, 0, stream), "flat select pick");
+      ++full_passes;
+      hip_check(hipMemcpyAsync(done.data(), p.done, nq * 4, hipMemcpyDeviceToHost, stream), "D2H");
+      hip_check(hipStreamSynchronize(stream), "flat select histogram");
+      if (std::all_of(done.begin(), done.end(), [](uint32_t d) { return d != kSelectRunning; })) break;
+    }
+  }
+  // 4. the radii, then the MFMA range scan, gather and sort with cap 4096 and no mask
+  hip_check(launch_flat_select_radius(p, all ? 1 : 0, stream), "flat select radius");
+  do_flat_range(ix, d_q, nq, p.radii, cap, nullptr, 0, nullptr, nullptr, ix->sel_cnt.as<uint32_t>(), ix->sel_ids.as<uint32_t>(),
+                ix->sel_d.as<float>(), stream, /*force_mfma=*/true);
+  // 5. cut
+  hip_check(launch_flat_select_cut(ix->sel_cnt.as<uint32_t>(), ix->sel_ids.as<uint32_t>(), ix->sel_d.as<float>(), cap, nq, k,
+                                   d_ids, d_dists, stream), "flat select cut");
+  std::vector<uint32_t> counts(nq);
+  unsigned long long sums[3] = {0, 0, 0};
+  hip_check(hipMemcpyAsync(counts.data(), ix->sel_cnt.ptr, nq * 4, hipMemcpyDeviceToHost, stream), "D2H");
+  if (ix->fr_path)  // (no eligible row at all: no scan ran)
+    hip_check(hipMemcpyAsync(sums, ix->fr_stats.ptr, sizeof(sums), hipMemcpyDeviceToHost, stream), "D2H");
+  hip_check(hipStreamSynchronize(stream), "flat select search");
+  // a list that is short of min(k, eligible rows) or past the cap (more than 4096 rows tie around the k-th
+  // distance, or a selection gone wrong): the exhaustive recompute answers, never a wrong list
+  const uint32_t need = all ? eligible : k;
+  uint32_t redo = 0;
+  std::vector<uint32_t> vbits, rid(k);
+  std::vector<float> rd(k);
+  for (uint64_t q = 0; q < nq; ++q) {
+    if (counts[q] >= need && counts[q] <= cap) continue;
+    ++redo;
+    if (stream != ix->stream) hip_check(hipStreamSynchronize(ix->stream), "flat select search");
+    flat_exhaustive_query(ix, d_q + q * ix->dim, k, rid.data(), rd.data(), vbits);
+    hip_check(hipMemcpy(d_ids + q * k, rid.data(), k * 4, hipMemcpyHostToDevice), "H2D");
+    hip_check(hipMemcpy(d_dists + q * k, rd.data(), k * 4, hipMemcpyHostToDevice), "H2D");
+  }
+  scratch_release(ix, stream);
+  ix->sel_last[0] = full_passes;
+  ix->sel_last[1] = sums[0];
+  ix->sel_last[2] = redo;
+  return redo;
+}
+
+int alaya_index_flat_select_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t *d_ids,
+                                          float *d_dists, uint32_t *n_recomputed, void *stream) {
+  return guarded([&] {
+    if (!ix || (nq && (!d_queries || !d_ids || !d_dists))) throw ArgError("invalid arguments");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    const uint32_t redo = do_flat_select(ix, d_queries, nq, k, d_ids, d_dists, static_cast<hipStream_t>(stream));
+    if (n_recomputed) *n_recomputed = redo;
+  });
+}
+
+int alaya_index_flat_select_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t *ids, float *dists,
+                                   uint32_t *n_recomputed) {
+  // up to the flat search's own limit that search answers, unless the environment asks for the selection
+  if (k <= static_cast<uint32_t>(alaya_amd::flat_max_k()) && !flat_select_forced())
+    return alaya_index_flat_search(ix, queries, nq, k, ids, dists, n_recomputed);
+  return guarded([&] {
+    if (!ix || (nq && (!queries || !ids))) throw ArgError("invalid arguments");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    if (n_recomputed) *n_recomputed = 0;
+    if (k == 0 || k > alaya_amd::kSelectMaxK)  // (before the result buffers are sized by it)
+      throw ArgError("flat select search needs 1 <= k <= " + std::to_string(alaya_amd::kSelectMaxK));
+    if (nq == 0) return;
+    scratch_acquire(ix, ix->stream);  // the upload buffers below are the index's, shared with other launches
+    const float *d_q = stage_queries(ix, queries, nq, k, "H2D", /*dists=*/true, /*counters=*/false);
+    const uint32_t redo = do_flat_select(ix, d_q, nq, k, ix->id_buf.as<uint32_t>(), ix->dist_buf.as<float>(), ix->stream);
+    fetch_results(ix, nq, k, ids, dists, nullptr);
+    stream_sync(ix, "flat select search");
+    if (n_recomputed) *n_recomputed = redo;
+  });
+}
+
+int alaya_index_flat_select_last(const alaya_index *ix, uint64_t *out) {
+  return guarded([&] {
+    if (!ix || !out) throw ArgError("invalid arguments");
+    std::memcpy(out, ix->sel_last, sizeof(ix->sel_last));
   });
 }
 

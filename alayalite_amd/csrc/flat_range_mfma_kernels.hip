@@ -34,6 +34,7 @@
 #include <cfloat>
 
 #include "exact_scan_device.h"
+#include "flat_mfma_split.h"
 #include "flat_range_bound.h"
 
 namespace alaya_amd {
@@ -47,14 +48,10 @@ constexpr int TT = kRangeMfmaTT;
 constexpr int kTile = 32;
 constexpr int kBPitch = KS + 8;                // bf16 per LDS row: 144 bytes, 16-byte reads spread over the banks
 constexpr int kHalf = kTile * kBPitch;         // bf16 of one hi (or lo) unit
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split_bf16(float x, __bf16 &hi, __bf16 &lo) {
-  hi = static_cast<__bf16>(x);
-  lo = static_cast<__bf16>(x - static_cast<float>(hi));
-}
+using mfma_split::bf16x4;
+using mfma_split::bf16x8;
+using mfma_split::f32x16;
+using mfma_split::split_bf16;
 
 __device__ __forceinline__ uint32_t read_lane(uint32_t v, int l) {
   return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), __builtin_amdgcn_readfirstlane(l)));

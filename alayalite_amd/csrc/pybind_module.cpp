@@ -344,8 +344,9 @@ class PyIndexInterface : public LaunchControls {
     py::array_t<float> dists = out2d<float>(nq, topk);
     {
       py::gil_scoped_release nogil;
-      check(alaya_index_flat_search(ix_, static_cast<const float *>(q.data()), nq, topk, ids32.data(),
-                                    dists.mutable_data(), nullptr));
+      // (topk <= 224 is alaya_index_flat_search there; above, the selection search up to 2048)
+      check(alaya_index_flat_select_search(ix_, static_cast<const float *>(q.data()), nq, topk, ids32.data(),
+                                           dists.mutable_data(), nullptr));
     }
     return py::make_tuple(widen_ids(ids32, nq, topk, true), dists);
   }
@@ -1390,6 +1391,34 @@ class DeviceIndex : public LaunchControls {
     check(alaya_index_flat_search_device(ix_, dptr<const float>(q), nq, k, dptr<uint32_t>(ids), dptr<float>(dists),
                                          dptr<uint32_t>(flags), dptr<void>(stream)));
   }
+  // flat_search for k up to 2048 (alaya_index_flat_select_search): (ids, dists, queries recomputed)
+  py::tuple flat_select_search(F32Array q, uint32_t k) {
+    const uint64_t nq = q.shape(0);
+    py::array_t<uint32_t> ids = out2d<uint32_t>(nq, k);
+    py::array_t<float> d = out2d<float>(nq, k);
+    uint32_t redo = 0;
+    const float *qp = q.data();
+    uint32_t *ip = ids.mutable_data();
+    float *dp = d.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_flat_select_search(ix_, qp, nq, k, ip, dp, &redo));
+    }
+    return py::make_tuple(ids, d, redo);
+  }
+  // the same on device pointers; returns the queries recomputed (the call waits for its launches)
+  uint32_t flat_select_search_device(uintptr_t q, uint64_t nq, uint32_t k, uintptr_t ids, uintptr_t dists, uintptr_t stream) {
+    uint32_t redo = 0;
+    check(alaya_index_flat_select_search_device(ix_, dptr<const float>(q), nq, k, dptr<uint32_t>(ids), dptr<float>(dists),
+                                                &redo, dptr<void>(stream)));
+    return redo;
+  }
+  // of the last selection search: (histogram passes over all rows, pairs verified, queries recomputed)
+  py::tuple flat_select_last() const {
+    uint64_t o[3];
+    check(alaya_index_flat_select_last(ix_, o));
+    return py::make_tuple(o[0], o[1], o[2]);
+  }
   // the exact k nearest among the valid rows allow_words (uint32 [n_masks, ceil(n / 32)], utils.pack_allow)
   // allows: a scan of those rows (alaya_index_flat_search_filtered); mask_of_query as for filtered_search
   py::tuple flat_search_filtered(F32Array q, uint32_t k, U32Array allow_words, py::object mask_of_query) {
@@ -1678,6 +1707,9 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("spill_mark", &DeviceIndex::spill_mark)
       .def("flat_search", &DeviceIndex::flat_search, py::arg("queries"), py::arg("k"))
       .def("flat_search_device", &DeviceIndex::flat_search_device)
+      .def("flat_select_search", &DeviceIndex::flat_select_search, py::arg("queries"), py::arg("k"))
+      .def("flat_select_search_device", &DeviceIndex::flat_select_search_device)
+      .def("flat_select_last", &DeviceIndex::flat_select_last)
       .def("flat_search_filtered", &DeviceIndex::flat_search_filtered, py::arg("queries"), py::arg("k"),
            py::arg("allow_words"), py::arg("mask_of_query") = py::none())
       .def("flat_search_filtered_device", &DeviceIndex::flat_search_filtered_device)

@@ -147,7 +147,15 @@ class Index:
         """The exact top-k of each query over the rows the index holds (valid rows only, the index's
         metric in f32, ties by id): the flat MFMA search on the device rows -- the ground truth for
         the recall of ``batch_search`` at some ``ef_search``.  Returns (ids, distances); slots past the
-        valid rows hold (the id type's maximum, FLT_MAX).  1 <= topk <= 224, float32 data.
+        valid rows hold (the id type's maximum, FLT_MAX).  1 <= topk <= 2048, float32 data.
+
+        Up to 224 the flat search's register lists hold the answer.  From 225 to 2048 (without ``allow``)
+        a selection runs instead: histogram passes on the MFMA scan find, per query, a radius that admits
+        at least topk rows and few more, the exact range scan of ``exact_range_search`` returns those rows
+        ordered by (distance, id), and the first topk are kept -- the same ids and distance bits a longer
+        list would give.  A query with more than 4096 rows tied around its topk-th distance is recomputed
+        exhaustively.  ``topk`` above 2048 raises ``ValueError``; with ``allow`` the limit stays 224.
+        ``ALAYA_FLAT_SELECT=1`` in the environment sends every topk through the selection (a test hook).
 
         With ``allow`` (``filtered_search``'s masks: a bool array of shape (n,), n = ``get_data_num()``,
         or (G, n) with ``groups`` of shape (nq,), the mask of each query) the answer is the exact

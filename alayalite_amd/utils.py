@@ -51,7 +51,8 @@ _GT_METRICS = {"l2": 0, "ip": 1, "cos": 2}
 def calc_gt_device(data, query, topk, device=0, metric="l2", allow=None):
     """Exact top-k on the MI355X: the flat MFMA path (IndexType::FLAT has no implementation in the
     reference; this is its exact search, find_exact_gt in include/utils/evaluate.hpp:29-62: the f32
-    l2_sqr metric, ties by id).  Any dimension, 1 <= topk <= 224.  Returns (ids int32, distances
+    l2_sqr metric, ties by id).  Any dimension, 1 <= topk <= 2048 (above 224, and without ``allow``,
+    the histogram-select scan of ``Index.exact_search``; with ``allow`` 1 <= topk <= 224).  Returns (ids int32, distances
     float32).  Differs from calc_gt (float64 norms) only where two rows tie within f32 rounding.
     metric "ip" ranks by the f32 ip_sqr distance -(q.b); "cos" does the same on copies of both
     arrays normalised row by row as ``fit`` normalises them.
@@ -78,7 +79,7 @@ def calc_gt_device(data, query, topk, device=0, metric="l2", allow=None):
             raise ValueError(f"allow must have shape (n,), got {allow.shape}")
         ids, dists = ix.flat_search_filtered(query, topk, pack_allow(allow, data.shape[0]))
         return ids.astype(np.int32), dists
-    ids, dists, _ = ix.flat_search(query, topk)
+    ids, dists, _ = ix.flat_select_search(query, topk)  # topk <= 224: flat_search itself
     return ids.astype(np.int32), dists
 
 

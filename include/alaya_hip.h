@@ -633,6 +633,24 @@ int alaya_flat_range_mfma_plan(uint64_t n, uint64_t nq, uint32_t max_results, ui
  * lo = -inf, hi = +inf: no bound. */
 int alaya_flat_range_bound(int ip, int contraction, uint32_t k_acc, float b_max, const float *radii, const float *q_norm2,
                            uint64_t n, float *lo, float *hi);
+/* Exact k nearest rows for k up to 2048, by selection (csrc/flat_select_kernels.hip): the answer of
+ * alaya_index_flat_search -- every valid row, the index's metric in reference f32 order, ties by id, slots past
+ * the valid rows (0xffffffff, FLT_MAX) -- for 1 <= k <= 2048.  A span scan over a row sample and histogram
+ * passes over all rows on the MFMA units find, per query, an edge that at least k and few more approximate
+ * distances lie below; the smallest radius whose proven-inside threshold (csrc/flat_range_bound.h) reaches the
+ * edge goes to the MFMA range scan of alaya_index_flat_range_search with cap 4096, and its sorted lists are cut
+ * at k.  A query whose list is short of min(k, valid rows) or longer than 4096 (more than 4096 rows tie around
+ * its k-th distance) is recomputed exhaustively as alaya_index_flat_search does; *n_recomputed counts them.
+ * The host call answers k <= 224 through alaya_index_flat_search unless ALAYA_FLAT_SELECT=1 is set (a test
+ * hook); the device call always selects.  The device call runs on `stream` but is not asynchronous: the host
+ * reads per-query states between the passes, and the results are complete when it returns.  No mask.
+ * alaya_index_flat_select_last, of the last call: out[0] = histogram passes over all rows (at most 4), out[1] =
+ * pairs whose exact distance the range scan computed, out[2] = queries recomputed. */
+int alaya_index_flat_select_search(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, uint32_t *ids, float *dists,
+                                   uint32_t *n_recomputed);
+int alaya_index_flat_select_search_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k, uint32_t *d_ids,
+                                          float *d_dists, uint32_t *n_recomputed, void *stream);
+int alaya_index_flat_select_last(const alaya_index *ix, uint64_t *out);
 /* Tuning / introspection: LDS visited-table size (log2 slots, 6..16; 0 = automatic) and layout
  * (0 = automatic, 1 = compact 16-bit slots, 2 = 32-bit id slots, 3 = compact with probe distance
  * capped at 2, a test hook for the spill-on-long-probe path).  Results never depend on either:
