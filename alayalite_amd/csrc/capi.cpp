@@ -3123,7 +3123,7 @@ static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uin
       const FlatFilteredMfmaPlan mp = flat_filtered_mfma_plan(ix->n, nq_g, k, cus);
       plan.chunk_rows = mp.chunk_rows;
       plan.chunks = mp.chunks;
-      plan.tile = kFilteredMfmaQueries;
+      plan.tile = kMfmaScanQueries;
       plan.sub_queries = mp.sub_queries;
       plan.partial_bytes = mp.partial_bytes;
     } else {
@@ -3133,8 +3133,8 @@ static void do_flat_filtered(alaya_index *ix, const float *d_q, uint64_t nq, uin
     stats[0] += m;
     FlatFilteredMfmaParams mq{};
     if (mfma) {
-      const uint64_t nq_up = std::min<uint64_t>(plan.sub_queries, (nq_g + kFilteredMfmaQueries - 1) / kFilteredMfmaQueries * kFilteredMfmaQueries);
-      mq.qwidth = flat_filtered_mfma_width(ix->stride);
+      const uint64_t nq_up = std::min<uint64_t>(plan.sub_queries, (nq_g + kMfmaScanQueries - 1) / kMfmaScanQueries * kMfmaScanQueries);
+      mq.qwidth = mfma_scan_width(ix->stride);
       ix->fr_qpad.reserve(nq_up * mq.qwidth * 4);
       ix->fr_qmeta.reserve(nq_up * 8);
       ix->fr_wave_stats.reserve(plan.chunks * (nq_up / 32) * 8);
@@ -3283,7 +3283,7 @@ int alaya_flat_filtered_mfma_plan(uint64_t n, uint64_t nq, uint32_t k, uint32_t 
     const alaya_amd::FlatFilteredMfmaPlan r = alaya_amd::flat_filtered_mfma_plan(n, nq, k, cus);
     out[0] = r.chunk_rows;
     out[1] = r.chunks;
-    out[2] = alaya_amd::kFilteredMfmaQueries;
+    out[2] = alaya_amd::kMfmaScanQueries;
     out[3] = r.sub_queries;
     out[4] = r.partial_bytes;
   });
@@ -3360,7 +3360,7 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
       const FlatRangeMfmaPlan mp = flat_range_mfma_plan(ix->n, nq_g, max_results, cus);
       plan.chunk_rows = mp.chunk_rows;
       plan.chunks = mp.chunks;
-      plan.tile = kRangeMfmaQueries;
+      plan.tile = kMfmaScanQueries;
       plan.sub_queries = mp.sub_queries;
       plan.slots = mp.slots;
       plan.staging_bytes = mp.staging_bytes;
@@ -3375,8 +3375,8 @@ static void do_flat_range(alaya_index *ix, const float *d_q, uint64_t nq, const 
     stats[4] += m;
     FlatRangeMfmaParams mq{};
     if (mfma) {
-      const uint64_t nq_up = std::min<uint64_t>(plan.sub_queries, (nq_g + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries);
-      mq.qwidth = flat_range_mfma_width(ix->stride);
+      const uint64_t nq_up = std::min<uint64_t>(plan.sub_queries, (nq_g + kMfmaScanQueries - 1) / kMfmaScanQueries * kMfmaScanQueries);
+      mq.qwidth = mfma_scan_width(ix->stride);
       ix->fr_qpad.reserve(nq_up * mq.qwidth * 4);
       ix->fr_qmeta.reserve(nq_up * 16);
       ix->fr_wave_stats.reserve(plan.chunks * (nq_up / 32) * 12);
@@ -3554,7 +3554,7 @@ int alaya_flat_range_mfma_plan(uint64_t n, uint64_t nq, uint32_t max_results, ui
     const alaya_amd::FlatRangeMfmaPlan r = alaya_amd::flat_range_mfma_plan(n, nq, max_results, cus);
     out[0] = r.chunk_rows;
     out[1] = r.chunks;
-    out[2] = alaya_amd::kRangeMfmaQueries;
+    out[2] = alaya_amd::kMfmaScanQueries;
     out[3] = r.sub_queries;
     out[4] = r.slots;
     out[5] = r.staging_bytes;
@@ -3595,7 +3595,7 @@ static uint32_t do_flat_select(alaya_index *ix, const float *d_q, uint64_t nq, u
   const uint32_t cap = kFlatRangeMaxCap;
   ensure_norms(ix, stream);  // ahead of the scratch: it waits for the norms once
   scratch_acquire(ix, stream);
-  const uint64_t nq_up = (nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries;
+  const uint64_t nq_up = (nq + kMfmaScanQueries - 1) / kMfmaScanQueries * kMfmaScanQueries;
   const FlatRangeMfmaPlan plan = flat_range_mfma_plan(ix->n, nq, 1, cus);  // (a list of one: no floor on the chunk)
   FlatSelectParams p{};
   p.base = ix->base.as<float>();
@@ -3609,7 +3609,7 @@ static uint32_t do_flat_select(alaya_index *ix, const float *d_q, uint64_t nq, u
   p.chunk_rows = plan.chunk_rows;
   p.chunks = plan.chunks;
   p.nq = nq;
-  p.qwidth = flat_range_mfma_width(ix->stride);
+  p.qwidth = mfma_scan_width(ix->stride);
   ix->fr_qpad.reserve(nq_up * p.qwidth * 4);
   ix->fr_qmeta.reserve(nq_up * 16);
   ix->sel_win.reserve(nq_up * 12);

@@ -14,25 +14,15 @@
 
 namespace alaya_amd {
 
-constexpr uint32_t kFilteredMfmaQueries = 128;  // queries per workgroup: 4 waves x 32
-constexpr uint32_t kFilteredMfmaKS = 64;        // columns per slab
-constexpr uint32_t kFilteredMfmaTT = 4;         // 32-row tiles per super-tile
-constexpr uint32_t kFilteredMfmaTileRows = 32 * kFilteredMfmaTT;
-
 struct FlatFilteredMfmaPlan {
-  uint64_t chunk_rows;     // rows of the index per chunk, a multiple of kFilteredMfmaTileRows
+  uint64_t chunk_rows;     // rows of the index per chunk, a multiple of kMfmaScanTileRows (exact_scan_plan.h)
   uint64_t chunks;         // row chunks (0 when n is 0)
-  uint64_t sub_queries;    // queries per scan launch, a multiple of kFilteredMfmaQueries
+  uint64_t sub_queries;    // queries per scan launch, a multiple of kMfmaScanQueries
   uint64_t partial_bytes;  // chunks x min(nq, sub_queries) x k (distance, id) pairs
 };
 
 // Pure host arithmetic.  n: the index's rows (the scan walks all of them; the mask words pick the eligible).
 FlatFilteredMfmaPlan flat_filtered_mfma_plan(uint64_t n, uint64_t nq, uint32_t k, uint32_t cus);
-
-// columns the contraction accumulates over: the stride rounded up to whole slabs
-inline uint32_t flat_filtered_mfma_width(uint32_t stride) {
-  return (stride + kFilteredMfmaKS - 1) / kFilteredMfmaKS * kFilteredMfmaKS;
-}
 
 struct FlatFilteredMfmaParams {
   const float *base;        // n x stride f32 rows

@@ -2,15 +2,10 @@
 //
 //   1. prepare  one wave per query of the launch: the query zero padded to whole slabs and |q|^2; the first
 //               threshold is +inf (-inf for the padding queries past nq, which then never have a candidate).
-//   2. scan     flat_filtered_mfma_kernel<kIp>.  Streaming and contraction are flat_range_mfma_kernel's, restated
-//               here (DESIGN.md "Round 26" says why it is a copy): a workgroup of 4 waves owns 128 queries (32
-//               per wave) and one contiguous row chunk, the grid is XCD-aware, rows stream through a
-//               double-buffered LDS unit of 32 rows x KS = 64 columns split into bf16 hi + lo when staged, a
-//               super-tile of TT = 4 tiles keeps 32x32 accumulators (C[query][row]: row = lane & 31, query =
-//               (r & 3) + 8 (r >> 2) + 4 h for register r) across the slabs, ql.bh + qh.bl + qh.bh on
-//               v_mfma_f32_32x32x16_bf16, and d~ = (|q|^2 + |b|^2) - 2 C (L2) or -C (IP).
+//   2. scan     flat_filtered_mfma_kernel<kIp>: the work split and the streaming pass that flat_mfma_scan.h
+//               describes, with the tile's eligibility word mask AND validity AND below n.
 //
-//               The consumer is new.  One wave owns a (chunk, query) pair and its list of up to k entries, which
+//               The consumer.  One wave owns a (chunk, query) pair and its list of up to k entries, which
 //               lives in the partial buffers in global memory (32 queries x 224 x 8 bytes per wave do not fit
 //               the LDS): ascending by (distance, id), `cnt` entries long.  Lane q < 32 of the wave holds query
 //               q's count and worst entry (w, id), FLT_MAX and the all-ones id while the list is not full, and a
@@ -46,47 +41,17 @@
 #include <cfloat>
 
 #include "exact_scan_device.h"
+#include "flat_mfma_scan.h"
 #include "flat_range_bound.h"
 
 namespace alaya_amd {
 
 using exact_scan::query_row;
+using namespace mfma_scan;
 
 namespace {
 
-constexpr int KS = kFilteredMfmaKS;
-constexpr int TT = kFilteredMfmaTT;
-constexpr int kTile = 32;
-constexpr int kBPitch = KS + 8;                // bf16 per LDS row: 144 bytes, 16-byte reads spread over the banks
-constexpr int kHalf = kTile * kBPitch;         // bf16 of one hi (or lo) unit
 constexpr uint32_t kEmptyId = 0xffffffffu;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split_bf16(float x, __bf16 &hi, __bf16 &lo) {
-  hi = static_cast<__bf16>(x);
-  lo = static_cast<__bf16>(x - static_cast<float>(hi));
-}
-
-__device__ __forceinline__ uint32_t read_lane(uint32_t v, int l) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), __builtin_amdgcn_readfirstlane(l)));
-}
-__device__ __forceinline__ float read_lane_f(float v, int l) {
-  return __int_as_float(static_cast<int>(read_lane(static_cast<uint32_t>(__float_as_int(v)), l)));
-}
-
-// a value every lane holds alike, as a scalar
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-  const uint32_t a = __builtin_amdgcn_readfirstlane(static_cast<int>(v));
-  const uint32_t b = __builtin_amdgcn_readfirstlane(static_cast<int>(v >> 32));
-  return (static_cast<uint64_t>(b) << 32) | a;
-}
-
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // the list's stores done before any lane of the wave reads the list again
 __device__ __forceinline__ void list_fence() {
@@ -102,7 +67,7 @@ __device__ __forceinline__ bool ff_before(float da, uint32_t ia, float db, uint3
 }  // namespace
 
 __global__ void __launch_bounds__(256) flat_filtered_mfma_prepare_kernel(FlatFilteredMfmaParams p) {
-  const uint64_t nq_up = (p.nq + kFilteredMfmaQueries - 1) / kFilteredMfmaQueries * kFilteredMfmaQueries;
+  const uint64_t nq_up = mfma_scan_queries_up(p.nq);
   const uint64_t qi = static_cast<uint64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (qi >= nq_up) return;
   const int lane = __lane_id();
@@ -123,7 +88,7 @@ __global__ void __launch_bounds__(256) flat_filtered_mfma_prepare_kernel(FlatFil
 
 template <bool kIp>
 __global__ void __launch_bounds__(256) flat_filtered_mfma_kernel(FlatFilteredMfmaParams p) {
-  __shared__ __attribute__((aligned(16))) __bf16 tile[2 * 2 * kHalf];  // two buffers of (hi unit, lo unit)
+  __shared__ __attribute__((aligned(16))) __bf16 tile[kTileLds];
   __shared__ uint64_t pend[4][16];  // per wave: the candidate ballots of a tile's registers
   __shared__ float thr[4][32];      // per wave: its queries' thresholds
   const int lane = __lane_id();
@@ -131,8 +96,8 @@ __global__ void __launch_bounds__(256) flat_filtered_mfma_kernel(FlatFilteredMfm
   const int col = lane & 31, h = lane >> 5;
   const uint32_t g = lane >> 3, m = lane & 7;
   const uint32_t k = p.k;
-  const uint64_t nq_up = (p.nq + kFilteredMfmaQueries - 1) / kFilteredMfmaQueries * kFilteredMfmaQueries;
-  const uint32_t nqg = static_cast<uint32_t>(nq_up / kFilteredMfmaQueries);
+  const uint64_t nq_up = mfma_scan_queries_up(p.nq);
+  const uint32_t nqg = static_cast<uint32_t>(nq_up / kMfmaScanQueries);
   // XCD-aware block -> (query group, chunk): the query groups of one chunk share an XCD label
   const uint32_t b = blockIdx.x;
   const uint32_t qg = (b / 8) % nqg;
@@ -141,13 +106,13 @@ __global__ void __launch_bounds__(256) flat_filtered_mfma_kernel(FlatFilteredMfm
   const uint64_t r0 = chunk * p.chunk_rows;
   const uint64_t r1 = min(p.n, r0 + p.chunk_rows);  // r0 < r1: the chunks cover n
   const int nslab = static_cast<int>(p.qwidth / KS);
-  const uint64_t q0 = static_cast<uint64_t>(qg) * kFilteredMfmaQueries + wave * 32;  // the wave's first query
+  const uint64_t q0 = static_cast<uint64_t>(qg) * kMfmaScanQueries + wave * 32;  // the wave's first query
 
   // per accumulator register: its query's threshold (and |q|^2 for L2)
   float hi[16], qn[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const uint64_t qi = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const uint64_t qi = query_slot(q0, r, h);
     qn[r] = kIp ? 0.f : p.qmeta[qi];
     hi[r] = p.qmeta[nq_up + qi];
   }
@@ -167,9 +132,6 @@ __global__ void __launch_bounds__(256) flat_filtered_mfma_kernel(FlatFilteredMfm
 
   // cooperative unit load: 32 rows x KS columns, 256 threads, float4 each; rows past n read row n - 1 (their
   // eligibility bits are clear), columns past stride are zeroed when stored
-  constexpr int kVecPerRow = KS / 4;
-  constexpr int kPerThread = kTile * kVecPerRow / 256;
-  static_assert(kTile * kVecPerRow % 256 == 0, "whole float4s per thread");
   auto load_unit = [&](uint64_t row0, uint32_t c0, float4 (&reg)[kPerThread]) {
 #pragma unroll
     for (int v = 0; v < kPerThread; ++v) {
@@ -393,7 +355,7 @@ __global__ void __launch_bounds__(256) flat_filtered_mfma_kernel(FlatFilteredMfm
         uint32_t pending = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float d = kIp ? -c[t][r] : (qn[r] + bn[t]) - 2.0f * c[t][r];
+          const float d = approx_distance<kIp>(qn[r], bn[t], c[t][r]);
           const uint64_t cm = __ballot(eligible && !(d > hi[r]));  // NaN: a candidate
           if (cm == 0ull) continue;
           if (lane == 0) pend[wave][r] = cm;
@@ -405,14 +367,14 @@ __global__ void __launch_bounds__(256) flat_filtered_mfma_kernel(FlatFilteredMfm
             const int r = __builtin_ctz(pending);
             pending &= pending - 1;
             const uint64_t cm = uniform64(pend[wave][r]);
-            const int qs = (r & 3) + 8 * (r >> 2);
+            const int qs = query_slot(0, r, 0);
 #pragma unroll 1
             for (int hh = 0; hh < 2; ++hh) settle(qs + 4 * hh, sup + kTile * t, static_cast<uint32_t>(cm >> (32 * hh)));
           }
           wave_fence();
           if (dirty) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) hi[r] = thr[wave][(r & 3) + 8 * (r >> 2) + 4 * h];
+            for (int r = 0; r < 16; ++r) hi[r] = thr[wave][query_slot(0, r, h)];
             dirty = false;
           }
         }
@@ -438,93 +400,56 @@ __global__ void __launch_bounds__(256) flat_filtered_mfma_kernel(FlatFilteredMfm
   }
 }
 
-// One workgroup: the per-wave counters of a scan launch added to the call's two sums.
 __global__ void __launch_bounds__(256) flat_filtered_mfma_reduce_kernel(const uint32_t *wave_stats, uint64_t waves,
                                                                         unsigned long long *stats) {
-  __shared__ unsigned long long part[2][256];
-  unsigned long long s[2] = {0, 0};
-  for (uint64_t i = threadIdx.x; i < waves; i += 256)
-    for (int j = 0; j < 2; ++j) s[j] += wave_stats[i * 2 + j];
-  for (int j = 0; j < 2; ++j) part[j][threadIdx.x] = s[j];
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    unsigned long long t = 0;
-    for (int i = 0; i < 256; ++i) t += part[threadIdx.x][i];
-    stats[threadIdx.x] += t;
-  }
+  reduce_wave_stats<2>(wave_stats, waves, stats);
 }
 
-__global__ void flat_filtered_mfma_clear_kernel(unsigned long long *stats) {
-  if (threadIdx.x < 2) stats[threadIdx.x] = 0;
-}
+__global__ void flat_filtered_mfma_clear_kernel(unsigned long long *stats) { clear_stats<2>(stats); }
 
 // ---- host side -------------------------------------------------------------------------------------
 FlatFilteredMfmaPlan flat_filtered_mfma_plan(uint64_t n, uint64_t nq, uint32_t k, uint32_t cus) {
   FlatFilteredMfmaPlan r{};
   k = std::min<uint32_t>(std::max<uint32_t>(k, 1), kFilteredMaxK);
   cus = std::max<uint32_t>(cus, 1);
-  const uint64_t all = (std::max<uint64_t>(nq, 1) + kFilteredMfmaQueries - 1) / kFilteredMfmaQueries * kFilteredMfmaQueries;
+  const uint64_t all = mfma_scan_queries_up(std::max<uint64_t>(nq, 1));
   r.sub_queries = all;
   if (n == 0) return r;
-  const uint64_t tiles = (n + kFilteredMfmaTileRows - 1) / kFilteredMfmaTileRows;
   // The shortest chunk: 1024 rows, or 32 k rows where that is more.  Every chunk starts with an empty list: its
   // first k eligible rows are verified and inserted whatever their distance, and until the first threshold
   // reaches the registers (one tile after the list fills) so is every eligible row; after that a list verifies
   // about k ln(rows / k) more when rows come in random order.  At 32 k rows the fill is 1/32 of the chunk and
   // the whole verify share about (1 + ln 32) / 32 = 0.14 of the rows; 1024 is the same rule at k = 32, below
   // which the 32-row tile, not k, is what the first threshold waits for.  Reasoned, not measured.
-  const uint64_t min_rows = std::max<uint64_t>(1024, (32ull * k + kFilteredMfmaTileRows - 1) / kFilteredMfmaTileRows * kFilteredMfmaTileRows);
-  // rows per chunk for `groups` query groups in flight: no more chunks than fill the CUs twice over
-  const auto rows_for = [&](uint64_t groups, uint64_t most) {
-    const uint64_t max_chunks = std::max<uint64_t>(1, std::min<uint64_t>(most, 2ull * cus / groups));
-    return std::max(min_rows, kFilteredMfmaTileRows * ((tiles + max_chunks - 1) / max_chunks));
-  };
+  const uint64_t min_rows = std::max<uint64_t>(1024, (32ull * k + kMfmaScanTileRows - 1) / kMfmaScanTileRows * kMfmaScanTileRows);
   const uint64_t list_bytes = static_cast<uint64_t>(k) * 8;
-  // all the queries in one launch where their lists fit the cap, else half as many, down to one query group --
-  // whose chunks are then as few as fit (the cap holds one group of one chunk at any k)
-  uint64_t sub = all, rows = 0;
-  for (;;) {
-    rows = rows_for(sub / kFilteredMfmaQueries, tiles);
-    const uint64_t chunks = (n + rows - 1) / rows;
-    if (chunks * sub * list_bytes <= kFilteredPartialCap) break;
-    if (sub == kFilteredMfmaQueries) {
-      rows = rows_for(1, std::max<uint64_t>(1, kFilteredPartialCap / (sub * list_bytes)));
-      break;
-    }
-    sub = std::max<uint64_t>(kFilteredMfmaQueries, sub / 2 / kFilteredMfmaQueries * kFilteredMfmaQueries);
-  }
-  r.chunk_rows = rows;
-  r.chunks = (n + rows - 1) / rows;
-  r.sub_queries = sub;
-  r.partial_bytes = r.chunks * std::min<uint64_t>(std::max<uint64_t>(nq, 1), sub) * list_bytes;
+  const MfmaScanChunks c = mfma_scan_chunks(n, all, cus, min_rows, kFilteredPartialCap, [&](uint64_t) { return list_bytes; });
+  r.chunk_rows = c.rows;
+  r.chunks = (n + c.rows - 1) / c.rows;
+  r.sub_queries = c.sub;
+  r.partial_bytes = r.chunks * std::min<uint64_t>(std::max<uint64_t>(nq, 1), c.sub) * list_bytes;
   return r;
 }
 
 hipError_t launch_flat_filtered_mfma_prepare(const FlatFilteredMfmaParams &p, hipStream_t s) {
-  if (p.nq == 0 || p.qwidth == 0 || p.qwidth % kFilteredMfmaKS != 0 || p.qwidth < p.dim) return hipErrorInvalidValue;
-  const uint64_t nq_up = (p.nq + kFilteredMfmaQueries - 1) / kFilteredMfmaQueries * kFilteredMfmaQueries;
+  if (p.nq == 0 || p.qwidth == 0 || p.qwidth % kMfmaScanKS != 0 || p.qwidth < p.dim) return hipErrorInvalidValue;
+  const uint64_t nq_up = mfma_scan_queries_up(p.nq);
   hipLaunchKernelGGL(flat_filtered_mfma_prepare_kernel, dim3(static_cast<uint32_t>(nq_up / 4)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 
 hipError_t launch_flat_filtered_mfma_scan(const FlatFilteredMfmaParams &p, hipStream_t s) {
-  if (p.nq == 0 || p.n == 0 || p.n > 0xffffffffull || p.chunks == 0 || p.chunk_rows == 0 ||
-      p.chunk_rows % kFilteredMfmaTileRows != 0)
-    return hipErrorInvalidValue;
-  if (p.chunks * p.chunk_rows < p.n || (p.chunks - 1) * p.chunk_rows >= p.n) return hipErrorInvalidValue;
+  const uint32_t grid = mfma_scan_grid(p.nq, p.n, p.chunk_rows, p.chunks, p.dim, p.stride, p.qwidth);
+  if (grid == 0 || p.n > 0xffffffffull) return hipErrorInvalidValue;
   if (p.k == 0 || p.k > kFilteredMaxK) return hipErrorInvalidValue;
-  if (p.stride < 4 || p.stride % 4 != 0 || p.qwidth != flat_filtered_mfma_width(p.stride) || p.dim > p.stride)
-    return hipErrorInvalidValue;
-  const uint64_t nqg = (p.nq + kFilteredMfmaQueries - 1) / kFilteredMfmaQueries;
-  const uint64_t grid = 8 * nqg * ((p.chunks + 7) / 8);
-  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
   if (p.ip)
-    hipLaunchKernelGGL(flat_filtered_mfma_kernel<true>, dim3(static_cast<uint32_t>(grid)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(flat_filtered_mfma_kernel<true>, dim3(grid), dim3(256), 0, s, p);
   else
-    hipLaunchKernelGGL(flat_filtered_mfma_kernel<false>, dim3(static_cast<uint32_t>(grid)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(flat_filtered_mfma_kernel<false>, dim3(grid), dim3(256), 0, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(flat_filtered_mfma_reduce_kernel, dim3(1), dim3(256), 0, s, p.wave_stats, p.chunks * nqg * 4, p.stats);
+  hipLaunchKernelGGL(flat_filtered_mfma_reduce_kernel, dim3(1), dim3(256), 0, s, p.wave_stats,
+                     p.chunks * (mfma_scan_queries_up(p.nq) / 32), p.stats);
   return hipGetLastError();
 }
 

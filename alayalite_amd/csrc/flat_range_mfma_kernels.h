@@ -13,24 +13,16 @@
 
 namespace alaya_amd {
 
-constexpr uint32_t kRangeMfmaQueries = 128;  // queries per workgroup: 4 waves x 32
-constexpr uint32_t kRangeMfmaKS = 64;        // columns per slab
-constexpr uint32_t kRangeMfmaTT = 4;         // 32-row tiles per super-tile
-constexpr uint32_t kRangeMfmaTileRows = 32 * kRangeMfmaTT;
-
 struct FlatRangeMfmaPlan {
-  uint64_t chunk_rows;     // rows per chunk, a multiple of kRangeMfmaTileRows
+  uint64_t chunk_rows;     // rows per chunk, a multiple of kMfmaScanTileRows (exact_scan_plan.h)
   uint64_t chunks;         // row chunks (0 when n is 0)
-  uint64_t sub_queries;    // queries per scan launch, a multiple of kRangeMfmaQueries
+  uint64_t sub_queries;    // queries per scan launch, a multiple of kMfmaScanQueries
   uint64_t slots;          // stored hits per (chunk, query): min(cap, chunk_rows)
   uint64_t staging_bytes;  // chunks x min(nq rounded up, sub_queries) x (slots pairs + one count)
 };
 
 // Pure host arithmetic.  n: the index's rows (the scan walks all of them; the mask words pick the eligible).
 FlatRangeMfmaPlan flat_range_mfma_plan(uint64_t n, uint64_t nq, uint32_t cap, uint32_t cus);
-
-// columns the contraction accumulates over: the stride rounded up to whole slabs
-inline uint32_t flat_range_mfma_width(uint32_t stride) { return (stride + kRangeMfmaKS - 1) / kRangeMfmaKS * kRangeMfmaKS; }
 
 struct FlatRangeMfmaParams {
   const float *base;        // n x stride f32 rows

@@ -2,16 +2,10 @@
 //
 //   1. prepare  one wave per query of the launch: the query zero padded to whole slabs, |q|^2, and the two
 //               thresholds lo <= hi of flat_range_bound.h.
-//   2. scan     flat_range_mfma_kernel<kIp>.  A workgroup of 4 waves owns 128 queries (32 per wave) and one
-//               contiguous row chunk; the grid is XCD-aware as flat_scan_kernel's.  Rows stream through a
-//               double-buffered LDS unit of 32 rows x KS = 64 columns, split into bf16 hi + lo once when the
-//               unit is staged.  Per slab a wave splits its queries' slice into hi / lo A fragments (lane
-//               (col, h) holds query col, columns h KS/2 .. + KS/2 of the slab) and runs a super-tile of TT = 4
-//               tiles whose 32x32 accumulators (C[query][row]: row = lane & 31, query = (r & 3) + 8 (r >> 2) +
-//               4 h for register r) persist across the slabs: qh.bh + qh.bl + ql.bh, three
-//               v_mfma_f32_32x32x16_bf16 per 16 columns.  After the last slab d~ = (|q|^2 + |b|^2) - 2 C (L2)
-//               or -C (IP); per accumulator register two compares, the tile's eligibility bit and a ballot:
-//               no candidate bit set, next register.  Otherwise the register's two ballots go to a per-wave LDS
+//   2. scan     flat_range_mfma_kernel<kIp>: the work split and the streaming pass that flat_mfma_scan.h describes,
+//               with the tile's eligibility word mask AND validity AND below n.  The consumer: per accumulator
+//               register of a super-tile d~, two compares, the tile's eligibility bit and a ballot: no
+//               candidate bit set, next register.  Otherwise the register's two ballots go to a per-wave LDS
 //               list that is settled after the super-tile's compares, per query of the register: the pairs that
 //               need the exact distance -- the band bits, and every candidate bit while the query's count is
 //               below `slots` -- are computed 8 at a time, a group of 8 lanes per pair in exact_scan_device.h's
@@ -20,12 +14,8 @@
 //               of the wave holds query q's), nothing is atomic, no workgroup waits for another.
 //   3. reduce   the per-wave counters (pairs verified, band pairs, pairs proven) summed by one workgroup.
 //
-// KS = 64, TT = 4: a lane holds 64 accumulators, 32 VGPRs of A fragments, 32 of the next slab's f32 slice, 48
-// of thresholds and 8 of staging: 245 VGPRs + 64 AGPRs for L2, 221 + 64 for IP, no scratch, one wave per SIMD;
-// KS = 128 doubles the fragment and prefetch registers and would spill.  LDS reads: a wave reads 2 x 16 bytes per lane (bh, bl) per 3 MFMAs, 2 KiB per
-// 96 MFMA cycles; 4 waves, 85 bytes per cycle of the CU's 128, whatever TT -- each B fragment feeds one wave's
-// 3 MFMAs.  TT amortises what is per slab: the 8 float4 loads and the 32 hi/lo splits of the A slice, over
-// TT x 12 MFMAs (1536 cycles at TT = 4), and the barrier per unit stays one per 12 MFMAs.
+// Resources: beside the pass's registers a lane holds 48 VGPRs of thresholds: 245 VGPRs + 64 AGPRs for L2, 221 +
+// 64 for IP, no scratch, one wave per SIMD.
 #include "flat_range_mfma_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -34,45 +24,16 @@
 #include <cfloat>
 
 #include "exact_scan_device.h"
-#include "flat_mfma_split.h"
+#include "flat_mfma_scan.h"
 #include "flat_range_bound.h"
 
 namespace alaya_amd {
 
 using exact_scan::query_row;
-
-namespace {
-
-constexpr int KS = kRangeMfmaKS;
-constexpr int TT = kRangeMfmaTT;
-constexpr int kTile = 32;
-constexpr int kBPitch = KS + 8;                // bf16 per LDS row: 144 bytes, 16-byte reads spread over the banks
-constexpr int kHalf = kTile * kBPitch;         // bf16 of one hi (or lo) unit
-using mfma_split::bf16x4;
-using mfma_split::bf16x8;
-using mfma_split::f32x16;
-using mfma_split::split_bf16;
-
-__device__ __forceinline__ uint32_t read_lane(uint32_t v, int l) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), __builtin_amdgcn_readfirstlane(l)));
-}
-
-// a value every lane holds alike, as a scalar
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-  const uint32_t a = __builtin_amdgcn_readfirstlane(static_cast<int>(v));
-  const uint32_t b = __builtin_amdgcn_readfirstlane(static_cast<int>(v >> 32));
-  return (static_cast<uint64_t>(b) << 32) | a;
-}
-
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-}  // namespace
+using namespace mfma_scan;
 
 __global__ void __launch_bounds__(256) flat_range_mfma_prepare_kernel(FlatRangeMfmaParams p) {
-  const uint64_t nq_up = (p.nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries;
+  const uint64_t nq_up = mfma_scan_queries_up(p.nq);
   const uint64_t qi = static_cast<uint64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (qi >= nq_up) return;
   const int lane = __lane_id();
@@ -98,14 +59,14 @@ __global__ void __launch_bounds__(256) flat_range_mfma_prepare_kernel(FlatRangeM
 
 template <bool kIp>
 __global__ void __launch_bounds__(256) flat_range_mfma_kernel(FlatRangeMfmaParams p) {
-  __shared__ __attribute__((aligned(16))) __bf16 tile[2 * 2 * kHalf];  // two buffers of (hi unit, lo unit)
+  __shared__ __attribute__((aligned(16))) __bf16 tile[kTileLds];
   __shared__ uint64_t pend[4][TT * 16][2];  // per wave: the (candidate, proven) ballots of a super-tile's registers
   const int lane = __lane_id();
   const int wave = threadIdx.x >> 6;
   const int col = lane & 31, h = lane >> 5;
   const uint32_t g = lane >> 3, m = lane & 7;
-  const uint64_t nq_up = (p.nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries;
-  const uint32_t nqg = static_cast<uint32_t>(nq_up / kRangeMfmaQueries);
+  const uint64_t nq_up = mfma_scan_queries_up(p.nq);
+  const uint32_t nqg = static_cast<uint32_t>(nq_up / kMfmaScanQueries);
   // XCD-aware block -> (query group, chunk): the query groups of one chunk share an XCD label
   const uint32_t b = blockIdx.x;
   const uint32_t qg = (b / 8) % nqg;
@@ -114,13 +75,13 @@ __global__ void __launch_bounds__(256) flat_range_mfma_kernel(FlatRangeMfmaParam
   const uint64_t r0 = chunk * p.chunk_rows;
   const uint64_t r1 = min(p.n, r0 + p.chunk_rows);  // r0 < r1: the chunks cover n
   const int nslab = static_cast<int>(p.qwidth / KS);
-  const uint64_t q0 = static_cast<uint64_t>(qg) * kRangeMfmaQueries + wave * 32;  // the wave's first query
+  const uint64_t q0 = static_cast<uint64_t>(qg) * kMfmaScanQueries + wave * 32;  // the wave's first query
 
   // per accumulator register: the thresholds of its query (and |q|^2 for L2)
   float lo[16], hi[16], qn[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const uint64_t qi = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const uint64_t qi = query_slot(q0, r, h);
     qn[r] = kIp ? 0.f : p.qmeta[qi];
     lo[r] = p.qmeta[nq_up + qi];
     hi[r] = p.qmeta[2 * nq_up + qi];
@@ -140,9 +101,6 @@ __global__ void __launch_bounds__(256) flat_range_mfma_kernel(FlatRangeMfmaParam
 
   // cooperative unit load: 32 rows x KS columns, 256 threads, float4 each; rows past n read row n - 1 (their
   // eligibility bits are clear), columns past stride are zeroed when stored
-  constexpr int kVecPerRow = KS / 4;
-  constexpr int kPerThread = kTile * kVecPerRow / 256;
-  static_assert(kTile * kVecPerRow % 256 == 0, "whole float4s per thread");
   auto load_unit = [&](uint64_t row0, uint32_t c0, float4 (&reg)[kPerThread]) {
 #pragma unroll
     for (int v = 0; v < kPerThread; ++v) {
@@ -183,7 +141,7 @@ __global__ void __launch_bounds__(256) flat_range_mfma_kernel(FlatRangeMfmaParam
     st_proven += proven;
     cnt += proven;  // (proven > 0 only past `slots`: nothing more is stored, the order no longer matters)
     if (need != 0) {
-      const float rad = __int_as_float(static_cast<int>(read_lane(static_cast<uint32_t>(__float_as_int(radv)), qs)));
+      const float rad = read_lane_f(radv, qs);
       const float *q = p.qpad + qi * p.qwidth;
       const uint64_t part = (chunk * p.nq + qi) * p.slots;
       while (need != 0) {
@@ -307,7 +265,7 @@ __global__ void __launch_bounds__(256) flat_range_mfma_kernel(FlatRangeMfmaParam
         const bool eligible = (el[t] >> col) & 1u;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float d = kIp ? -c[t][r] : (qn[r] + bn[t]) - 2.0f * c[t][r];
+          const float d = approx_distance<kIp>(qn[r], bn[t], c[t][r]);
           const bool cand = eligible && !(d > hi[r]);  // NaN: the band
           const uint64_t cm = __ballot(cand);
           if (cm == 0ull) continue;
@@ -327,7 +285,7 @@ __global__ void __launch_bounds__(256) flat_range_mfma_kernel(FlatRangeMfmaParam
         pending &= pending - 1ull;
         const uint64_t cm = uniform64(pend[wave][idx][0]), sm = uniform64(pend[wave][idx][1]);
         const int t = idx >> 4, r = idx & 15;
-        const int qs = (r & 3) + 8 * (r >> 2);
+        const int qs = query_slot(0, r, 0);
 #pragma unroll 1
         for (int hh = 0; hh < 2; ++hh)
           settle(qs + 4 * hh, sup + kTile * t, static_cast<uint32_t>(cm >> (32 * hh)), static_cast<uint32_t>(sm >> (32 * hh)));
@@ -345,89 +303,52 @@ __global__ void __launch_bounds__(256) flat_range_mfma_kernel(FlatRangeMfmaParam
   }
 }
 
-// One workgroup: the per-wave counters of a scan launch added to the call's three sums.
 __global__ void __launch_bounds__(256) flat_range_mfma_reduce_kernel(const uint32_t *wave_stats, uint64_t waves,
                                                                      unsigned long long *stats) {
-  __shared__ unsigned long long part[3][256];
-  unsigned long long s[3] = {0, 0, 0};
-  for (uint64_t i = threadIdx.x; i < waves; i += 256)
-    for (int j = 0; j < 3; ++j) s[j] += wave_stats[i * 3 + j];
-  for (int j = 0; j < 3; ++j) part[j][threadIdx.x] = s[j];
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    unsigned long long t = 0;
-    for (int i = 0; i < 256; ++i) t += part[threadIdx.x][i];
-    stats[threadIdx.x] += t;
-  }
+  reduce_wave_stats<3>(wave_stats, waves, stats);
 }
 
-__global__ void flat_range_mfma_clear_kernel(unsigned long long *stats) {
-  if (threadIdx.x < 3) stats[threadIdx.x] = 0;
-}
+__global__ void flat_range_mfma_clear_kernel(unsigned long long *stats) { clear_stats<3>(stats); }
 
 // ---- host side -------------------------------------------------------------------------------------
 FlatRangeMfmaPlan flat_range_mfma_plan(uint64_t n, uint64_t nq, uint32_t cap, uint32_t cus) {
   FlatRangeMfmaPlan r{};
   cap = std::min<uint32_t>(std::max<uint32_t>(cap, 1), kFlatRangeMaxCap);
   cus = std::max<uint32_t>(cus, 1);
-  const uint64_t all = (std::max<uint64_t>(nq, 1) + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries;
+  const uint64_t all = mfma_scan_queries_up(std::max<uint64_t>(nq, 1));
   r.sub_queries = all;
   if (n == 0) return r;
-  const uint64_t tiles = (n + kRangeMfmaTileRows - 1) / kRangeMfmaTileRows;
   // a chunk is no shorter than twice its list: of a chunk full of hits at least half are counted without a distance
-  const uint64_t min_rows = (2ull * cap + kRangeMfmaTileRows - 1) / kRangeMfmaTileRows * kRangeMfmaTileRows;
-  // rows per chunk for `groups` query groups in flight: no more chunks than fill the CUs twice over
-  const auto rows_for = [&](uint64_t groups, uint64_t most) {
-    const uint64_t max_chunks = std::max<uint64_t>(1, std::min<uint64_t>(most, 2ull * cus / groups));
-    return std::max(min_rows, kRangeMfmaTileRows * ((tiles + max_chunks - 1) / max_chunks));
-  };
+  const uint64_t min_rows = (2ull * cap + kMfmaScanTileRows - 1) / kMfmaScanTileRows * kMfmaScanTileRows;
   const auto pair_bytes = [&](uint64_t rows) { return std::min<uint64_t>(cap, rows) * 8 + 4; };
-  // all the queries in one launch where their lists fit the staging cap, else half as many, down to one
-  // query group -- whose chunks are then as few as fit (the cap holds one group of one chunk at any list)
-  uint64_t sub = all, rows = 0;
-  for (;;) {
-    rows = rows_for(sub / kRangeMfmaQueries, tiles);
-    const uint64_t chunks = (n + rows - 1) / rows;
-    if (chunks * sub * pair_bytes(rows) <= kFlatRangeStagingCap) break;
-    if (sub == kRangeMfmaQueries) {
-      const uint64_t most = std::max<uint64_t>(1, kFlatRangeStagingCap / (sub * (static_cast<uint64_t>(cap) * 8 + 4)));
-      rows = rows_for(1, most);
-      break;
-    }
-    sub = std::max<uint64_t>(kRangeMfmaQueries, sub / 2 / kRangeMfmaQueries * kRangeMfmaQueries);
-  }
-  r.chunk_rows = rows;
-  r.chunks = (n + rows - 1) / rows;
-  r.sub_queries = sub;
-  r.slots = std::min<uint64_t>(cap, rows);
-  r.staging_bytes = r.chunks * std::min(all, sub) * pair_bytes(rows);
+  const MfmaScanChunks c = mfma_scan_chunks(n, all, cus, min_rows, kFlatRangeStagingCap, pair_bytes);
+  r.chunk_rows = c.rows;
+  r.chunks = (n + c.rows - 1) / c.rows;
+  r.sub_queries = c.sub;
+  r.slots = std::min<uint64_t>(cap, c.rows);
+  r.staging_bytes = r.chunks * std::min(all, c.sub) * pair_bytes(c.rows);
   return r;
 }
 
 hipError_t launch_flat_range_mfma_prepare(const FlatRangeMfmaParams &p, hipStream_t s) {
-  if (p.nq == 0 || p.qwidth == 0 || p.qwidth % kRangeMfmaKS != 0 || p.qwidth < p.dim) return hipErrorInvalidValue;
-  const uint64_t nq_up = (p.nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries;
+  if (p.nq == 0 || p.qwidth == 0 || p.qwidth % kMfmaScanKS != 0 || p.qwidth < p.dim) return hipErrorInvalidValue;
+  const uint64_t nq_up = mfma_scan_queries_up(p.nq);
   hipLaunchKernelGGL(flat_range_mfma_prepare_kernel, dim3(static_cast<uint32_t>(nq_up / 4)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 
 hipError_t launch_flat_range_mfma_scan(const FlatRangeMfmaParams &p, hipStream_t s) {
-  if (p.nq == 0 || p.n == 0 || p.chunks == 0 || p.chunk_rows == 0 || p.chunk_rows % kRangeMfmaTileRows != 0)
-    return hipErrorInvalidValue;
-  if (p.chunks * p.chunk_rows < p.n || (p.chunks - 1) * p.chunk_rows >= p.n) return hipErrorInvalidValue;
+  const uint32_t grid = mfma_scan_grid(p.nq, p.n, p.chunk_rows, p.chunks, p.dim, p.stride, p.qwidth);
+  if (grid == 0) return hipErrorInvalidValue;
   if (p.cap == 0 || p.cap > kFlatRangeMaxCap || p.slots == 0 || p.slots > p.cap) return hipErrorInvalidValue;
-  if (p.stride < 4 || p.stride % 4 != 0 || p.qwidth != flat_range_mfma_width(p.stride) || p.dim > p.stride)
-    return hipErrorInvalidValue;
-  const uint64_t nqg = (p.nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries;
-  const uint64_t grid = 8 * nqg * ((p.chunks + 7) / 8);
-  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
   if (p.ip)
-    hipLaunchKernelGGL(flat_range_mfma_kernel<true>, dim3(static_cast<uint32_t>(grid)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(flat_range_mfma_kernel<true>, dim3(grid), dim3(256), 0, s, p);
   else
-    hipLaunchKernelGGL(flat_range_mfma_kernel<false>, dim3(static_cast<uint32_t>(grid)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(flat_range_mfma_kernel<false>, dim3(grid), dim3(256), 0, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(flat_range_mfma_reduce_kernel, dim3(1), dim3(256), 0, s, p.wave_stats, p.chunks * nqg * 4, p.stats);
+  hipLaunchKernelGGL(flat_range_mfma_reduce_kernel, dim3(1), dim3(256), 0, s, p.wave_stats,
+                     p.chunks * (mfma_scan_queries_up(p.nq) / 32), p.stats);
   return hipGetLastError();
 }
 

@@ -18,7 +18,7 @@ constexpr uint32_t kSelectPitch = kSelectBins + 1;  // counters per query: the b
 constexpr uint32_t kSelectMaxK = kFlatRangeMaxCap / 2;  // 2048: the threshold bin and ties keep room under the cap
 constexpr uint32_t kSelectMaxPasses = 4;            // full histogram passes of one call, at most
 // LDS of one histogram workgroup beside the 18 KB of tile buffers: 128 histograms and the 128 windows
-constexpr size_t kSelectHistLds = size_t(kRangeMfmaQueries) * kSelectPitch * 4 + size_t(kRangeMfmaQueries) * 3 * 4;
+constexpr size_t kSelectHistLds = size_t(kMfmaScanQueries) * kSelectPitch * 4 + size_t(kMfmaScanQueries) * 3 * 4;
 
 // Query states (FlatSelectParams::done)
 constexpr uint32_t kSelectRunning = 0, kSelectDone = 1, kSelectFallback = 2;

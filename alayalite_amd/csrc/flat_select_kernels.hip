@@ -1,12 +1,8 @@
 // Exact k-NN for k above the register-list limit: a histogram-select scan on the MFMA units.
 //
-//   scan    flat_select_hist_kernel<kIp>.  The work split and the data movement are flat_range_mfma_kernel's: a
-//           workgroup of 4 waves owns 128 queries (32 per wave) and one contiguous row chunk on the XCD-aware
-//           grid; rows stream through a double-buffered LDS unit of 32 rows x 64 columns, split into bf16 hi + lo
-//           when staged; per slab a wave splits its query slice into hi / lo A fragments; a super-tile of 4 tiles
-//           keeps its 32x32 f32 accumulators across the slabs, qh.bh + qh.bl + ql.bh per 16 columns.  After the
-//           last slab d~ = (|q|^2 + |b|^2) - 2 C (L2) or -C (IP), in the same operation order, so a pair's d~ has
-//           the bits the range scan will compare.  The epilogue is the new part:
+//   scan    flat_select_hist_kernel<kIp>: the work split and the streaming pass that flat_mfma_scan.h describes,
+//           with the eligibility word validity AND below n, and d~ in the same operation order, so a pair's d~
+//           has the bits the range scan will compare.  The epilogue:
 //             histogram mode  each query of the workgroup has a window [lo, hi) and an inverse bin width in LDS
 //                             and a histogram of 256 bins + a `below` counter there (128 x 257 x 4 B = 128.5 KB
 //                             beside the 18 KB of tile buffers: one workgroup per CU, which the scan runs at
@@ -37,23 +33,15 @@
 #include <algorithm>
 #include <cfloat>
 
-#include "flat_mfma_split.h"
+#include "flat_mfma_scan.h"
 #include "flat_range_bound.h"
 
 namespace alaya_amd {
 
 namespace {
 
-using mfma_split::bf16x4;
-using mfma_split::bf16x8;
-using mfma_split::f32x16;
-using mfma_split::split_bf16;
+using namespace mfma_scan;
 
-constexpr int KS = kRangeMfmaKS;
-constexpr int TT = kRangeMfmaTT;
-constexpr int kTile = 32;
-constexpr int kBPitch = KS + 8;         // bf16 per LDS row: 144 bytes, 16-byte reads spread over the banks
-constexpr int kHalf = kTile * kBPitch;  // bf16 of one hi (or lo) unit
 constexpr int kBins = kSelectBins;
 constexpr int kPitch = kSelectPitch;
 
@@ -90,15 +78,15 @@ __device__ __forceinline__ float window_inv(float lo, float hi) { return static_
 
 template <bool kIp>
 __global__ void __launch_bounds__(256) flat_select_hist_kernel(FlatSelectParams p) {
-  __shared__ __attribute__((aligned(16))) __bf16 tile[2 * 2 * kHalf];  // two buffers of (hi unit, lo unit)
+  __shared__ __attribute__((aligned(16))) __bf16 tile[kTileLds];
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // histogram mode: 128 x 257 counters, 3 x 128 window floats
   uint32_t *hist = reinterpret_cast<uint32_t *>(smem);
-  float *win = reinterpret_cast<float *>(smem + sizeof(uint32_t) * kRangeMfmaQueries * kPitch);
+  float *win = reinterpret_cast<float *>(smem + sizeof(uint32_t) * kMfmaScanQueries * kPitch);
   const int lane = __lane_id();
   const int wave = threadIdx.x >> 6;
   const int col = lane & 31, h = lane >> 5;
-  const uint64_t nq_up = (p.nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries;
-  const uint32_t nqg = static_cast<uint32_t>(nq_up / kRangeMfmaQueries);
+  const uint64_t nq_up = mfma_scan_queries_up(p.nq);
+  const uint32_t nqg = static_cast<uint32_t>(nq_up / kMfmaScanQueries);
   // XCD-aware block -> (query group, chunk): the query groups of one chunk share an XCD label
   const uint32_t b = blockIdx.x;
   const uint32_t qg = (b / 8) % nqg;
@@ -108,20 +96,20 @@ __global__ void __launch_bounds__(256) flat_select_hist_kernel(FlatSelectParams 
   const uint64_t r1 = min(p.n, r0 + p.chunk_rows);  // r0 < r1: the chunks cover n
   const uint64_t sup_rows = static_cast<uint64_t>(kTile * TT) * p.sup_step;
   const int nslab = static_cast<int>(p.qwidth / KS);
-  const uint64_t qg0 = static_cast<uint64_t>(qg) * kRangeMfmaQueries;
+  const uint64_t qg0 = static_cast<uint64_t>(qg) * kMfmaScanQueries;
   const uint64_t q0 = qg0 + wave * 32;  // the wave's first query
   const bool span = p.span != 0;        // uniform over the launch
 
   if (!span) {
-    for (int i = threadIdx.x; i < static_cast<int>(kRangeMfmaQueries) * kPitch; i += 256) hist[i] = 0;
-    for (int i = threadIdx.x; i < static_cast<int>(kRangeMfmaQueries) * 3; i += 256)
-      win[i] = p.win[static_cast<uint64_t>(i / kRangeMfmaQueries) * nq_up + qg0 + i % kRangeMfmaQueries];
+    for (int i = threadIdx.x; i < static_cast<int>(kMfmaScanQueries) * kPitch; i += 256) hist[i] = 0;
+    for (int i = threadIdx.x; i < static_cast<int>(kMfmaScanQueries) * 3; i += 256)
+      win[i] = p.win[static_cast<uint64_t>(i / kMfmaScanQueries) * nq_up + qg0 + i % kMfmaScanQueries];
   }
   // per accumulator register: |q|^2 of its query (L2), and the span mode's running min / max
   float qn[16], mn[16], mx[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    qn[r] = kIp ? 0.f : p.qmeta[q0 + (r & 3) + 8 * (r >> 2) + 4 * h];
+    qn[r] = kIp ? 0.f : p.qmeta[query_slot(q0, r, h)];
     mn[r] = INFINITY;
     mx[r] = -INFINITY;
   }
@@ -136,9 +124,6 @@ __global__ void __launch_bounds__(256) flat_select_hist_kernel(FlatSelectParams 
 
   // cooperative unit load: 32 rows x KS columns, 256 threads, float4 each; rows past n read row n - 1 (their
   // eligibility bits are clear), columns past stride are zeroed when stored
-  constexpr int kVecPerRow = KS / 4;
-  constexpr int kPerThread = kTile * kVecPerRow / 256;
-  static_assert(kTile * kVecPerRow % 256 == 0, "whole float4s per thread");
   auto load_unit = [&](uint64_t row0, uint32_t c0, float4 (&reg)[kPerThread]) {
 #pragma unroll
     for (int v = 0; v < kPerThread; ++v) {
@@ -253,13 +238,13 @@ __global__ void __launch_bounds__(256) flat_select_hist_kernel(FlatSelectParams 
         const bool eligible = (el[t] >> col) & 1u;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float d = kIp ? -c[t][r] : (qn[r] + bn[t]) - 2.0f * c[t][r];
+          const float d = approx_distance<kIp>(qn[r], bn[t], c[t][r]);
           if (span) {
             mn[r] = fminf(mn[r], eligible ? d : INFINITY);
             mx[r] = fmaxf(mx[r], eligible ? d : -INFINITY);
           } else if (eligible) {
-            const int qs = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float wl = win[qs], wh = win[kRangeMfmaQueries + qs], iv = win[2 * kRangeMfmaQueries + qs];
+            const int qs = query_slot(wave * 32, r, h);
+            const float wl = win[qs], wh = win[kMfmaScanQueries + qs], iv = win[2 * kMfmaScanQueries + qs];
             if (d < wl)
               atomicAdd(&hist[qs * kPitch + kBins], 1u);
             else if (d < wh)
@@ -278,7 +263,7 @@ __global__ void __launch_bounds__(256) flat_select_hist_kernel(FlatSelectParams 
         z = fmaxf(z, __shfl_xor(z, x));
       }
       if (col == 0 && a <= z) {  // (an empty or all-NaN register: nothing)
-        const uint64_t qi = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const uint64_t qi = query_slot(q0, r, h);
         atomicMin(&p.span_keys[qi], float_key(a));
         atomicMax(&p.span_keys[nq_up + qi], float_key(z));
       }
@@ -286,7 +271,7 @@ __global__ void __launch_bounds__(256) flat_select_hist_kernel(FlatSelectParams 
     if (qg == 0 && threadIdx.x == 0 && met != 0) atomicAdd(p.eligible, met);
   } else {
     __syncthreads();
-    for (int i = threadIdx.x; i < static_cast<int>(kRangeMfmaQueries) * kPitch; i += 256) {
+    for (int i = threadIdx.x; i < static_cast<int>(kMfmaScanQueries) * kPitch; i += 256) {
       const uint32_t v = hist[i];
       if (v != 0) atomicAdd(&p.hist[qg0 * kPitch + i], v);
     }
@@ -408,7 +393,7 @@ __global__ void flat_select_cut_kernel(const uint32_t *counts, const uint32_t *i
 
 // ---- host side -------------------------------------------------------------------------------------
 namespace {
-uint64_t select_nq_up(const FlatSelectParams &p) { return (p.nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries * kRangeMfmaQueries; }
+uint64_t select_nq_up(const FlatSelectParams &p) { return mfma_scan_queries_up(p.nq); }
 uint32_t per_query_grid(uint64_t nq_up) { return static_cast<uint32_t>((nq_up + 255) / 256); }
 bool per_query_ok(const FlatSelectParams &p) { return p.nq != 0 && p.nq <= 0x7fffffffull; }
 }  // namespace
@@ -421,20 +406,14 @@ hipError_t launch_flat_select_init(const FlatSelectParams &p, hipStream_t s) {
 }
 
 hipError_t launch_flat_select_scan(const FlatSelectParams &p, hipStream_t s) {
-  if (p.nq == 0 || p.n == 0 || p.chunks == 0 || p.chunk_rows == 0 || p.chunk_rows % kRangeMfmaTileRows != 0)
-    return hipErrorInvalidValue;
-  if (p.chunks * p.chunk_rows < p.n || (p.chunks - 1) * p.chunk_rows >= p.n) return hipErrorInvalidValue;
+  const uint32_t grid = mfma_scan_grid(p.nq, p.n, p.chunk_rows, p.chunks, p.dim, p.stride, p.qwidth);
+  if (grid == 0) return hipErrorInvalidValue;
   if (p.sup_step == 0 || p.sup_step > 0xffffu) return hipErrorInvalidValue;
-  if (p.stride < 4 || p.stride % 4 != 0 || p.qwidth != flat_range_mfma_width(p.stride) || p.dim > p.stride)
-    return hipErrorInvalidValue;
-  const uint64_t nqg = (p.nq + kRangeMfmaQueries - 1) / kRangeMfmaQueries;
-  const uint64_t grid = 8 * nqg * ((p.chunks + 7) / 8);
-  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
   const size_t lds = p.span ? 0 : kSelectHistLds;
   if (p.ip)
-    hipLaunchKernelGGL(flat_select_hist_kernel<true>, dim3(static_cast<uint32_t>(grid)), dim3(256), lds, s, p);
+    hipLaunchKernelGGL(flat_select_hist_kernel<true>, dim3(grid), dim3(256), lds, s, p);
   else
-    hipLaunchKernelGGL(flat_select_hist_kernel<false>, dim3(static_cast<uint32_t>(grid)), dim3(256), lds, s, p);
+    hipLaunchKernelGGL(flat_select_hist_kernel<false>, dim3(grid), dim3(256), lds, s, p);
   return hipGetLastError();
 }
 
