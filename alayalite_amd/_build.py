@@ -28,8 +28,8 @@ ARCH = os.environ.get("ALAYA_OFFLOAD_ARCH", "gfx950")
 LIB = os.path.join(HERE, "libalaya_hip.so")
 EXT = os.path.join(HERE, "_alayalitepy" + sysconfig.get_config_var("EXT_SUFFIX"))
 
-LIB_SOURCES = ["search_kernels.hip", "build_kernels.hip", "extend_kernels.hip", "flat_kernels.hip", "flat_filtered_kernels.hip", "flat_range_kernels.hip", "flat_range_mfma_kernels.hip", "flat_filtered_mfma_kernels.hip", "flat_select_kernels.hip", "capi.cpp", "hnsw_build.cpp", "graph_update.cpp"]
-LIB_HEADERS = ["search_kernels.h", "search_variants.h", "search_device.h", "screen_bound.h", "build_kernels.h", "extend_kernels.h", "flat_kernels.h", "flat_filtered_kernels.h", "flat_range_kernels.h", "flat_range_mfma_kernels.h", "flat_filtered_mfma_kernels.h", "flat_select_kernels.h", "flat_mfma_scan.h", "flat_range_bound.h", "exact_scan_plan.h", "exact_scan_device.h", "flat_bound.h", "hnsw_build.h", "host_distance.h", "graph_update.h"]
+LIB_SOURCES = ["search_kernels.hip", "build_kernels.hip", "extend_kernels.hip", "flat_kernels.hip", "flat_filtered_kernels.hip", "flat_range_kernels.hip", "flat_range_mfma_kernels.hip", "flat_filtered_mfma_kernels.hip", "flat_select_kernels.hip", "flat_lists_kernels.hip", "capi.cpp", "hnsw_build.cpp", "graph_update.cpp"]
+LIB_HEADERS = ["search_kernels.h", "search_variants.h", "search_device.h", "screen_bound.h", "build_kernels.h", "extend_kernels.h", "flat_kernels.h", "flat_filtered_kernels.h", "flat_range_kernels.h", "flat_range_mfma_kernels.h", "flat_filtered_mfma_kernels.h", "flat_select_kernels.h", "flat_lists_kernels.h", "flat_mfma_scan.h", "flat_range_bound.h", "exact_scan_plan.h", "exact_scan_device.h", "flat_bound.h", "hnsw_build.h", "host_distance.h", "graph_update.h"]
 EXT_SOURCES = ["pybind_module.cpp"]
 
 
@@ -93,7 +93,8 @@ def build(force: bool = False, verbose: bool = False) -> tuple[str, str]:
             # against 201) at the same 64 AGPRs, no scratch and one wave per SIMD either way (DESIGN.md "Round
             # 24").  The host pass of the same line does not know the feature and says that it ignores it.  Older
             # translation units keep the flags their generated code was recorded with.
-            if src in ("flat_range_mfma_kernels.hip", "flat_filtered_mfma_kernels.hip", "flat_select_kernels.hip"):
+            if src in ("flat_range_mfma_kernels.hip", "flat_filtered_mfma_kernels.hip", "flat_select_kernels.hip",
+                       "flat_lists_kernels.hip"):
                 flags[1:1] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
             if verbose:
                 print(" ".join(flags), flush=True)

@@ -22,6 +22,7 @@
 #include "flat_bound.h"
 #include "flat_filtered_kernels.h"
 #include "flat_filtered_mfma_kernels.h"
+#include "flat_lists_kernels.h"
 #include "flat_range_kernels.h"
 #include "flat_range_mfma_kernels.h"
 #include "flat_range_bound.h"
@@ -155,6 +156,11 @@ struct alaya_index {
   int ff_path = 0;            // the last call's path: 0 the f32 scan, 1 the MFMA scan (for any of its masks)
   uint64_t ff_pairs = 0;      // eligible rows x queries, summed over the last call's masks, when ff_path is 1
   hipEvent_t ff_done = nullptr;  // recorded after the last MFMA call's launches: what alaya_index_flat_filtered_path waits for
+  // exact k-NN over candidate lists (alaya_index_flat_search_lists*, flat_lists_kernels.hip): the host entry's
+  // lims and ids, the queries' first pieces and the piece table of one launch; the partial lists are the
+  // filtered scan's buffers
+  DevBuf fl_lims, fl_ids, fl_first, fl_table;
+  uint64_t fl_last[4] = {0, 0, 0, 0};  // alaya_index_flat_lists_last
   // exact range search (alaya_index_flat_range_search*): it shares the filtered scan's id list, block sums,
   // count, query order and partial-list buffers; its own are the per-(chunk, query) hit counts and the
   // all-ones words that stand for "no mask" on an index without a validity bitmap
@@ -3301,6 +3307,124 @@ int alaya_flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k, uint32
     out[2] = r.tile;
     out[3] = r.sub_queries;
     out[4] = r.partial_bytes;
+  });
+}
+
+// ---- exact k-NN over per-query candidate lists: pieces, gather-and-select scan, merge (flat_lists_kernels.hip) ----
+static uint64_t flat_lists_forced_piece() { return env_u64("ALAYA_FLAT_LISTS_PIECE"); }
+
+// Every pointer is a device pointer; nothing is read back and the host waits for nothing: the piece table of a
+// launch is sized from `total` and the launch's query count alone.
+static void do_flat_lists(alaya_index *ix, const float *d_q, uint64_t nq, uint32_t k, const int64_t *d_lims,
+                          const uint32_t *d_cand, uint64_t total, uint32_t *d_ids, float *d_dists, hipStream_t stream) {
+  using namespace alaya_amd;
+  if (!ix->base.ptr) throw ArgError("index has no base vectors");
+  if (ix->generic) throw ArgError("flat lists search: float32 rows only");
+  if (k == 0 || k > kListsMaxK) throw ArgError("flat lists search: k must be in 1..224");
+  if (nq == 0) return;
+  if (nq > 0xffffffffull) throw ArgError("flat lists search: too many queries");
+  const FlatListsPlan plan = flat_lists_plan(total, nq, k, ix->stride, static_cast<uint32_t>(stream_cus(ix, stream)),
+                                             flat_lists_forced_piece());
+  if (plan.sub_queries == 0) throw ArgError("flat lists search: k / dim too large for the LDS budget, or the lists too long");
+  if (plan.table > 0x7fffffffull) throw ArgError("flat lists search: too many pieces for one launch");
+  scratch_acquire(ix, stream);
+  // (a buffer that grows is freed first, which waits for the launches that still read it)
+  ix->fl_first.reserve((plan.sub_queries + 1) * 8);
+  ix->fl_table.reserve(plan.table * sizeof(FlatListsPiece));
+  ix->ff_part_d.reserve(plan.partial_bytes / 2);
+  ix->ff_part_i.reserve(plan.partial_bytes / 2);
+  FlatListsParams p{};
+  p.base = ix->base.as<float>();
+  p.n = ix->n;
+  p.valid = ix->has_valid ? ix->valid.as<uint32_t>() : nullptr;
+  p.dim = ix->dim;
+  p.stride = ix->stride;
+  p.ip = ix->metric == ALAYA_METRIC_L2 ? 0 : 1;
+  p.queries = d_q;
+  p.q_stride = ix->dim;
+  p.lims = d_lims;
+  p.ids = d_cand;
+  p.total = total;
+  p.piece = static_cast<uint32_t>(plan.piece);
+  p.k = k;
+  p.first_piece = ix->fl_first.as<uint64_t>();
+  p.pieces = ix->fl_table.as<FlatListsPiece>();
+  p.part_d = ix->ff_part_d.as<float>();
+  p.part_i = ix->ff_part_i.as<uint32_t>();
+  p.out_ids = d_ids;
+  p.out_dists = d_dists;
+  for (uint64_t sb = 0; sb < nq; sb += plan.sub_queries) {
+    p.q_first = sb;
+    p.nq = std::min<uint64_t>(plan.sub_queries, nq - sb);
+    p.table = total / plan.piece + p.nq;
+    hip_check(launch_flat_lists_pieces(p, stream), "flat lists pieces");
+    hip_check(launch_flat_lists_scan(p, stream), "flat lists scan");
+    hip_check(launch_flat_lists_merge(p, stream), "flat lists merge");
+  }
+  scratch_release(ix, stream);
+  ix->fl_last[0] = total;
+  ix->fl_last[1] = plan.piece;
+  ix->fl_last[2] = plan.table;
+  ix->fl_last[3] = plan.launches;
+}
+
+int alaya_index_flat_search_lists_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k,
+                                         const int64_t *d_lims, const uint32_t *d_cand_ids, uint64_t total,
+                                         uint32_t *d_ids, float *d_dists, void *stream) {
+  return guarded([&] {
+    if (!ix || (nq && (!d_queries || !d_ids || !d_lims)) || (total && !d_cand_ids)) throw ArgError("invalid arguments");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    do_flat_lists(ix, d_queries, nq, k, d_lims, d_cand_ids, total, d_ids, d_dists, static_cast<hipStream_t>(stream));
+  });
+}
+
+int alaya_index_flat_search_lists(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, const int64_t *lims,
+                                  const uint32_t *cand_ids, uint32_t *ids, float *dists) {
+  return guarded([&] {
+    if (!ix || (nq && (!queries || !ids || !lims))) throw ArgError("invalid arguments");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    set_device(ix);
+    if (k == 0 || k > 224) throw ArgError("flat lists search: k must be in 1..224");
+    if (nq == 0) return;
+    if (lims[0] != 0) throw ArgError("flat lists search: lims[0] must be 0");
+    for (uint64_t i = 0; i < nq; ++i)
+      if (lims[i + 1] < lims[i]) throw ArgError("flat lists search: lims must not decrease");
+    const uint64_t total = static_cast<uint64_t>(lims[nq]);
+    if (total && !cand_ids) throw ArgError("invalid arguments");
+    for (uint64_t e = 0; e < total; ++e)
+      if (cand_ids[e] >= ix->n) throw ArgError("flat lists search: a candidate id is past the index's rows");
+    scratch_acquire(ix, ix->stream);  // the upload buffers below are the index's, shared with other launches
+    const float *d_q = stage_queries(ix, queries, nq, k, "upload queries", /*dists=*/true, /*counters=*/false);
+    ix->fl_lims.reserve((nq + 1) * 8);
+    ix->fl_ids.reserve(total * 4);
+    hip_check(hipMemcpyAsync(ix->fl_lims.ptr, lims, (nq + 1) * 8, hipMemcpyHostToDevice, ix->stream), "upload lims");
+    if (total) hip_check(hipMemcpyAsync(ix->fl_ids.ptr, cand_ids, total * 4, hipMemcpyHostToDevice, ix->stream), "upload candidates");
+    do_flat_lists(ix, d_q, nq, k, ix->fl_lims.as<int64_t>(), ix->fl_ids.as<uint32_t>(), total, ix->id_buf.as<uint32_t>(),
+                  ix->dist_buf.as<float>(), ix->stream);
+    fetch_results(ix, nq, k, ids, dists, nullptr);
+    stream_sync(ix, "flat lists search");
+  });
+}
+
+int alaya_index_flat_lists_last(const alaya_index *ix, uint64_t *out) {
+  return guarded([&] {
+    if (!ix || !out) throw ArgError("invalid arguments");
+    std::memcpy(out, ix->fl_last, sizeof(ix->fl_last));
+  });
+}
+
+int alaya_flat_lists_plan(uint64_t total, uint64_t nq, uint32_t k, uint32_t stride, uint32_t cus, uint64_t *out) {
+  return guarded([&] {
+    if (!out) throw ArgError("invalid arguments");
+    if (k == 0 || k > alaya_amd::kListsMaxK) throw ArgError("flat lists plan: k must be in 1..224");
+    const alaya_amd::FlatListsPlan r = alaya_amd::flat_lists_plan(total, nq, k, stride, cus, flat_lists_forced_piece());
+    if (r.sub_queries == 0) throw ArgError("flat lists plan: k / dim too large for the LDS budget, or the lists too long");
+    out[0] = r.piece;
+    out[1] = r.table;
+    out[2] = r.sub_queries;
+    out[3] = r.partial_bytes;
+    out[4] = r.launches;
   });
 }
 

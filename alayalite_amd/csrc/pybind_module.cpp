@@ -79,6 +79,13 @@ struct Masks {
   U32Array indices;
 };
 
+// the shapes of a lists search's CSR arguments; the library checks their values
+void check_lists(const CArray<int64_t> &lims, const U32Array &ids, uint64_t nq) {
+  if (lims.ndim() != 1 || static_cast<uint64_t>(lims.shape(0)) != nq + 1) throw py::value_error("lims must be int64 [nq + 1]");
+  if (ids.ndim() != 1 || static_cast<int64_t>(ids.shape(0)) != lims.data()[nq])
+    throw py::value_error("ids must be uint32 [lims[nq]]");
+}
+
 Masks parse_masks(const U32Array &allow_words, const py::object &mask_of_query, uint64_t n, uint64_t nq) {
   if (allow_words.ndim() != 2 || static_cast<uint64_t>(allow_words.shape(1)) != (n + 31) / 32 || allow_words.shape(0) < 1)
     throw py::value_error("allow_words must be uint32 [n_masks, ceil(n / 32)]");
@@ -407,6 +414,25 @@ class PyIndexInterface : public LaunchControls {
       py::gil_scoped_release nogil;
       check(alaya_index_flat_search_filtered(ix_, static_cast<const float *>(q.data()), nq, topk, m.words, m.n_masks,
                                              m.of_query, ids32.data(), dists.mutable_data()));
+    }
+    return py::make_tuple(widen_ids(ids32, nq, topk, true), dists);
+  }
+
+  // --- extra (not in the reference binding): exact_search over the candidate rows each query lists itself
+  // (alaya_index_flat_search_lists).  lims: int64 [nq + 1], ids: uint32 [lims[nq]], query i's candidates
+  // ids[lims[i] .. lims[i + 1]); the query forms and the empty slots are exact_search's.  An SQ8 index is
+  // scanned on its f32 rows.
+  py::object exact_search_lists(py::array queries, uint32_t topk, CArray<int64_t> lims, U32Array ids) {
+    if (!graph_) throw std::runtime_error("Index is not init yet");
+    py::array q = prepare_queries(queries);
+    const uint64_t nq = q.shape(0);
+    check_lists(lims, ids, nq);
+    std::vector<uint32_t> ids32(nq * topk);
+    py::array_t<float> dists = out2d<float>(nq, topk);
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_flat_search_lists(ix_, static_cast<const float *>(q.data()), nq, topk, lims.data(), ids.data(),
+                                          ids32.data(), dists.mutable_data()));
     }
     return py::make_tuple(widen_ids(ids32, nq, topk, true), dists);
   }
@@ -1441,6 +1467,37 @@ class DeviceIndex : public LaunchControls {
                                                   n_masks, dptr<const uint32_t>(mask_of_query), dptr<uint32_t>(ids),
                                                   dptr<float>(dists), dptr<void>(stream)));
   }
+  // the exact k nearest among the valid rows each query lists itself (alaya_index_flat_search_lists): lims int64
+  // [nq + 1], ids uint32 [lims[nq]]
+  py::tuple flat_search_lists(F32Array q, uint32_t k, CArray<int64_t> lims, U32Array cand) {
+    const uint64_t nq = q.shape(0);
+    check_lists(lims, cand, nq);
+    py::array_t<uint32_t> ids = out2d<uint32_t>(nq, k);
+    py::array_t<float> d = out2d<float>(nq, k);
+    const float *qp = q.data();
+    const int64_t *lp = lims.data();
+    const uint32_t *cp = cand.data();
+    uint32_t *ip = ids.mutable_data();
+    float *dp = d.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      check(alaya_index_flat_search_lists(ix_, qp, nq, k, lp, cp, ip, dp));
+    }
+    return py::make_tuple(ids, d);
+  }
+  // the same on device pointers; total: the entries of `cand`.  Never waits on the stream.
+  void flat_search_lists_device(uintptr_t q, uint64_t nq, uint32_t k, uintptr_t lims, uintptr_t cand, uint64_t total,
+                                uintptr_t ids, uintptr_t dists, uintptr_t stream) {
+    check(alaya_index_flat_search_lists_device(ix_, dptr<const float>(q), nq, k, dptr<const int64_t>(lims),
+                                               dptr<const uint32_t>(cand), total, dptr<uint32_t>(ids), dptr<float>(dists),
+                                               dptr<void>(stream)));
+  }
+  // of the last lists search: (list entries, entries per piece, piece-table entries of a launch, launches)
+  py::tuple flat_lists_last() const {
+    uint64_t o[4] = {0, 0, 0, 0};
+    check(alaya_index_flat_lists_last(ix_, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3]);
+  }
   // (allowed valid rows over the masks, row chunks of the last scan, its query tile, scan launches)
   py::tuple flat_filtered_last() const {
     uint64_t o[4] = {0, 0, 0, 0};
@@ -1614,6 +1671,8 @@ PYBIND11_MODULE(_alayalitepy, m) {
       .def("exact_search", &PyIndexInterface::exact_search, py::arg("queries"), py::arg("topk"))
       .def("exact_search_filtered", &PyIndexInterface::exact_search_filtered, py::arg("queries"), py::arg("topk"),
            py::arg("allow_words"), py::arg("mask_of_query") = py::none())
+      .def("exact_search_lists", &PyIndexInterface::exact_search_lists, py::arg("queries"), py::arg("topk"),
+           py::arg("lims"), py::arg("ids"))
       .def("exact_range_search", &PyIndexInterface::exact_range_search, py::arg("queries"), py::arg("radius"),
            py::arg("max_results"), py::arg("allow_words") = py::none(), py::arg("mask_of_query") = py::none())
       .def("save", &PyIndexInterface::save, py::arg("index_path"), py::arg("data_path"),
@@ -1714,7 +1773,11 @@ PYBIND11_MODULE(_alayalitepy, m) {
            py::arg("allow_words"), py::arg("mask_of_query") = py::none())
       .def("flat_search_filtered_device", &DeviceIndex::flat_search_filtered_device)
       .def("flat_filtered_last", &DeviceIndex::flat_filtered_last)
-      .def("flat_range_search", &DeviceIndex::flat_range_search, py::arg("queries"), py::arg("radii"),
+      .def("flat_search_lists", &DeviceIndex::flat_search_lists, py::arg("queries"), py::arg("k"), py::arg("lims"),
+           py::arg("ids"))
+      .def("flat_search_lists_device", &DeviceIndex::flat_search_lists_device)
+      .def("flat_lists_last", &DeviceIndex::flat_lists_last)
+      .def("flat_range_search",&DeviceIndex::flat_range_search, py::arg("queries"), py::arg("radii"),
            py::arg("max_results"), py::arg("words") = py::none(), py::arg("groups") = py::none())
       .def("flat_range_search_device", &DeviceIndex::flat_range_search_device)
       .def("flat_range_last", &DeviceIndex::flat_range_last)
@@ -1790,6 +1853,13 @@ PYBIND11_MODULE(_alayalitepy, m) {
     check(alaya_flat_filtered_plan(n_allowed, nq, k, stride, cus, o));
     return py::make_tuple(o[0], o[1], o[2], o[3], o[4]);
   }, py::arg("n_allowed"), py::arg("nq"), py::arg("k"), py::arg("stride"), py::arg("cus"));
+  // the lists scan's launch plan on the host (alaya_flat_lists_plan): (entries per piece, piece-table entries of
+  // a launch, queries per launch, partial-list bytes, launches)
+  m.def("flat_lists_plan", [](uint64_t total, uint64_t nq, uint32_t k, uint32_t stride, uint32_t cus) {
+    uint64_t o[5] = {0, 0, 0, 0, 0};
+    check(alaya_flat_lists_plan(total, nq, k, stride, cus, o));
+    return py::make_tuple(o[0], o[1], o[2], o[3], o[4]);
+  }, py::arg("total"), py::arg("nq"), py::arg("k"), py::arg("stride"), py::arg("cus"));
   // the MFMA filtered scan's launch plan (alaya_flat_filtered_mfma_plan), same fields as flat_filtered_plan
   m.def("flat_filtered_mfma_plan", [](uint64_t n, uint64_t nq, uint32_t k, uint32_t cus) {
     uint64_t o[5] = {0, 0, 0, 0, 0};

@@ -10,7 +10,7 @@ import numpy as np
 from ._native import PyIndexInterface as _PyIndexInterface
 from .common import VectorLike, VectorLikeBatch, _assert
 from .schema import IndexParams, load_schema
-from .utils import exact_range_args, pack_allow, range_csr
+from .utils import candidate_lists, exact_range_args, pack_allow, range_csr
 
 
 class Index:
@@ -143,7 +143,7 @@ class Index:
         """The underlying PyIndexInterface (device counters, graph arrays, tuning)."""
         return self.__index
 
-    def exact_search(self, queries: VectorLikeBatch, topk: int, allow=None, groups=None):
+    def exact_search(self, queries: VectorLikeBatch, topk: int, allow=None, groups=None, candidates=None, _chunk=None):
         """The exact top-k of each query over the rows the index holds (valid rows only, the index's
         metric in f32, ties by id): the flat MFMA search on the device rows -- the ground truth for
         the recall of ``batch_search`` at some ``ef_search``.  Returns (ids, distances); slots past the
@@ -165,8 +165,33 @@ class Index:
         allowed rows x queries: it is meant for small allowed shares, where the graph
         ``filtered_search`` loses recall.  Above the measured crossover (a few per cent of the rows,
         DESIGN.md section 3, Round 16) the graph ``filtered_search`` or the unmasked
-        ``exact_search`` is faster."""
+        ``exact_search`` is faster.
+
+        With ``candidates=(lims, ids)`` each query brings its own list of row ids in CSR form -- the union of
+        two retrievers' hits, a metadata filter evaluated per query, another index's answer: ``lims`` integers
+        of shape (nq + 1,), non-decreasing, ``lims[0] == 0``; query i's candidates are
+        ``ids[lims[i]:lims[i + 1]]``, any integer dtype, in any order, each below ``get_data_num()``.  The
+        answer is the masked call's: the exact top-k among the listed rows that are valid, by (distance, id),
+        same distance bits, same empty slots; a row listed several times counts once.  It excludes ``allow``,
+        and 1 <= topk <= 224.  Each listed row is gathered once per query that lists it, so the cost grows with
+        the entries ("Round 29"); one mask per query costs n / 8 bytes of mask and one
+        scan launch per query instead."""
         self._check_queries(queries, 2, "queries")
+        if candidates is not None:
+            _assert(allow is None and groups is None, "candidates and allow exclude each other")
+            _assert(1 <= topk <= 224, "topk must be in 1..224 with candidates")
+            nq = queries.shape[0]
+            lims, ids = candidate_lists(candidates, nq, self.get_data_num())
+            # chunks of queries: at most 2^26 result slots per call
+            step = max(1, (1 << 26) // topk) if _chunk is None else int(_chunk)
+            parts = [self.__index.exact_search_lists(queries[lo:lo + step], topk, lims[lo:lo + step + 1] - lims[lo],
+                                                     ids[lims[lo]:lims[min(nq, lo + step)]])
+                     for lo in range(0, nq, step)]
+            if len(parts) == 1:
+                return parts[0]
+            if not parts:
+                return np.zeros((0, topk), self.__params.id_type), np.zeros((0, topk), np.float32)
+            return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
         if allow is None:
             _assert(groups is None, "groups needs allow")
             return self.__index.exact_search(queries, topk)

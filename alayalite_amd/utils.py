@@ -48,7 +48,27 @@ def calc_gt(data, query, topk):
 _GT_METRICS = {"l2": 0, "ip": 1, "cos": 2}
 
 
-def calc_gt_device(data, query, topk, device=0, metric="l2", allow=None):
+def candidate_lists(candidates, nq, n):
+    """``candidates=(lims, ids)`` of ``Index.exact_search`` and ``calc_gt_device``, checked, as (lims int64,
+    ids uint32): ``lims`` integers of shape (nq + 1,), ``lims[0] == 0``, non-decreasing; ``ids`` integers of shape
+    (lims[nq],), each in [0, n)."""
+    if not isinstance(candidates, (tuple, list)) or len(candidates) != 2:
+        raise ValueError("candidates must be (lims, ids)")
+    lims, ids = np.asarray(candidates[0]), np.asarray(candidates[1])
+    if not (np.issubdtype(lims.dtype, np.integer) and (ids.size == 0 or np.issubdtype(ids.dtype, np.integer))):
+        raise ValueError("candidates must hold integers")
+    if lims.shape != (nq + 1,):
+        raise ValueError(f"lims must have shape (nq + 1,) = ({nq + 1},), got {lims.shape}")
+    if int(lims[0]) != 0 or (lims[1:] < lims[:-1]).any():
+        raise ValueError("lims must start at 0 and not decrease")
+    if ids.shape != (int(lims[-1]),):
+        raise ValueError(f"ids must have shape (lims[nq],) = ({int(lims[-1])},), got {ids.shape}")
+    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+        raise ValueError(f"candidate ids must be in [0, {n})")
+    return np.ascontiguousarray(lims, np.int64), np.ascontiguousarray(ids, np.uint32)
+
+
+def calc_gt_device(data, query, topk, device=0, metric="l2", allow=None, candidates=None):
     """Exact top-k on the MI355X: the flat MFMA path (IndexType::FLAT has no implementation in the
     reference; this is its exact search, find_exact_gt in include/utils/evaluate.hpp:29-62: the f32
     l2_sqr metric, ties by id).  Any dimension, 1 <= topk <= 2048 (above 224, and without ``allow``,
@@ -61,18 +81,31 @@ def calc_gt_device(data, query, topk, device=0, metric="l2", allow=None):
     the same ids and distance bits as ``calc_gt_device(data[rows], ...)`` mapped through
     ``rows = nonzero(allow)``, slots past the allowed rows (-1, FLT_MAX), without a second copy of
     the rows -- a scan of the allowed rows, meant for small allowed shares; above a few per cent
-    the unmasked call on a sub-base is faster."""
+    the unmasked call on a sub-base is faster.
+
+    ``candidates=(lims, ids)`` (CSR, as ``Index.exact_search`` takes them; not with ``allow``) restricts query
+    i's answer to the rows ``ids[lims[i]:lims[i + 1]]``, each counted once: a gather of those rows,
+    1 <= topk <= 224."""
     if metric not in _GT_METRICS:
         raise ValueError(f"metric must be one of {sorted(_GT_METRICS)}, got {metric!r}")
+    if allow is not None and candidates is not None:
+        raise ValueError("candidates and allow exclude each other")
     from . import _native
 
     data = np.ascontiguousarray(data, dtype=np.float32)
     query = np.ascontiguousarray(query, dtype=np.float32)
+    if candidates is not None:
+        if not 1 <= int(topk) <= 224:
+            raise ValueError(f"topk must be in 1..224 with candidates, got {topk}")
+        candidates = candidate_lists(candidates, query.shape[0], data.shape[0])
     if metric == "cos":
         data = _native._ext.normalize_rows(data)
         query = _native._ext.normalize_rows(query)
     ix = _native._ext.DeviceIndex(device)
     ix.set_base(data, _GT_METRICS[metric])
+    if candidates is not None:
+        ids, dists = ix.flat_search_lists(query, topk, *candidates)
+        return ids.astype(np.int32), dists
     if allow is not None:
         allow = np.asarray(allow)
         if allow.ndim != 1:

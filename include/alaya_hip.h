@@ -547,6 +547,50 @@ int alaya_flat_filtered_mfma_plan(uint64_t n, uint64_t nq, uint32_t k, uint32_t 
  * outside 1..224 or the rows are too wide for the LDS. */
 int alaya_flat_filtered_plan(uint64_t n_allowed, uint64_t nq, uint32_t k, uint32_t stride, uint32_t cus,
                              uint64_t *out);
+/* ---- exact k-NN over per-query candidate lists: a gather-and-select scan ---------------------------
+ * Stands in for find_exact_gt (include/utils/evaluate.hpp:29-62) over a row set that each query names itself --
+ * the union of two retrievers' hits, a per-query metadata filter, another index's answer.  The lists are CSR:
+ * lims (int64, nq + 1 entries, lims[0] == 0, non-decreasing) and cand_ids (uint32, lims[nq] entries); query i's
+ * candidates are cand_ids[lims[i] .. lims[i + 1]), in any order.  Row i of ids / dists (nq x k, 1 <= k <= 224)
+ * holds the candidates that count, ordered by (distance, id), the first k of them; the remaining slots hold
+ * (0xffffffff, FLT_MAX), alaya_index_flat_search's convention.
+ * 1. Distance: the index's metric in f32 in the reference's order from the start (l2_sqr_avx2; ip_sqr_avx2
+ *    negated for IP and COS, the caller having normalised rows and queries for COS) -- the bits of
+ *    alaya_index_flat_search_filtered and alaya_index_distances.  Nothing is approximate, flagged or recomputed.
+ * 2. A candidate counts when its row is valid (the validity bitmap): removed rows are skipped.
+ * 3. A candidate id that appears several times in one list counts once.
+ * 4. Ids >= n: the host entry returns ALAYA_ERR_ARG.  The device entry cannot check without a read-back: its
+ *    kernel skips such ids and never forms an address from them -- every row load is behind id < n.
+ * 5. lims: the host entry checks them (ALAYA_ERR_ARG).  On the device a decreasing pair is an empty list and
+ *    ends are clamped to [0, total]; lims that are not non-decreasing can name more than `total` entries, and
+ *    lists past the launch's piece table (total / piece + queries entries) are then cut short -- nothing is
+ *    read or written out of bounds.
+ * 6. No graph is needed; an index with SQ8 codes is scanned on its f32 rows; ALAYA_DIST_GENERIC bases are
+ *    refused.
+ * 7. The result is a function of the inputs alone: not of the piece length, the grid, or how a batch is split
+ *    over launches.  Environment ALAYA_FLAT_LISTS_PIECE=r (diagnostics, read per call) forces the piece length.
+ * The lists are cut into pieces of at most `piece` entries; one wave gathers one piece's rows against that
+ * piece's query and keeps its k best, one wave per query merges its pieces.  No two queries share a row read:
+ * the work grows with the entries, at the speed of a gather of rows.  No workgroup waits for another. */
+int alaya_index_flat_search_lists(alaya_index *ix, const float *queries, uint64_t nq, uint32_t k, const int64_t *lims,
+                                  const uint32_t *cand_ids, uint32_t *ids, float *dists);
+/* Same on device buffers, launched on `stream`.  total: the entries of d_cand_ids, from the caller; the call
+ * never waits on `stream` and reads nothing back (rules 4 and 5), and when it returns its launches may still be
+ * running.  d_dists may be NULL. */
+int alaya_index_flat_search_lists_device(alaya_index *ix, const float *d_queries, uint64_t nq, uint32_t k,
+                                         const int64_t *d_lims, const uint32_t *d_cand_ids, uint64_t total,
+                                         uint32_t *d_ids, float *d_dists, void *stream);
+/* Introspection of the last call above: out[0] = list entries, out[1] = entries per piece, out[2] = piece-table
+ * entries of one launch, out[3] = launches. */
+int alaya_index_flat_lists_last(const alaya_index *ix, uint64_t *out);
+/* The launch plan as pure host arithmetic (no device): for `total` list entries, nq queries, k, rows of `stride`
+ * floats and `cus` compute units, out[0] = entries per piece (a multiple of the 8 candidates a wave takes per
+ * pass; ALAYA_FLAT_LISTS_PIECE rounded up to one), out[1] = piece-table entries of one launch =
+ * total / out[0] + out[2], a bound on its pieces that needs no look at lims, out[2] = queries per launch,
+ * out[3] = bytes of partial lists of one launch = 8 k out[1], at most 256 MiB unless the piece is forced,
+ * out[4] = launches (out[2] out[4] >= nq).  ALAYA_ERR_ARG if k is outside 1..224 or the rows are too wide for
+ * the LDS. */
+int alaya_flat_lists_plan(uint64_t total, uint64_t nq, uint32_t k, uint32_t stride, uint32_t cus, uint64_t *out);
 /* ---- exact range search: every eligible row within a radius, by a scan of the rows ---------------
  * The exact counterpart of alaya_index_range_search (no reference counterpart: find_exact_gt,
  * include/utils/evaluate.hpp:29-62, keeps the k nearest).  For query i with radius r_i = radii[i] and cap

@@ -1,6 +1,6 @@
 """Filtered graph search on a GIST-shaped device-built index: rate and recall per allowed share.
 
-usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact|mfma|through|screen] [--n 1000000] [--nq 1000] [--ef 387]
+usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact|mfma|through|screen|lists] [--n 1000000] [--nq 1000] [--ef 387]
                                     [--shares 1,0.5,0.1,0.01] [--reps 20] [--out FILE]
 
   sweep     per share of allowed rows: queries/s of DeviceIndex.filtered_search_device, recall@10 of its
@@ -51,6 +51,12 @@ usage: python tools/filter_sweep.py [--leg sweep|filtered|plain|sq8|sq8-ab|exact
             whether ids, distance bits and counters are equal, the launch's screen counts, both plans and the
             recall@10 over the allowed rows; last, for orientation, the unfiltered batch search of the same
             index with ALAYA_SEARCH_SCOUT=0 and as the environment plans it.
+  lists     exact k-NN over per-query candidate lists (DeviceIndex.flat_search_lists_device: pieces, scan and merge
+            together, --nq queries with --lens random ids each) alternated in one process with what a caller had
+            before it, flat_search_filtered_device with one mask per query over the same sets (the first
+            --mask-queries queries, once per round): --rounds rounds of --reps launches after a warm-up, times,
+            medians, spreads, microseconds per query of both and their ratio, whether ids and distance bits are
+            equal, the bytes of the listed rows over the call's time, and the plan.
 Every leg prints one JSON line per measurement; --out appends them to a file."""
 import argparse
 import json
@@ -378,6 +384,76 @@ def mfma_leg(args):
         emit(dict(leg="mfma-crossover", k=k, shares_won=won, faster_from_share=won[0] if won else None))
 
 
+def lists_leg(args):
+    """Exact k-NN over per-query candidate lists against one mask per query over the same sets."""
+    import torch
+    from alayalite_amd import _native
+    from alayalite_amd.utils import pack_allow
+    from workloads.datasets import gist_like
+
+    ext = _native._ext
+    st = torch.cuda.current_stream()
+    n, nq, nm = args.n, args.nq, min(args.nq, args.mask_queries)
+    base, queries = gist_like(n, nq, dim=args.dim)
+    dev = ext.DeviceIndex(0)
+    dev.set_base(base, 0)
+    qd = torch.from_numpy(np.ascontiguousarray(queries)).cuda()
+    out = {m: (torch.empty((nq, K), dtype=torch.int32, device="cuda"), torch.empty((nq, K), dtype=torch.float32, device="cuda"))
+           for m in ("lists", "masks")}
+    groups = torch.arange(nm, dtype=torch.int32, device="cuda")
+
+    def emit(rec):
+        rec.update(n=n, nq=nq, dim=args.dim, metric="l2", k=K)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    def timed(run, reps):
+        run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(reps):
+            run()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    for length in [int(v) for v in args.lens.split(",")]:
+        cand = np.random.default_rng(length).integers(0, n, (nq, length), dtype=np.uint32)
+        lims = torch.arange(nq + 1, dtype=torch.int64, device="cuda") * length
+        cd = torch.from_numpy(cand.view(np.int32).reshape(-1)).cuda()
+        allow = np.zeros((nm, n), bool)  # what a caller has today: one mask per query, the first nm queries
+        np.put_along_axis(allow, cand[:nm].astype(np.int64), True, axis=1)
+        words = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+
+        def lists():
+            dev.flat_search_lists_device(qd.data_ptr(), nq, K, lims.data_ptr(), cd.data_ptr(), nq * length,
+                                         out["lists"][0].data_ptr(), out["lists"][1].data_ptr(), st.cuda_stream)
+
+        def masks():
+            dev.flat_search_filtered_device(qd.data_ptr(), nm, K, words.data_ptr(), nm, groups.data_ptr(),
+                                            out["masks"][0].data_ptr(), out["masks"][1].data_ptr(), st.cuda_stream)
+
+        ms = {"lists": [], "masks": []}
+        for _ in range(args.rounds):  # alternated: same rows, queries and clocks
+            ms["lists"].append(timed(lists, args.reps))
+            ms["masks"].append(timed(masks, 1))
+        med = {m: float(np.median(v)) for m, v in ms.items()}
+        same = all(bool(torch.equal(out["lists"][j][:nm], out["masks"][j][:nm])) for j in (0, 1))
+        gathered = float(nq) * length * base.shape[1] * 4
+        emit(dict(leg="lists", entries_per_query=length, lists_ms=sorted(ms["lists"]), masks_ms=sorted(ms["masks"]),
+                  mask_queries=nm, lists_median=med["lists"], masks_median=med["masks"],
+                  lists_spread=(max(ms["lists"]) - min(ms["lists"])) / med["lists"],
+                  masks_spread=(max(ms["masks"]) - min(ms["masks"])) / med["masks"],
+                  lists_us_per_query=1e3 * med["lists"] / nq, masks_us_per_query=1e3 * med["masks"] / nm,
+                  masks_over_lists_per_query=(med["masks"] / nm) / (med["lists"] / nq), ids_and_bits_equal=same,
+                  # the whole call over the bytes of the listed rows: pieces, scan and merge together
+                  gathered_gb=gathered / 1e9, gather_tb_per_s=gathered / (med["lists"] * 1e-3) / 1e12,
+                  plan=[int(v) for v in dev.flat_lists_last()]))
+
+
 def through_leg(args):
     """The through search against the plain filtered search and the exact filtered scan, alternated."""
     import torch
@@ -583,7 +659,7 @@ def screen_leg(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact", "mfma", "through", "screen"),
+    ap.add_argument("--leg", choices=("sweep", "filtered", "plain", "sq8", "sq8-ab", "exact", "mfma", "through", "screen", "lists"),
                     default="sweep")
     ap.add_argument("--space", choices=("f32", "sq8"), default="f32",
                     help="exact leg: f32 = GIST-shaped L2 rows; sq8 = config 5's text-like IP rows with SQ8 codes")
@@ -595,6 +671,8 @@ def main():
     ap.add_argument("--shares", default="", help="default 1,0.5,0.1,0.01 (exact leg: 0.001,0.01,0.05,0.1,0.2,0.5,1)")
     ap.add_argument("--hop-ladder", default="10,16,24,32,48,64,96,128,192,256", help="through leg: the short ef sweep")
     ap.add_argument("--ks", default="10,100", help="mfma leg: the k values")
+    ap.add_argument("--lens", default="1000,10000,100000", help="lists leg: candidate ids per query")
+    ap.add_argument("--mask-queries", type=int, default=100, help="lists leg: queries of the one-mask-per-query call")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default="")
@@ -608,6 +686,9 @@ def main():
         args.shares = args.shares or "0.05,0.1,0.2,0.5,1"
         args.dim = args.dim or 960
         return mfma_leg(args)
+    if args.leg == "lists":
+        args.dim = args.dim or 960
+        return lists_leg(args)
     if args.leg == "through":
         args.shares = args.shares or "1,0.5,0.2,0.1,0.05,0.02,0.01"
         args.dim = args.dim or 960
